@@ -46,6 +46,10 @@ group; the frame leg renders this rank's rows only): the GPU pool admits at most
 
 Synthetic inputs: lego camera geometry, pose_spherical(0,-30,4), 4096 pixels from
 RandomState(0), Xavier(seed 0) weights with the density head x20, counter-based jitter seed 0.
+
+--dump-outputs DIR: what the LAST timed step returned to its caller (render_rays' rgb_c [n,3], disp_c [n], rgb_f [n,3], disp_f [n] of
+the headline batch), copied off the device right after the timed steps and written as DIR/<name>.npy in float32 (DIR/<name>.rank<R>.npy
+on each rank of an N > 1 run: its own shard).  The inputs are fixed by the seeds above, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -108,7 +112,20 @@ def parse():
     ap.add_argument("--no-small-batch", action="store_true", help="skip the 256..2048-ray legs (N = 1)")
     ap.add_argument("--no-bf16-leg", action="store_true", help="skip the bf16 leg (BASELINE config #5) of the default fp32 run")
     ap.add_argument("--no-f16s-leg", action="store_true", help="skip the split-precision (f16 hi + lo operands, fp32-grade results) leg of the default fp32 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rgb_c, disp_c, rgb_f, disp_f) as DIR/<name>.npy, float32")
     return ap.parse_args()
+
+
+OUTPUT_NAMES = ("rgb_c", "disp_c", "rgb_f", "disp_f")       # render_rays' outputs, in the order of a batch's `out`
+
+
+def write_outputs(out_dir: str, arrays: dict, rank=None) -> None:
+    """--dump-outputs: DIR/<name>.npy in float32 (DIR/<name>.rank<R>.npy when `rank` is given: one rank's shard of an N > 1 run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ("" if rank is None else f".rank{rank}") + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -463,9 +480,16 @@ def worker(args) -> None:
     strong = make_batch(first_s, n_s)
     weak = strong if world == 1 else make_batch(rank * N_RAYS, N_RAYS)
     value = value_weak = ms_strong = ms_weak = ms_median = None
+    last_out = None                                                   # --dump-outputs: the headline batch's outputs of its last timed step
+
+    def snapshot(b):
+        return {k: t.cpu().numpy() for k, t in zip(OUTPUT_NAMES, b.out)}
+
     if args.scaling in ("strong", "both") or world == 1:
         el = timed_steps(strong, args.warmup, args.steps)
         value, ms_strong = N_RAYS * args.steps / el, 1e3 * el / args.steps
+        if args.dump_outputs:
+            last_out = snapshot(strong)
         ms_median = median_step_ms(strong, max(args.steps, 3))
         assert torch.isfinite(strong.out[2]).all()
     if world == 1:
@@ -473,6 +497,8 @@ def worker(args) -> None:
     elif args.scaling in ("weak", "both"):
         el = timed_steps(weak, args.warmup, args.steps)
         value_weak, ms_weak = world * N_RAYS * args.steps / el, 1e3 * el / args.steps
+        if args.dump_outputs and last_out is None:                   # no strong leg: the weak batch is the headline's
+            last_out = snapshot(weak)
         if ms_median is None:
             ms_median = median_step_ms(weak, max(args.steps, 3))
         assert torch.isfinite(weak.out[2]).all()
@@ -921,6 +947,8 @@ def worker(args) -> None:
                          f"{n_cpu} rays of the same 4096-ray batch (the reference's chunk size), median of {len(reps)} rep(s), {spent:.0f} s of CPU work; "
                          "SURVEY section 6 timed the reference itself at 691 rays/s on 8 vCPU of the build container"}
 
+    if last_out is not None:
+        write_outputs(args.dump_outputs, last_out, rank if world > 1 else None)
     if rank == 0 or solo:
         head_value = value if headline_strong else value_weak
         head_ms = ms_strong if headline_strong else ms_weak
@@ -991,6 +1019,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_workers(args.gpus))             # before anything in this process touches the GPU
     worker(args)

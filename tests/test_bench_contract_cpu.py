@@ -122,3 +122,12 @@ def test_worker_exit_status():
     assert bench.exit_status(False, "gloo", 4, {"distinct_devices": 1}) == 0
     assert bench.exit_status(False, "nccl", 1, None) == 0
     assert bench.exit_status(True, "nccl", 8, {"distinct_devices": 8}) == bench.EXIT_C_ABI_HUNG == 75
+
+
+def test_steps_below_one_is_refused():
+    """`ms_per_step` is the timed window over --steps: a run with no timed step is refused before any worker starts."""
+    import subprocess
+    import sys
+    for args in (["--steps", "0"], ["--steps", "1", "--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and not r.stdout.strip(), args

@@ -204,3 +204,22 @@ def test_bench_one_rank_of_eight_alone(workload, rank):
     assert "collective" not in j
     assert j["value"] > 0 and j["value_weak"] > 0 and j["frame_ms"] > 0
     assert j["bf16"]["rays_per_s"] > 0 and 0 < j["roofline"]["frac"] <= 1.0
+
+
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_are_what_the_timed_step_returned(packed, tmp_path):
+    """`bench.py --dump-outputs DIR`: the four arrays render_rays hands its caller in the last timed step, float32, bit-equal to the
+    same call made here on the bench's inputs (weights seed 0, lego pose, pixels of RandomState(0), jitter seed 0); `steps` is --steps."""
+    j = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "0", "--no-cpu-baseline", "--train-steps", "0", "--no-small-batch",
+                "--no-bf16-leg", "--no-f16s-leg", "--dump-outputs", str(tmp_path)], {})
+    assert j["steps"] == 2 and j["ms_per_step"] > 0
+    K, H, W, _, opts = _scene("lego")
+    pix = torch.from_numpy(synthetic.pixel_batch(H, W, 4096, 0)).to(DEV)
+    o, d = ops.make_o_d_pixels(W, H, K, synthetic.pose_spherical(0.0, -30.0, 4.0), pix)
+    rays = torch.cat([o, d], -1).contiguous()
+    want = ops.render_rays(packed.net, packed.coarse, packed.fine, ops.render_cfg(opts.near, opts.far, SC, NF, False, False, seed=0, ray_offset=0),
+                           rays, None, None)[:4]
+    assert sorted(os.listdir(tmp_path)) == ["disp_c.npy", "disp_f.npy", "rgb_c.npy", "rgb_f.npy"]
+    for name, t in zip(("rgb_c", "disp_c", "rgb_f", "disp_f"), want):
+        got = np.load(os.path.join(tmp_path, name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, t.cpu().numpy()), name
