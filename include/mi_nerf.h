@@ -39,6 +39,17 @@ extern "C" {
                                        mi_nerf_pack_weights_f16s), FINE network in bf16 (packed_fine from mi_nerf_pack_weights_bf16):
                                        the fine sample positions come out fp32-grade, the 3/4 of the evaluations that the fine network
                                        makes run at the bf16 rate                                                                     */
+                                    /* 7: reserved; refused                                                                            */
+#define MI_NERF_MODE_F16 8          /* f16 MFMA, one MFMA per product (the bf16 kernel on f16 operands: 8x finer rounding at the bf16
+                                       rate): BOTH networks; blobs of mi_nerf_pack_weights_f16s (its hi halves are read), so the
+                                       split-precision RANGE CONTRACT below holds as it is.  W = 256.  Also the one-network mode of
+                                       mi_nerf_time_mlp_rays (the f16 network alone)                                                  */
+#define MI_NERF_MODE_F16_BF16 9     /* mi_nerf_render_rays only: COARSE network in f16 (packed_coarse from mi_nerf_pack_weights_f16s),
+                                       FINE network in bf16 (packed_fine from mi_nerf_pack_weights_bf16): BASELINE config #5 at 1.07 x
+                                       the all-bf16 step time (MI_NERF_MODE_F16S_BF16: 1.63 x), but NOT within 0.05 dB of fp32 on every
+                                       scene (-0.08 dB on a long-trained sharp one, where mode 6 gives -0.004 dB): INTEGRATION.md    */
+/* Modes 8 and 9 are a compatible extension of ABI 4 (MI_NERF_ABI_VERSION stays 4): a library that predates them answers MI_NERF_EINVAL
+ * with a message naming MI_NERF_MODE_, as it does for every value it does not know. */
 
 /* status codes */
 #define MI_NERF_OK 0

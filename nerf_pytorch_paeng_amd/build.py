@@ -30,13 +30,14 @@ INCLUDE = os.path.join(ROOT, "include")
 SCRATCH = os.path.join(ROOT, "build_scratch")
 LIB = os.path.join(HERE, "libmi_nerf.so")
 STAMP = LIB + ".stamp"
-SOURCES = ["api.hip", "stages.hip", "mlp_fp32.hip", "mlp_fp32_wide.hip", "mlp_bf16.hip", "mlp_f16s.hip", "mlp_f16s_stash.hip", "dgrad_f16s.hip", "mlp_train.hip", "frames.hip", "comm.hip", "pack.cpp"]
+SOURCES = ["api.hip", "stages.hip", "mlp_fp32.hip", "mlp_fp32_wide.hip", "mlp_bf16.hip", "mlp_f16.hip", "mlp_f16s.hip", "mlp_f16s_stash.hip", "dgrad_f16s.hip", "mlp_train.hip", "frames.hip", "comm.hip", "pack.cpp"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          # the MLP kernel's register-resident design needs its k-loops FULLY unrolled (static register indices)
          "-mllvm", "-pragma-unroll-threshold=1000000"]
-# mlp_bf16.hip manages the whole AGPR file by hand (explicit a[N] operands in asm statements): hipcc must not park spilled VGPRs there
-FILE_FLAGS = {"mlp_bf16.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "mlp_f16s.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"],
+# mlp_bf16.hip / mlp_f16.hip manage the whole AGPR file by hand (explicit a[N] operands in asm statements): hipcc must not park spilled VGPRs there
+FILE_FLAGS = {"mlp_bf16.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "mlp_f16.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"],
+              "mlp_f16s.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"],
               "mlp_f16s_stash.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "dgrad_f16s.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"]}
 
 

@@ -55,6 +55,9 @@ int mlp_rays_fp32(const mi_nerf_net*, const void*, const float*, const float*, i
 int mlp_embedded_fp32(const mi_nerf_net*, const void*, const float*, int64_t, float*, hipStream_t);
 int mlp_rays_bf16(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t, int points_per_wave, const StratDraw* strat,
                   FineDraw* fine = nullptr);
+int mlp_rays_f16(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t, int points_per_wave, const StratDraw* strat,
+                 FineDraw* fine);
+int check_net_f16_variant(const mi_nerf_net*);
 size_t packed_bytes_f16s(const mi_nerf_net*);
 int pack_f16s(const mi_nerf_net*, const mi_nerf_params*, void*, size_t);
 int mlp_rays_f16s(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t);
@@ -428,15 +431,20 @@ int mi_nerf_render_rays(const mi_nerf_net* net, const void* packed_c, const void
     const int Sc = cfg->Sc, St = cfg->Sc + cfg->Nf;
     // 1-a) stratified depths; 2-a) coarse net; 3-a) composite          (nerf_process.py:187-198)
     // t_rand / u NULL: the jitter is drawn inside the consuming kernels (cfg->seed, cfg->ray_offset + ray, sample)
-    MN_CHECK_ARG(cfg->mode >= MI_NERF_MODE_F32 && cfg->mode <= MI_NERF_MODE_F16S_BF16, "mode must be one of MI_NERF_MODE_* (0..6; got %d)", cfg->mode);
+    MN_CHECK_ARG((cfg->mode >= MI_NERF_MODE_F32 && cfg->mode <= MI_NERF_MODE_F16S_BF16) || cfg->mode == MI_NERF_MODE_F16 || cfg->mode == MI_NERF_MODE_F16_BF16,
+                 "mode must be one of MI_NERF_MODE_* (0..6, 8, 9; got %d)", cfg->mode);
     const int ppw = bf16_points_per_wave(cfg->mode);
-    // per network: which kernel family evaluates it (MI_NERF_MODE_F16S_BF16: coarse in split precision, fine in bf16)
+    // per network: which kernel family evaluates it (MI_NERF_MODE_F16S_BF16 / MI_NERF_MODE_F16_BF16: coarse in split precision / f16, fine in bf16)
     const bool coarse_f16s = cfg->mode == MI_NERF_MODE_F16S || cfg->mode == MI_NERF_MODE_F16S_BF16;
     const bool fine_f16s = cfg->mode == MI_NERF_MODE_F16S;
+    const bool coarse_f16 = cfg->mode == MI_NERF_MODE_F16 || cfg->mode == MI_NERF_MODE_F16_BF16;
+    const bool fine_f16 = cfg->mode == MI_NERF_MODE_F16;
     const bool coarse_bf16 = mode_is_bf16(cfg->mode);
-    const bool fine_bf16 = mode_is_bf16(cfg->mode) || cfg->mode == MI_NERF_MODE_F16S_BF16;
+    const bool fine_bf16 = mode_is_bf16(cfg->mode) || cfg->mode == MI_NERF_MODE_F16S_BF16 || cfg->mode == MI_NERF_MODE_F16_BF16;
+    if (coarse_f16)
+        if (int rc = check_net_f16_variant(net)) return rc;                // before any launch: both networks of these modes are 256 wide
     FineDraw fd{};
-    if (coarse_bf16) {
+    if (coarse_bf16 || coarse_f16) {
         // the bf16 kernel draws the stratified depths in its own prologue and writes z_c (one launch fewer: at a 512-ray shard a
         // launch is ~4 us of a ~130 us step)
         // ... and, for a small shard (one 32-point unit per wave: <= 512 rays on 256 CUs), render_rays' middle as well: `fd.taken`
@@ -445,7 +453,8 @@ int mi_nerf_render_rays(const mi_nerf_net* net, const void* packed_c, const void
             MN_CHECK_ARG(packed_f && rgb_f && disp_f, "fine pass needs packed_fine and outputs");
             fd = FineDraw{cfg->Nf, cfg->det, u, cfg->seed, cfg->ray_offset, rgb_c, disp_c, wts_c, (float*)(w + L.z_f), false};
         }
-        if (int rc = mlp_rays_bf16(net, packed_c, rays, nullptr, n, Sc, raw_c, st, ppw, &sd, cfg->Nf > 0 && ppw == 0 ? &fd : nullptr)) return rc;
+        if (int rc = (coarse_f16 ? mlp_rays_f16 : mlp_rays_bf16)(net, packed_c, rays, nullptr, n, Sc, raw_c, st, ppw, &sd, cfg->Nf > 0 && ppw == 0 ? &fd : nullptr))
+            return rc;
     } else {
         if (int rc = stage_stratified(n, Sc, cfg->near_, cfg->far_, t_rand, cfg->seed, cfg->ray_offset, z_c, st)) return rc;
         if (int rc = coarse_f16s ? mlp_rays_f16s(net, packed_c, rays, z_c, n, Sc, raw_c, st) : mlp_rays_fp32(net, packed_c, rays, z_c, n, Sc, raw_c, st)) return rc;
@@ -459,6 +468,7 @@ int mi_nerf_render_rays(const mi_nerf_net* net, const void* packed_c, const void
             if (int rc = stage_composite_fine_z(raw_c, z_c, rays, n, Sc, cfg->Nf, cfg->det, u, cfg->seed, cfg->ray_offset, rgb_c, disp_c, wts_c, z_f, st))
                 return rc;
         if (int rc = fine_f16s ? mlp_rays_f16s(net, packed_f, rays, z_f, n, St, raw_f, st)
+                          : fine_f16 ? mlp_rays_f16(net, packed_f, rays, z_f, n, St, raw_f, st, ppw, nullptr, nullptr)
                           : fine_bf16 ? mlp_rays_bf16(net, packed_f, rays, z_f, n, St, raw_f, st, ppw, nullptr)
                                       : mlp_rays_fp32(net, packed_f, rays, z_f, n, St, raw_f, st)) return rc;
         if (int rc = stage_composite(raw_f, z_f, rays, 6, n, St, rgb_f, disp_f, nullptr, nullptr, nullptr, st)) return rc;
@@ -470,7 +480,10 @@ int mi_nerf_time_mlp_rays(const mi_nerf_net* net, const void* packed, const floa
                           float* raw, int iters, int mode, float* avg_ms, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     MN_CHECK_ARG(iters >= 1 && avg_ms, "bad iters / NULL output");
-    MN_CHECK_ARG(mode >= MI_NERF_MODE_F32 && mode <= MI_NERF_MODE_F16S, "mode must be MI_NERF_MODE_F32 .. MI_NERF_MODE_F16S: one network, one kernel family (got %d)", mode);
+    MN_CHECK_ARG((mode >= MI_NERF_MODE_F32 && mode <= MI_NERF_MODE_F16S) || mode == MI_NERF_MODE_F16,
+                 "mode must be MI_NERF_MODE_F32 .. MI_NERF_MODE_F16S or MI_NERF_MODE_F16: one network, one kernel family (got %d)", mode);
+    if (mode == MI_NERF_MODE_F16)
+        if (int rc = check_net_f16_variant(net)) return rc;                // before the events: no GPU call for a network the kernel cannot run
     hipEvent_t e0, e1;
     MN_HIP(hipEventCreate(&e0));
     MN_HIP(hipEventCreate(&e1));
@@ -478,6 +491,7 @@ int mi_nerf_time_mlp_rays(const mi_nerf_net* net, const void* packed, const floa
     MN_HIP(hipEventRecord(e0, st));
     for (int i = 0; i < iters && rc == MI_NERF_OK; ++i)
         rc = mode == MI_NERF_MODE_F16S ? mlp_rays_f16s(net, packed, rays, z, n_rays, S, raw, st)
+             : mode == MI_NERF_MODE_F16 ? mlp_rays_f16(net, packed, rays, z, n_rays, S, raw, st, 0, nullptr, nullptr)
              : mode ? mlp_rays_bf16(net, packed, rays, z, n_rays, S, raw, st, bf16_points_per_wave(mode), nullptr)
                         : mlp_rays_fp32(net, packed, rays, z, n_rays, S, raw, st);
     MN_HIP(hipEventRecord(e1, st));
