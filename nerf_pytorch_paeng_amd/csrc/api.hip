@@ -71,9 +71,6 @@ int pack_bwd_f16s(const mi_nerf_net*, const mi_nerf_params*, void*, size_t);
 size_t pack_map_bwd_f16s_len(const mi_nerf_net*);
 int pack_map_bwd_f16s(const mi_nerf_net*, int32_t*, size_t);
 int pack_apply_bwd_f16s(const mi_nerf_net*, const int32_t*, const float*, void*, size_t, unsigned*, hipStream_t);
-// MI_NERF_MODE_* (mi_nerf_render_cfg.mode / mi_nerf_time_mlp_rays) -> launch shape of the bf16 kernel (0: chosen per launch)
-static inline int bf16_points_per_wave(int mode) { return mode == MI_NERF_MODE_BF16_64 ? 64 : (mode == MI_NERF_MODE_BF16_32 ? 32 : (mode == 4 ? 832 : 0)); }
-static inline bool mode_is_bf16(int mode) { return mode >= MI_NERF_MODE_BF16 && mode <= 4; }
 int wgrad_products(int, const float* const*, const int*, const int*, const float* const*, const int*, const int*, int64_t, float* const*, const int*,
                    float* const*, void*, size_t, hipStream_t, bool);
 int mlp_rays_fp32_stash(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, float*, float*, float*, unsigned*,
@@ -116,6 +113,33 @@ static int check_net_basic(const mi_nerf_net* net) {
                  "unsupported encoding L_x=%d L_d=%d (the kernels evaluate up to 10 / 4 frequencies; fewer run with zero weights on the rest)", net->L_x, net->L_d);
     MN_CHECK_ARG(net->skip >= -1, "bad skip=%d", net->skip);
     return MI_NERF_OK;
+}
+
+// ---- MI_NERF_MODE_* (mi_nerf_render_cfg.mode, mi_nerf_time_mlp_rays): which kernel family evaluates the coarse and the fine network ----
+enum class Family { FP32, F16S, BF16, F16 };
+struct ModePlan { Family coarse, fine; int points_per_wave; };      // points_per_wave: the half kernels' launch shape (0: chosen per launch)
+
+static int mode_plan(int mode, ModePlan* p) {
+    switch (mode) {
+        case MI_NERF_MODE_F32:       *p = {Family::FP32, Family::FP32, 0}; return MI_NERF_OK;
+        case MI_NERF_MODE_BF16:      *p = {Family::BF16, Family::BF16, 0}; return MI_NERF_OK;
+        case MI_NERF_MODE_BF16_64:   *p = {Family::BF16, Family::BF16, 64}; return MI_NERF_OK;
+        case MI_NERF_MODE_BF16_32:   *p = {Family::BF16, Family::BF16, 32}; return MI_NERF_OK;
+        case MI_NERF_MODE_F16S:      *p = {Family::F16S, Family::F16S, 0}; return MI_NERF_OK;
+        case MI_NERF_MODE_F16S_BF16: *p = {Family::F16S, Family::BF16, 0}; return MI_NERF_OK;
+        case MI_NERF_MODE_F16:       *p = {Family::F16, Family::F16, 0}; return MI_NERF_OK;
+        case MI_NERF_MODE_F16_BF16:  *p = {Family::F16, Family::BF16, 0}; return MI_NERF_OK;
+    }
+    set_error("mode must be one of MI_NERF_MODE_* (0..3, 5, 6, 8, 9; got %d)", mode);      // 4: retired (tools/ABLATIONS.md), 7: reserved
+    return MI_NERF_EINVAL;
+}
+
+// one network through the fused MLP of `family`; strat / fine: the half kernels' coarse-pass extras (mlp_half_core.h)
+static int mlp_rays_family(Family family, const mi_nerf_net* net, const void* packed, const float* rays, const float* z, int64_t n, int S, float* raw,
+                           hipStream_t st, int points_per_wave, const StratDraw* strat = nullptr, FineDraw* fine = nullptr) {
+    if (family == Family::FP32) return mlp_rays_fp32(net, packed, rays, z, n, S, raw, st);
+    if (family == Family::F16S) return mlp_rays_f16s(net, packed, rays, z, n, S, raw, st);
+    return (family == Family::F16 ? mlp_rays_f16 : mlp_rays_bf16)(net, packed, rays, z, n, S, raw, st, points_per_wave, strat, fine);
 }
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -431,46 +455,33 @@ int mi_nerf_render_rays(const mi_nerf_net* net, const void* packed_c, const void
     const int Sc = cfg->Sc, St = cfg->Sc + cfg->Nf;
     // 1-a) stratified depths; 2-a) coarse net; 3-a) composite          (nerf_process.py:187-198)
     // t_rand / u NULL: the jitter is drawn inside the consuming kernels (cfg->seed, cfg->ray_offset + ray, sample)
-    MN_CHECK_ARG((cfg->mode >= MI_NERF_MODE_F32 && cfg->mode <= MI_NERF_MODE_F16S_BF16) || cfg->mode == MI_NERF_MODE_F16 || cfg->mode == MI_NERF_MODE_F16_BF16,
-                 "mode must be one of MI_NERF_MODE_* (0..6, 8, 9; got %d)", cfg->mode);
-    const int ppw = bf16_points_per_wave(cfg->mode);
-    // per network: which kernel family evaluates it (MI_NERF_MODE_F16S_BF16 / MI_NERF_MODE_F16_BF16: coarse in split precision / f16, fine in bf16)
-    const bool coarse_f16s = cfg->mode == MI_NERF_MODE_F16S || cfg->mode == MI_NERF_MODE_F16S_BF16;
-    const bool fine_f16s = cfg->mode == MI_NERF_MODE_F16S;
-    const bool coarse_f16 = cfg->mode == MI_NERF_MODE_F16 || cfg->mode == MI_NERF_MODE_F16_BF16;
-    const bool fine_f16 = cfg->mode == MI_NERF_MODE_F16;
-    const bool coarse_bf16 = mode_is_bf16(cfg->mode);
-    const bool fine_bf16 = mode_is_bf16(cfg->mode) || cfg->mode == MI_NERF_MODE_F16S_BF16 || cfg->mode == MI_NERF_MODE_F16_BF16;
-    if (coarse_f16)
+    ModePlan p;
+    if (int rc = mode_plan(cfg->mode, &p)) return rc;
+    if (p.coarse == Family::F16 || p.fine == Family::F16)
         if (int rc = check_net_f16_variant(net)) return rc;                // before any launch: both networks of these modes are 256 wide
     FineDraw fd{};
-    if (coarse_bf16 || coarse_f16) {
-        // the bf16 kernel draws the stratified depths in its own prologue and writes z_c (one launch fewer: at a 512-ray shard a
+    if (p.coarse == Family::BF16 || p.coarse == Family::F16) {
+        // the half kernel draws the stratified depths in its own prologue and writes z_c (one launch fewer: at a 512-ray shard a
         // launch is ~4 us of a ~130 us step)
         // ... and, for a small shard (one 32-point unit per wave: <= 512 rays on 256 CUs), render_rays' middle as well: `fd.taken`
         const StratDraw sd{cfg->near_, cfg->far_, t_rand, cfg->seed, cfg->ray_offset, z_c};
-        if (cfg->Nf > 0) {
-            MN_CHECK_ARG(packed_f && rgb_f && disp_f, "fine pass needs packed_fine and outputs");
-            fd = FineDraw{cfg->Nf, cfg->det, u, cfg->seed, cfg->ray_offset, rgb_c, disp_c, wts_c, (float*)(w + L.z_f), false};
-        }
-        if (int rc = (coarse_f16 ? mlp_rays_f16 : mlp_rays_bf16)(net, packed_c, rays, nullptr, n, Sc, raw_c, st, ppw, &sd, cfg->Nf > 0 && ppw == 0 ? &fd : nullptr))
+        if (cfg->Nf > 0) fd = FineDraw{cfg->Nf, cfg->det, u, cfg->seed, cfg->ray_offset, rgb_c, disp_c, wts_c, (float*)(w + L.z_f), false};
+        if (int rc = mlp_rays_family(p.coarse, net, packed_c, rays, nullptr, n, Sc, raw_c, st, p.points_per_wave, &sd,
+                                     cfg->Nf > 0 && p.points_per_wave == 0 ? &fd : nullptr))
             return rc;
     } else {
         if (int rc = stage_stratified(n, Sc, cfg->near_, cfg->far_, t_rand, cfg->seed, cfg->ray_offset, z_c, st)) return rc;
-        if (int rc = coarse_f16s ? mlp_rays_f16s(net, packed_c, rays, z_c, n, Sc, raw_c, st) : mlp_rays_fp32(net, packed_c, rays, z_c, n, Sc, raw_c, st)) return rc;
+        if (int rc = mlp_rays_family(p.coarse, net, packed_c, rays, z_c, n, Sc, raw_c, st, p.points_per_wave)) return rc;
     }
     if (cfg->Nf == 0) return stage_composite(raw_c, z_c, rays, 6, n, Sc, rgb_c, disp_c, nullptr, wts_c, nullptr, st);
     {
         // 3-a) + 1-b) composite, resample + merge in one launch; 2-b) fine net over all Sc+Nf depths; 3-b) composite   (:198-213)
         float* z_f = (float*)(w + L.z_f);
         float* raw_f = (float*)(w + L.raw_f);
-        if (!fd.taken)        // (a small bf16 coarse launch has done this in its epilogue)
+        if (!fd.taken)        // (a small half-kernel coarse launch has done this in its epilogue)
             if (int rc = stage_composite_fine_z(raw_c, z_c, rays, n, Sc, cfg->Nf, cfg->det, u, cfg->seed, cfg->ray_offset, rgb_c, disp_c, wts_c, z_f, st))
                 return rc;
-        if (int rc = fine_f16s ? mlp_rays_f16s(net, packed_f, rays, z_f, n, St, raw_f, st)
-                          : fine_f16 ? mlp_rays_f16(net, packed_f, rays, z_f, n, St, raw_f, st, ppw, nullptr, nullptr)
-                          : fine_bf16 ? mlp_rays_bf16(net, packed_f, rays, z_f, n, St, raw_f, st, ppw, nullptr)
-                                      : mlp_rays_fp32(net, packed_f, rays, z_f, n, St, raw_f, st)) return rc;
+        if (int rc = mlp_rays_family(p.fine, net, packed_f, rays, z_f, n, St, raw_f, st, p.points_per_wave)) return rc;
         if (int rc = stage_composite(raw_f, z_f, rays, 6, n, St, rgb_f, disp_f, nullptr, nullptr, nullptr, st)) return rc;
     }
     return MI_NERF_OK;
@@ -480,9 +491,10 @@ int mi_nerf_time_mlp_rays(const mi_nerf_net* net, const void* packed, const floa
                           float* raw, int iters, int mode, float* avg_ms, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     MN_CHECK_ARG(iters >= 1 && avg_ms, "bad iters / NULL output");
-    MN_CHECK_ARG((mode >= MI_NERF_MODE_F32 && mode <= MI_NERF_MODE_F16S) || mode == MI_NERF_MODE_F16,
-                 "mode must be MI_NERF_MODE_F32 .. MI_NERF_MODE_F16S or MI_NERF_MODE_F16: one network, one kernel family (got %d)", mode);
-    if (mode == MI_NERF_MODE_F16)
+    ModePlan p;
+    if (int rc = mode_plan(mode, &p)) return rc;
+    MN_CHECK_ARG(p.coarse == p.fine, "MI_NERF_MODE_* %d is two kernel families (mi_nerf_render_rays only): one network, one kernel family", mode);
+    if (p.fine == Family::F16)
         if (int rc = check_net_f16_variant(net)) return rc;                // before the events: no GPU call for a network the kernel cannot run
     hipEvent_t e0, e1;
     MN_HIP(hipEventCreate(&e0));
@@ -490,10 +502,7 @@ int mi_nerf_time_mlp_rays(const mi_nerf_net* net, const void* packed, const floa
     int rc = MI_NERF_OK;
     MN_HIP(hipEventRecord(e0, st));
     for (int i = 0; i < iters && rc == MI_NERF_OK; ++i)
-        rc = mode == MI_NERF_MODE_F16S ? mlp_rays_f16s(net, packed, rays, z, n_rays, S, raw, st)
-             : mode == MI_NERF_MODE_F16 ? mlp_rays_f16(net, packed, rays, z, n_rays, S, raw, st, 0, nullptr, nullptr)
-             : mode ? mlp_rays_bf16(net, packed, rays, z, n_rays, S, raw, st, bf16_points_per_wave(mode), nullptr)
-                        : mlp_rays_fp32(net, packed, rays, z, n_rays, S, raw, st);
+        rc = mlp_rays_family(p.fine, net, packed, rays, z, n_rays, S, raw, st, p.points_per_wave);
     MN_HIP(hipEventRecord(e1, st));
     MN_HIP(hipEventSynchronize(e1));
     float ms = 0.f;

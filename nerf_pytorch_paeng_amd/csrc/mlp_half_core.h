@@ -870,8 +870,8 @@ template <bool F16>
 static int mlp_rays_half(const mi_nerf_net* net, const HalfBlob& L, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays,
                          int S, float* raw_dev, hipStream_t st, int points_per_wave, const StratDraw* strat, FineDraw* fine) {
     MN_CHECK_ARG(n_rays >= 0 && S >= 1, "bad sizes n_rays=%lld S=%d", (long long)n_rays, S);
-    MN_CHECK_ARG(points_per_wave == 0 || points_per_wave == 32 || points_per_wave == 64 || points_per_wave == 832,
-                 "points_per_wave must be 0 (auto), 32, 64 or 832 (8 waves of 32) (got %d)", points_per_wave);
+    MN_CHECK_ARG(points_per_wave == 0 || points_per_wave == 32 || points_per_wave == 64, "points_per_wave must be 0 (auto), 32 or 64 (got %d)",
+                 points_per_wave);
     if (n_rays == 0) return MI_NERF_OK;
     MN_CHECK_ARG(packed_dev && rays_dev && raw_dev && (z_dev || (strat && strat->z_out)), "NULL device pointer");
     MlpArgsB a{};
@@ -896,7 +896,6 @@ static int mlp_rays_half(const mi_nerf_net* net, const HalfBlob& L, const void* 
     // (An 8-wave shape -- 32 points per wave, two waves per SIMD -- was measured SLOWER than the 64-point shape at every size: 4096 rays, fine
     // launch 638 vs 603 us, profiles/r03_bf16_two_waves_per_simd.txt.  The kernel is not short of latency hiding, it is short of power: twice
     // the LDS reads per FLOP cost more clock than the interleaving wins back.  Its instantiation is gone: tools/ABLATIONS.md.)
-    MN_CHECK_ARG(points_per_wave != 832, "the 8-wave shape (832) was an experiment and is not built (tools/ABLATIONS.md)");
     // The launch plan.  A pass of the 64-point shape takes the same time whatever the number of active CUs (the kernel is bound by
     // what ONE CU does per pass), a pass of the 32-point shape ~0.65 of it (half the matrix work, the same weight stream:
     // profiles/r03_bf16_small_launch_shape.txt).  So: whole rounds of the 64-point shape (every wave of the chip a pair of tiles),

@@ -213,19 +213,19 @@ def llff_cameras(raw_poses, raw_bds, bd_factor=.75, path_zflat: bool = False) ->
 # ---------------------------------------------------------------------------------------------------
 # eval / video harness
 # ---------------------------------------------------------------------------------------------------
+# opts.precision -> the precision flags it sets (ops.PRECISION_FLAGS)
+_PRECISIONS = {"fp32": (), "f16s": ("f16s",), "bf16": ("bf16",), "f16s+bf16": ("bf16", "coarse_f16s"), "f16": ("f16",), "f16+bf16": ("bf16", "coarse_f16")}
+
+
 def _precision(opts) -> Dict[str, bool]:
     """``opts.precision`` (not a flag of the reference's config.py; absent = "fp32", the reference's arithmetic) selects the network's
     precision mode for the eval / video harness: "fp32" | "f16s" (split precision: fp32-grade results, ~3x faster) | "bf16" |
     "f16s+bf16" (coarse network in split precision -- the fine sample positions are the fp32 path's -- fine network in bf16) |
-    "f16" (both networks on the f16 MFMA kernel) | "f16+bf16" (coarse network in f16, fine network in bf16)."""
+    "f16" (both networks on the f16 MFMA kernel) | "f16+bf16" (coarse network in f16, fine network in bf16).  Returns all five flags."""
     mode = str(getattr(opts, "precision", "fp32")).lower()
-    if mode not in ("fp32", "f16s", "bf16", "f16s+bf16", "f16", "f16+bf16"):
-        raise ValueError(f"opts.precision must be 'fp32', 'f16s', 'bf16', 'f16s+bf16', 'f16' or 'f16+bf16', got {mode!r}")
-    out = {"bf16": mode in ("bf16", "f16s+bf16", "f16+bf16"), "f16s": mode == "f16s", "coarse_f16s": mode == "f16s+bf16"}
-    # the f16 keys only in the f16 modes: the three-key dict of the other modes is existing surface (tests/test_gpu_f16s.py compares it whole)
-    if mode in ("f16", "f16+bf16"):
-        out.update(f16=mode == "f16", coarse_f16=mode == "f16+bf16")
-    return out
+    if mode not in _PRECISIONS:
+        raise ValueError(f"opts.precision must be one of {', '.join(repr(k) for k in _PRECISIONS)}, got {mode!r}")
+    return {k: k in _PRECISIONS[mode] for k in ops.PRECISION_FLAGS}
 
 
 def _frozen(model, opts):
@@ -234,8 +234,7 @@ def _frozen(model, opts):
     with a weight beyond the f16 range raises instead of rendering from a clipped network."""
     from .weights import packed_for
     packed = packed_for(model)
-    prec = _precision(opts)
-    if prec["f16s"] or prec["coarse_f16s"] or prec.get("f16") or prec.get("coarse_f16"):
+    if ops.precision(**_precision(opts)).reads_f16s:
         packed.f16s()
         packed.check_f16s_range()
     return packed

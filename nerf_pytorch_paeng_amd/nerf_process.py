@@ -143,17 +143,16 @@ def run_network(model, embedded, is_fine: bool = False):
 
 
 # --------------------------------------------------------------------------------------------------
-def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, ray_offset: int, bf16: bool,
-            intermediates: bool, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False,
-            coarse_f16: bool = False) -> Dict[str, torch.Tensor]:
+def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, ray_offset: int, prec: ops.Precision,
+            intermediates: bool) -> Dict[str, torch.Tensor]:
     n = rays.shape[0]
     dev = rays.device
     Sc, Nf = int(opts.N_samples_c), int(opts.N_samples_f)
     det = _det(opts)
     # jitter: explicit tensors when the caller injects them (or wants them back); otherwise the kernels draw it themselves from the
     # same counter-based generator, keyed on (seed, ray_offset + ray, sample) -- identical values, no tensors, no extra launches
-    cfg = ops.render_cfg(float(opts.near), float(opts.far), Sc, Nf, det, bf16, seed=seed, ray_offset=ray_offset, f16s=f16s, coarse_f16s=coarse_f16s,
-                         f16=f16, coarse_f16=coarse_f16)
+    cfg = ops.render_cfg(float(opts.near), float(opts.far), Sc, Nf, det, seed=seed, ray_offset=ray_offset)
+    cfg.mode = prec.mode
     if t_rand is not None:
         t_rand = as_f32_dev(t_rand, dev)
     elif intermediates:
@@ -165,11 +164,8 @@ def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, 
             u = ops.fill_uniform(seed, 1, ray_offset, n, Nf, dev)
     else:
         u = None
-    if coarse_f16s or coarse_f16:                                   # MI_NERF_MODE_F16S_BF16 / F16_BF16: one blob of each family (both 256 wide)
-        blobs = (packed.f16s()[0], packed.bf16()[1])
-    else:                                                           # the f16 kernel reads the split-precision blobs' hi halves
-        blobs = packed.f16s() if (f16s or f16) else (packed.bf16() if bf16 else (packed.coarse, packed.fine))
-    rgb_c, disp_c, rgb_f, disp_f, ws = ops.render_rays(packed.kernel_net(bf16, f16s or f16), blobs[0], blobs[1] if Nf > 0 else None, cfg, rays, t_rand, u)
+    net, blob_c, blob_f = packed.kernel_blobs(prec)
+    rgb_c, disp_c, rgb_f, disp_f, ws = ops.render_rays(net, blob_c, blob_f if Nf > 0 else None, cfg, rays, t_rand, u)
     out = {"rgb_c": rgb_c, "disp_c": disp_c}                        # nerf_process.py:215-216
     if Nf > 0:
         out["rgb_f"], out["disp_f"] = rgb_f, disp_f
@@ -180,25 +176,29 @@ def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, 
     return out
 
 
+def _train_f16s(prec: ops.Precision, intermediates: bool = False) -> bool:
+    """The training path's precision: True = split precision (f16s forward, fp32 backward), False = fp32.  It has no other mode."""
+    if prec.fine not in ("fp32", "f16s") or intermediates:
+        raise MiNerfError("the training path has no bf16 / f16 mode (fp32, or f16s=True: split-precision forward, fp32 backward) and returns no intermediates")
+    return prec.fine == "f16s"
+
+
 def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ray_offset: int = 0, bf16: bool = False,
                 return_intermediates: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False):
     """Coarse pass -> composite -> resample -> fine pass (nerf_process.py:185-216) as one fused launch
-    sequence.  Returns ``{'rgb_c','disp_c'[,'rgb_f','disp_f']}``.  ``bf16`` / ``f16s`` select the network's precision mode
-    (fp32 MFMA by default; bf16 MFMA; f16 split precision: fp32-grade results on the f16 matrix pipe); ``bf16`` with ``coarse_f16s``
-    evaluates the coarse network in split precision and the fine one in bf16 (the fine sample positions then match the fp32 path's).
-    ``f16`` runs both networks on the f16 MFMA kernel (one MFMA per product, 8x finer rounding than bf16 at the bf16 rate); ``bf16`` with
-    ``coarse_f16`` the coarse network in f16 and the fine one in bf16.  Inference only."""
+    sequence.  Returns ``{'rgb_c','disp_c'[,'rgb_f','disp_f']}``.  ``bf16`` / ``f16s`` / ``coarse_f16s`` / ``f16`` / ``coarse_f16`` select
+    the networks' precision mode (ops.precision(); fp32 MFMA by default).  With gradients: fp32 or f16s."""
+    prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
     if train_path.wants_grad(model):
-        if bf16 or f16 or coarse_f16 or return_intermediates:
-            raise MiNerfError("the training path has no bf16 / f16 mode (fp32, or f16s=True: split-precision forward) and returns no intermediates")
+        train_f16s = _train_f16s(prec, return_intermediates)
         if rays.dim() != 2 or rays.shape[1] != 6:
             raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
-        return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=_next_seed(seed), ray_offset=int(ray_offset), f16s=f16s)
+        return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=_next_seed(seed), ray_offset=int(ray_offset), f16s=train_f16s)
     packed = packed_for(model)
     rays = as_f32_dev(rays, packed.device)
     if rays.dim() != 2 or rays.shape[1] != 6:
         raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
-    return _render(rays, packed, opts, t_rand, u, _next_seed(seed), int(ray_offset), bf16, return_intermediates, f16s, coarse_f16s, f16, coarse_f16)
+    return _render(rays, packed, opts, t_rand, u, _next_seed(seed), int(ray_offset), prec, return_intermediates)
 
 
 def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts, *, t_rand=None, u=None, seed=None,
@@ -210,9 +210,9 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
     ``opts.chunk_rays`` bounded the reference's activation memory; the fused kernels keep activations in
     registers, so rays are launched in slabs of up to MAX_RAYS_PER_LAUNCH.  The result does not depend on
     the slab size because the jitter is keyed on the global ray index (``ray_offset`` + position)."""
+    prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
     training = train_path.wants_grad(model)
-    if training and (bf16 or f16 or coarse_f16):
-        raise MiNerfError("the training path has no bf16 / f16 mode (fp32, or f16s=True: split-precision forward, fp32 backward)")
+    train_f16s = _train_f16s(prec) if training else False
     packed = None if training else packed_for(model)
     dev = next(model.parameters()).device if training else packed.device
     ray_d = as_f32_dev(ray_d, dev)
@@ -234,9 +234,9 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
         tr, uu = (None if t_rand is None else t_rand[i:j]), (None if u is None else u[i:j])
         if training:                                                # train.py:53-54: one autograd node per slab
             parts.append(train_path.render_train(rays[i:j].contiguous(), model, opts, t_rand=tr, u=uu, seed=seed,
-                                                 ray_offset=int(ray_offset) + i, f16s=f16s))
+                                                 ray_offset=int(ray_offset) + i, f16s=train_f16s))
         else:
-            parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, bf16, False, f16s, coarse_f16s, f16, coarse_f16))
+            parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False))
     def cat(key):
         return parts[0][key] if len(parts) == 1 else torch.cat([p[key] for p in parts], dim=0)
     if Nf > 0:

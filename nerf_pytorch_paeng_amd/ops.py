@@ -6,7 +6,7 @@ immediately (no host synchronisation).  PyTorch is used for device memory and st
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -615,29 +615,50 @@ def permute_rows(src: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 # MI_NERF_MODE_* of include/mi_nerf.h (mi_nerf_render_cfg.mode, mi_nerf_time_mlp_rays)
 MODE_F32, MODE_BF16, MODE_BF16_64, MODE_BF16_32, MODE_F16S, MODE_F16S_BF16, MODE_F16, MODE_F16_BF16 = 0, 1, 2, 3, 5, 6, 8, 9
-BF16_SHAPES = {0: MODE_BF16, 64: MODE_BF16_64, 32: MODE_BF16_32, 832: 4}          # points per wave -> mode (832: a retired shape the library refuses)
+# the precision keyword flags (render_cfg, time_mlp_rays, nerf_process.render_rays, ...); the ones set, for each combination that names a
+# mode -> the kernel family of the (coarse, fine) network; (coarse, fine, points_per_wave) -> MI_NERF_MODE_*
+PRECISION_FLAGS = ("bf16", "f16s", "coarse_f16s", "f16", "coarse_f16")
+_FAMILIES = {(): ("fp32", "fp32"), ("bf16",): ("bf16", "bf16"), ("f16s",): ("f16s", "f16s"), ("bf16", "coarse_f16s"): ("f16s", "bf16"),
+             ("f16",): ("f16", "f16"), ("bf16", "coarse_f16"): ("f16", "bf16")}
+_MODES = {("fp32", "fp32", 0): MODE_F32, ("bf16", "bf16", 0): MODE_BF16, ("bf16", "bf16", 64): MODE_BF16_64, ("bf16", "bf16", 32): MODE_BF16_32,
+          ("f16s", "f16s", 0): MODE_F16S, ("f16s", "bf16", 0): MODE_F16S_BF16, ("f16", "f16", 0): MODE_F16, ("f16", "bf16", 0): MODE_F16_BF16}
+
+
+class Precision(NamedTuple):
+    """Which kernel family -- "fp32" | "f16s" (split precision) | "bf16" | "f16" -- evaluates the coarse and which the fine network, and the
+    bf16 kernel's launch shape (0 = chosen per launch, 64 / 32 pinned).  ``reads_f16s``: a network runs on PackedNeRF.f16s() blobs."""
+    coarse: str
+    fine: str
+    points_per_wave: int = 0
+
+    @property
+    def mode(self) -> int:
+        return _MODES[self]
+
+    @property
+    def reads_f16s(self) -> bool:
+        return bool({self.coarse, self.fine} & {"f16s", "f16"})          # (the f16 kernel reads the hi halves)
+
+
+def precision(bf16: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False,
+              points_per_wave: int = 0) -> Precision:
+    """The precision flags resolved (the modes: include/mi_nerf.h).  ``points_per_wave`` pins the launch shape of bf16
+    alone; the fp32 and split-precision kernels have none and ignore it.  Any other combination raises MiNerfError."""
+    on = tuple(k for k, v in zip(PRECISION_FLAGS, (bf16, f16s, coarse_f16s, f16, coarse_f16)) if v)
+    if on not in _FAMILIES:
+        raise MiNerfError(f"no precision mode sets {' + '.join(on)}: none (fp32), bf16, f16s, f16, or bf16 with one of coarse_f16s / coarse_f16")
+    coarse, fine = _FAMILIES[on]
+    p = Precision(coarse, fine, 0 if fine in ("fp32", "f16s") else int(points_per_wave))
+    if p not in _MODES:
+        raise MiNerfError(f"points_per_wave={points_per_wave}: 0 (chosen per launch), or 64 / 32 with bf16 alone")
+    return p
 
 
 def render_cfg(near: float, far: float, Sc: int, Nf: int, det: bool, bf16: bool = False, points_per_wave: int = 0, seed: int = 0,
                ray_offset: int = 0, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False) -> RenderCfg:
-    """``points_per_wave`` (bf16 only): 0 = the bf16 kernel's launch shape is chosen per launch; 64 / 32 pin it.
-    ``f16s``: the split-precision MLP variant (blobs from PackedNeRF.f16s()).
-    ``bf16`` with ``coarse_f16s``: MI_NERF_MODE_F16S_BF16 -- the coarse network in split precision (fp32-grade fine sample positions),
-    the fine network in bf16; the caller hands PackedNeRF.f16s()[0] and PackedNeRF.bf16()[1].
-    ``f16``: MI_NERF_MODE_F16 -- both networks on the f16 kernel (one MFMA per product, blobs from PackedNeRF.f16s()).
-    ``bf16`` with ``coarse_f16``: MI_NERF_MODE_F16_BF16 -- the coarse network in f16, the fine network in bf16; the caller hands
-    PackedNeRF.f16s()[0] and PackedNeRF.bf16()[1].
+    """The precision flags and ``points_per_wave``: precision() (the blobs that go with them: PackedNeRF.kernel_blobs).
     ``seed`` / ``ray_offset`` key the jitter the kernels draw themselves when render_rays gets no ``t_rand`` / ``u`` tensor."""
-    if bf16 and f16s:
-        raise MiNerfError("bf16 and f16s are different precision modes: pick one (bf16 with coarse_f16s=True mixes them per network)")
-    if f16 and (bf16 or f16s or coarse_f16s or coarse_f16 or points_per_wave):
-        raise MiNerfError("f16 is a precision mode of its own: not with bf16, f16s, coarse_f16s, coarse_f16 or points_per_wave")
-    if coarse_f16s and (not bf16 or points_per_wave):
-        raise MiNerfError("coarse_f16s goes with bf16=True (fine network in bf16, launch shape chosen per launch)")
-    if coarse_f16 and (not bf16 or points_per_wave or coarse_f16s or f16s):
-        raise MiNerfError("coarse_f16 goes with bf16=True alone (fine network in bf16, launch shape chosen per launch)")
-    mode = (MODE_F16 if f16 else MODE_F16S if f16s else MODE_F16S_BF16 if coarse_f16s else MODE_F16_BF16 if coarse_f16 else
-            BF16_SHAPES[int(points_per_wave)] if bf16 else MODE_F32)
+    mode = precision(bf16, f16s, coarse_f16s, f16, coarse_f16, points_per_wave).mode
     return RenderCfg(float(near), float(far), int(Sc), int(Nf), int(bool(det)), mode, int(seed) & 0xFFFFFFFF, 0, int(ray_offset))
 
 
@@ -693,15 +714,14 @@ def workspace_views(cfg: RenderCfg, n: int, workspace: torch.Tensor) -> Dict[str
 
 def time_mlp_rays(net: Net, packed: torch.Tensor, rays: torch.Tensor, z: torch.Tensor, raw: torch.Tensor, iters: int, bf16: bool = False,
                   points_per_wave: int = 0, f16s: bool = False, f16: bool = False) -> float:
-    """Average device milliseconds per fused-MLP launch, from hipEvents on the launch stream.  ``f16``: the f16 kernel (MI_NERF_MODE_F16;
-    ``packed`` from PackedNeRF.f16s() / pack_module(..., f16s=True))."""
-    if f16 and (bf16 or f16s or points_per_wave):
-        raise MiNerfError("f16 is a precision mode of its own: not with bf16, f16s or points_per_wave")
+    """Average device milliseconds per fused-MLP launch, from hipEvents on the launch stream.  The precision flags: precision().  ``f16``:
+    the f16 kernel (``packed`` from PackedNeRF.f16s() / pack_module(..., f16s=True))."""
+    mode = precision(bf16, f16s, f16=f16, points_per_wave=points_per_wave).mode
     n, S = z.shape
     ms = C.c_float(0.0)
     with _guard(z.device):
         check(lib().mi_nerf_time_mlp_rays(C.byref(net), dev_ptr(packed, "packed", torch.uint8, 16), dev_ptr(rays, "rays"), dev_ptr(z, "z"), n, S,
-                                          dev_ptr(raw, "raw", align=16), iters, MODE_F16 if f16 else MODE_F16S if f16s else (BF16_SHAPES[int(points_per_wave)] if bf16 else 0), C.byref(ms),
+                                          dev_ptr(raw, "raw", align=16), iters, mode, C.byref(ms),
                                           stream_ptr(z.device)), "mi_nerf_time_mlp_rays")
     return float(ms.value)
 

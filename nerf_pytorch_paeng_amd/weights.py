@@ -159,6 +159,13 @@ class PackedNeRF:
             return padded_256_net(self.net, "split-precision" if f16s else "bf16")
         return self.net
 
+    def kernel_blobs(self, prec: "ops.Precision") -> Tuple[Net, torch.Tensor, torch.Tensor]:
+        """(network, coarse blob, fine blob) to hand the library for ``prec`` (ops.precision()): each blob from its kernel family's packer
+        (the f16 kernel reads the split-precision blobs' hi halves), the 256-wide network whenever a family is not fp32."""
+        blobs = {"fp32": lambda: (self.coarse, self.fine), "bf16": self.bf16, "f16s": self.f16s, "f16": self.f16s}
+        coarse, fine = blobs[prec.coarse]()[0], blobs[prec.fine]()[1]
+        return self.kernel_net(bf16=prec.fine == "bf16", f16s=prec.reads_f16s), coarse, fine
+
     def _wide_flats(self, wide: Net):
         """The device-resident flat parameter vectors scattered into the layout of ``wide`` (nn.Module source)."""
         if wide is self.net:

@@ -3,6 +3,7 @@ network in bf16), checked without a GPU: the mode values and their Python surfac
 layout assumption the kernel's weight addressing rests on (csrc/mlp_half_core.h: the split-precision blob's hi quads, 2 KiB apart, ARE the
 bf16 stream), the object checks of mlp_f16.hip, and the f16 rounding-point oracle the GPU tests hold the kernel to."""
 import ctypes as C
+import itertools
 import os
 import re
 import sys
@@ -101,7 +102,14 @@ def test_mode_values():
     assert not any(k.startswith("MI_NERF_MODE_") and v in (4, 7) for k, v in d.items())      # 4 retired, 7 reserved
 
 
-def test_render_cfg_and_precision_strings():
+FLAGS = ("bf16", "f16s", "coarse_f16s", "f16", "coarse_f16")
+# the flags that name a mode (in FLAGS order) -> MI_NERF_MODE_* at points_per_wave 0 / 32 / 64 (None: refused), as render_cfg has
+# resolved them since the f16 modes were added; every other combination is refused at every launch shape
+SWEEP = {(0, 0, 0, 0, 0): (0, 0, 0), (1, 0, 0, 0, 0): (1, 3, 2), (0, 1, 0, 0, 0): (5, 5, 5), (1, 0, 1, 0, 0): (6, None, None),
+         (0, 0, 0, 1, 0): (8, None, None), (1, 0, 0, 0, 1): (9, None, None)}
+
+
+def test_render_cfg_and_precision_strings_resolve_to_modes():
     cfg = lambda **kw: ops.render_cfg(2.0, 6.0, 64, 128, False, **kw)
     assert cfg(f16=True).mode == 8
     assert cfg(bf16=True, coarse_f16=True).mode == 9
@@ -115,12 +123,35 @@ def test_render_cfg_and_precision_strings():
     with pytest.raises(MiNerfError):
         ops.time_mlp_rays(ops.make_net(8, 256, 4), None, None, torch.zeros(1, 1), None, 1, bf16=True, f16=True)
     P = lambda s: harness._precision(type("O", (), {"precision": s})())
-    assert P("f16") == {"bf16": False, "f16s": False, "coarse_f16s": False, "f16": True, "coarse_f16": False}
-    assert P("f16+bf16") == {"bf16": True, "f16s": False, "coarse_f16s": False, "f16": False, "coarse_f16": True}
-    assert P("f16s+bf16") == {"bf16": True, "f16s": False, "coarse_f16s": True}
+    want = {"fp32": ((), "fp32", "fp32", 0), "bf16": (("bf16",), "bf16", "bf16", 1), "f16s": (("f16s",), "f16s", "f16s", 5),
+            "f16s+bf16": (("bf16", "coarse_f16s"), "f16s", "bf16", 6), "f16": (("f16",), "f16", "f16", 8),
+            "f16+bf16": (("bf16", "coarse_f16"), "f16", "bf16", 9)}
+    for s, (on, coarse, fine, mode) in want.items():
+        assert P(s) == {k: k in on for k in FLAGS}, s
+        prec = ops.precision(**P(s))
+        assert (prec.coarse, prec.fine, prec.mode) == (coarse, fine, mode), s
+        assert prec.reads_f16s == (coarse in ("f16s", "f16")), s
     for s in ("fp16", "f16+f16s", "bf16+f16"):
         with pytest.raises(ValueError):
             P(s)
+
+
+def test_every_flag_combination_resolves_to_its_mode_or_is_refused():
+    for bits in itertools.product((0, 1), repeat=len(FLAGS)):
+        kw = dict(zip(FLAGS, map(bool, bits)))
+        for ppw, mode in zip((0, 32, 64), SWEEP.get(bits, (None, None, None))):
+            if mode is None:
+                with pytest.raises(MiNerfError):
+                    ops.precision(**kw, points_per_wave=ppw)
+                with pytest.raises(MiNerfError):
+                    ops.render_cfg(2.0, 6.0, 64, 128, False, points_per_wave=ppw, **kw)
+            else:
+                assert ops.precision(**kw, points_per_wave=ppw).mode == mode, (kw, ppw)
+                assert ops.render_cfg(2.0, 6.0, 64, 128, False, points_per_wave=ppw, **kw).mode == mode, (kw, ppw)
+    with pytest.raises(MiNerfError):                # the retired 8-wave shape: refused before the library sees mode 4 (which it refuses too)
+        ops.render_cfg(2.0, 6.0, 64, 128, False, True, points_per_wave=832)
+    with pytest.raises(MiNerfError):
+        ops.time_mlp_rays(ops.make_net(8, 256, 4), None, None, torch.zeros(1, 1), None, 1, True, 832)
 
 
 def _render_call(lib, net, mode):

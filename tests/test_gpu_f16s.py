@@ -548,7 +548,7 @@ def test_training_path_notices_a_saturated_f16s_backward(lego_rays, monkeypatch)
     assert not train_path.f16s_status(bad2)["saturated"]                         # read and reset
 
 
-def test_f16s_training_llff_and_two_slabs(monkeypatch):
+def test_f16s_training_llff_two_slabs_and_precision_flags(monkeypatch):
     """The split-precision step through the NDC (llff) entry, with the batch cut into two autograd nodes (slab size lowered): losses and
     coarse-network gradients equal the fp32 path's to fp32 rounding; harness.train takes the mode as opts.precision."""
     from nerf_pytorch_paeng_amd import harness, train_path
@@ -574,5 +574,5 @@ def test_f16s_training_llff_and_two_slabs(monkeypatch):
     for k, a in res[False][2].items():
         b = res[True][2][k]
         assert torch.isfinite(b).all() and float((a - b).abs().max()) <= 2e-5 * float(a.abs().max()) + 1e-12, k
-    assert harness._precision(make_opts(precision="f16s")) == {"bf16": False, "f16s": True, "coarse_f16s": False}
-    assert harness._precision(make_opts(precision="f16s+bf16")) == {"bf16": True, "f16s": False, "coarse_f16s": True}
+    assert harness._precision(make_opts(precision="f16s")) == {"bf16": False, "f16s": True, "coarse_f16s": False, "f16": False, "coarse_f16": False}
+    assert harness._precision(make_opts(precision="f16s+bf16")) == {"bf16": True, "f16s": False, "coarse_f16s": True, "f16": False, "coarse_f16": False}
