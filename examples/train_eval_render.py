@@ -58,8 +58,9 @@ def main(argv=None):
             print(f"step {i:6d}  loss {float(out['loss']):.5f}  psnr_f {float(out['psnr_f']):.2f} dB  {(time.perf_counter() - t0) / i * 1e3:.1f} ms/step", flush=True)
     fresh = NeRF(8, a.net_width, 63, 27, skips=[4]).to(dev)                                      # test() loads the checkpoint train() saved (test.py:20-21)
     res = harness.test(a.steps, i_test, posenc, fresh, images[i_test], K, poses[i_test].to(dev), (H, W), opts, log_dir=a.out,
-                       save_dir=os.path.join(a.out, "test_result"))                              # main.py:140-149
-    print(f"test: PSNR {['%.2f' % p for p in res['psnr']]} dB (mean {res['mean_psnr']:.2f}); PNGs and _result.txt in {a.out}/test_result")
+                       save_dir=os.path.join(a.out, "test_result"), ssim=True)                   # main.py:140-149
+    print(f"test: PSNR {['%.2f' % p for p in res['psnr']]} dB (mean {res['mean_psnr']:.2f}), SSIM {['%.4f' % v for v in res['ssim']]} "
+          f"(mean {res['mean_ssim']:.4f}); PNGs and _result.txt in {a.out}/test_result")
     rgbs, disps = harness.render(a.steps, posenc, fresh, K, None, (H, W), opts, log_dir=a.out, save_dir=os.path.join(a.out, "render_result"))   # main.py:150-158
     print(f"render: {rgbs.shape[0]} frames {rgbs.shape[1]}x{rgbs.shape[2]} in {a.out}/render_result")
     return res

@@ -1,6 +1,6 @@
-"""Build libmi_nerf.so with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libmi_nerf.so and libmi_nerf_iqa.so with hipcc for gfx950 (cross-compiles without a GPU).
 
-    python -m nerf_pytorch_paeng_amd.build [--force]          the shipped library (clean build: ~1 min 20 s on 8 cores)
+    python -m nerf_pytorch_paeng_amd.build [--force]          the shipped libraries (clean build: ~1 min 20 s on 8 cores)
     python -m nerf_pytorch_paeng_amd.build --variant TAG -DFOO -DBAR=1     an A/B variant (tools/ab_probe.py)
     python -m nerf_pytorch_paeng_amd.build --diag             the -DMN_DIAG variant (s_memtime stamps; never shipped or timed)
     python -m nerf_pytorch_paeng_amd.build --clean            remove every object and every variant
@@ -10,6 +10,8 @@ What lands where:
                                                     with the repository snapshot to the GPU box.  The stamp is a hash of every source,
                                                     header and flag: the library is up to date iff the stamp matches (no mtimes, no
                                                     objects needed -- the GPU box gets neither).
+  nerf_pytorch_paeng_amd/libmi_nerf_iqa.so (+ .stamp)   the image-quality metrics (include/mi_nerf_iqa.h, csrc/iqa.hip): a library of its own with a stamp
+                                                    of its own; libmi_nerf.so's sources and stamp inputs do not know it.
   build_scratch/obj/                                objects of the shipped library (cache; tests/test_packing_cpu.py disassembles them)
   build_scratch/obj_TAG/, build_scratch/libmi_nerf_TAG.so    variants.  build_scratch/ is git-ignored AND gpurun-ignored: a variant is
                                                     built where it is used (tools/ab_probe.py builds the ones it is asked for on the box).
@@ -31,6 +33,10 @@ SCRATCH = os.path.join(ROOT, "build_scratch")
 LIB = os.path.join(HERE, "libmi_nerf.so")
 STAMP = LIB + ".stamp"
 SOURCES = ["api.hip", "stages.hip", "mlp_fp32.hip", "mlp_fp32_wide.hip", "mlp_bf16.hip", "mlp_f16.hip", "mlp_f16s.hip", "mlp_f16s_stash.hip", "dgrad_f16s.hip", "mlp_train.hip", "frames.hip", "comm.hip", "pack.cpp"]
+# libmi_nerf_iqa.so: its own sources and its own header; common.h and mi_nerf.h are not part of it
+IQA_LIB = os.path.join(HERE, "libmi_nerf_iqa.so")
+IQA_STAMP = IQA_LIB + ".stamp"
+IQA_SOURCES = ["iqa.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          # the MLP kernel's register-resident design needs its k-loops FULLY unrolled (static register indices)
@@ -52,6 +58,10 @@ def _headers():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(INCLUDE, "mi_nerf.h")]
 
 
+def _iqa_headers():
+    return [os.path.join(INCLUDE, "mi_nerf_iqa.h")]
+
+
 def _digest(paths, extra=()) -> str:
     h = hashlib.sha256()
     for p in paths:
@@ -71,14 +81,14 @@ def object_dir(tag: str = "") -> str:
     return os.path.join(SCRATCH, "obj" + ("_" + tag if tag else ""))
 
 
-def _compile(src: str, force: bool, extra=(), tag: str = "") -> str:
+def _compile(src: str, force: bool, extra=(), tag: str = "", headers=None) -> str:
     """One translation unit -> build_scratch/obj[_TAG]/SRC.o, skipped when the object's own stamp (source + headers + flags) matches."""
     bdir = object_dir(tag)
     os.makedirs(bdir, exist_ok=True)
     obj = os.path.join(bdir, src + ".o")
     spath = os.path.join(CSRC, src)
     cmd_flags = [*FLAGS, *FILE_FLAGS.get(src, []), *extra]
-    want = _digest([spath] + _headers(), cmd_flags)
+    want = _digest([spath] + (_headers() if headers is None else headers), cmd_flags)
     stamp = obj + ".stamp"
     if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == want:
         return obj
@@ -117,6 +127,26 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     if verbose:
         print(f"built {LIB} ({os.path.getsize(LIB) / 1024:.0f} KiB, stamp {want[:16]})")
     return LIB
+
+
+def iqa_source_stamp() -> str:
+    return _digest([os.path.join(CSRC, s) for s in IQA_SOURCES] + _iqa_headers(), [FLAGS])
+
+
+def build_iqa_library(force: bool = False, verbose: bool = False) -> str:
+    """libmi_nerf_iqa.so, a no-op when its stamp matches (like build_library)."""
+    want = iqa_source_stamp()
+    if not force and os.path.exists(IQA_LIB) and os.path.exists(IQA_STAMP) and open(IQA_STAMP).read() == want:
+        if verbose:
+            print(f"up to date: {IQA_LIB} ({os.path.getsize(IQA_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+        return IQA_LIB
+    objs = [_compile(s, force, headers=_iqa_headers()) for s in IQA_SOURCES]
+    _link(objs, IQA_LIB)
+    with open(IQA_STAMP, "w") as fh:
+        fh.write(want)
+    if verbose:
+        print(f"built {IQA_LIB} ({os.path.getsize(IQA_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+    return IQA_LIB
 
 
 def variant_path(tag: str) -> str:
@@ -163,3 +193,4 @@ if __name__ == "__main__":
         print(build_variant(sys.argv[i + 1], [a for a in sys.argv[i + 2:] if a.startswith("-D")]))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True))
+        print(build_iqa_library(force="--force" in sys.argv, verbose=True))

@@ -548,6 +548,40 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def ssim(pred: torch.Tensor, target: torch.Tensor, *, hw=None, downsample: int = 1, clamp_cs: bool = False, return_map: bool = False):
+    """SSIM of ``pred`` against ``target`` (include/mi_nerf_iqa.h has the definition; the number test.py:71 prints): a device tensor of N
+    floats, one per frame, never synchronised.  Accepts [H,W,3], [H*W,3] together with ``hw=(H,W)`` (the flat frames test() holds), or
+    [N,H,W,3].  ``downsample``: 1 none, f > 1 average-pool by f first, 0 the MATLAB rule.  ``clamp_cs``: clamp the contrast-structure
+    factor at 0.  ``return_map``: also return the [N, H'-10, W'-10, 3] map."""
+    from . import _iqa
+    if pred.shape != target.shape or pred.numel() == 0:
+        raise MiNerfError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} must match and be non-empty")
+    shape = tuple(pred.shape)
+    if len(shape) == 2 and shape[1] == 3 and hw is not None and int(hw[0]) * int(hw[1]) == shape[0]:
+        n, H, W = 1, int(hw[0]), int(hw[1])
+    elif len(shape) == 3 and shape[2] == 3 and hw is None:
+        n, H, W = 1, shape[0], shape[1]
+    elif len(shape) == 4 and shape[3] == 3 and hw is None:
+        n, H, W = shape[0], shape[1], shape[2]
+    else:
+        raise MiNerfError(f"ssim takes [H,W,3], [H*W,3] with hw=(H,W), or [N,H,W,3]; got {shape} with hw={hw}")
+    dev = pred.device
+    with _guard(dev):
+        L = _iqa.lib()
+        ds = int(downsample)
+        nbytes = L.mi_iqa_ssim_scratch_bytes(n, H, W, ds)
+        f = L.mi_iqa_ssim_downsample_factor(H, W, ds)
+        if nbytes == 0 or f == 0:
+            raise MiNerfError(f"mi_iqa_ssim refused: {_iqa.last_error()}")
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        smap = torch.empty(n, H // f - 10, W // f - 10, 3, dtype=torch.float32, device=dev) if return_map else None
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        _iqa.check(L.mi_iqa_ssim(dev_ptr(pred, "pred"), dev_ptr(target, "target"), n, H, W, ds, _iqa.SSIM_CLAMP_CS if clamp_cs else 0,
+                                 dev_ptr(out), dev_ptr(smap, "map"), dev_ptr(scratch, "scratch", torch.float64, 8), nbytes, stream_ptr(dev)),
+                   "mi_iqa_ssim")
+    return (out, smap) if return_map else out
+
+
 def nanmax(x: torch.Tensor) -> torch.Tensor:
     if x.numel() == 0:
         raise MiNerfError("nanmax of an empty tensor")
