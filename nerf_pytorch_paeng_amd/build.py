@@ -32,7 +32,7 @@ INCLUDE = os.path.join(ROOT, "include")
 SCRATCH = os.path.join(ROOT, "build_scratch")
 LIB = os.path.join(HERE, "libmi_nerf.so")
 STAMP = LIB + ".stamp"
-SOURCES = ["api.hip", "stages.hip", "mlp_fp32.hip", "mlp_fp32_wide.hip", "mlp_bf16.hip", "mlp_f16.hip", "mlp_f16s.hip", "mlp_f16s_stash.hip", "dgrad_f16s.hip", "mlp_train.hip", "frames.hip", "comm.hip", "pack.cpp"]
+SOURCES = ["api.hip", "stages.hip", "mlp_fp32.hip", "mlp_fp32_wide.hip", "mlp_bf16.hip", "mlp_f16.hip", "mlp_f16s.hip", "mlp_f16s_stash.hip", "dgrad_f16s.hip", "mlp_train.hip", "frames.hip", "comm.hip", "pack.cpp", "pack_half.hip"]
 # libmi_nerf_iqa.so: its own sources and its own header; common.h and mi_nerf.h are not part of it
 IQA_LIB = os.path.join(HERE, "libmi_nerf_iqa.so")
 IQA_STAMP = IQA_LIB + ".stamp"

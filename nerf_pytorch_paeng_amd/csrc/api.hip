@@ -1,8 +1,7 @@
 // api.hip -- extern "C" surface of libmi_nerf.so (include/mi_nerf.h): argument checks, error text,
 // the fused render_rays launch sequence, the hipEvent timing hook and the MFMA layout self test.
 #include <string>
-#include "common.h"
-#include "layout.h"
+#include "half_layout.h"
 
 namespace minerf {
 
@@ -44,33 +43,16 @@ int ensure_lds_opt_in(LdsOptIn& state, const void* kernel) {
     return MI_NERF_OK;
 }
 
-// ---- implemented in the other translation units --------------------------------------------------
-int pack_fp32(const mi_nerf_net*, const mi_nerf_params*, void*, size_t);
-int pack_bf16(const mi_nerf_net*, const mi_nerf_params*, void*, size_t);
-size_t packed_bytes_bf16(const mi_nerf_net*);
-size_t pack_map_bf16_len(const mi_nerf_net*);
-int pack_map_bf16(const mi_nerf_net*, int32_t*, size_t);
-int pack_apply_bf16(const mi_nerf_net*, const int32_t*, const float*, void*, size_t, hipStream_t);
+// ---- implemented in the other translation units (the weight packers: half_layout.h) --------------
 int mlp_rays_fp32(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t);
 int mlp_embedded_fp32(const mi_nerf_net*, const void*, const float*, int64_t, float*, hipStream_t);
 int mlp_rays_bf16(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t, int points_per_wave, const StratDraw* strat,
                   FineDraw* fine = nullptr);
 int mlp_rays_f16(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t, int points_per_wave, const StratDraw* strat,
                  FineDraw* fine);
-int check_net_f16_variant(const mi_nerf_net*);
-size_t packed_bytes_f16s(const mi_nerf_net*);
-int pack_f16s(const mi_nerf_net*, const mi_nerf_params*, void*, size_t);
 int mlp_rays_f16s(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t);
 int mlp_rays_f16s_stash(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, float*, float*, float*, unsigned*, unsigned*,
                         hipStream_t);
-size_t pack_map_f16s_len(const mi_nerf_net*);
-int pack_map_f16s(const mi_nerf_net*, int32_t*, size_t);
-int pack_apply_f16s(const mi_nerf_net*, const int32_t*, const float*, void*, size_t, unsigned*, hipStream_t);
-size_t packed_bytes_bwd_f16s(const mi_nerf_net*);
-int pack_bwd_f16s(const mi_nerf_net*, const mi_nerf_params*, void*, size_t);
-size_t pack_map_bwd_f16s_len(const mi_nerf_net*);
-int pack_map_bwd_f16s(const mi_nerf_net*, int32_t*, size_t);
-int pack_apply_bwd_f16s(const mi_nerf_net*, const int32_t*, const float*, void*, size_t, unsigned*, hipStream_t);
 int wgrad_products(int, const float* const*, const int*, const int*, const float* const*, const int*, const int*, int64_t, float* const*, const int*,
                    float* const*, void*, size_t, hipStream_t, bool);
 int mlp_rays_fp32_stash(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, float*, float*, float*, unsigned*,
@@ -82,9 +64,6 @@ int mlp_embedded_fp32_stash(const mi_nerf_net*, const void*, const float*, int64
 int train_layout(const mi_nerf_net*, int64_t, int, mi_nerf_train_layout*);
 size_t wgrad_scratch_bytes();
 int pack_apply(const int32_t*, const float*, size_t, void*, hipStream_t);
-int pack_bwd_fp32(const mi_nerf_net*, const mi_nerf_params*, void*, size_t);
-size_t packed_bytes_bwd(const mi_nerf_net*);
-int pack_map(const mi_nerf_net*, int, int32_t*, size_t);
 int frames_image_metrics(const float*, const float*, int64_t, float*, void*, size_t, hipStream_t);
 int frames_nanmax(const float*, int64_t, float*, void*, size_t, hipStream_t);
 int frames_to8b(const float*, int64_t, const float*, unsigned char*, hipStream_t);
@@ -458,7 +437,7 @@ int mi_nerf_render_rays(const mi_nerf_net* net, const void* packed_c, const void
     ModePlan p;
     if (int rc = mode_plan(cfg->mode, &p)) return rc;
     if (p.coarse == Family::F16 || p.fine == Family::F16)
-        if (int rc = check_net_f16_variant(net)) return rc;                // before any launch: both networks of these modes are 256 wide
+        if (int rc = check_net_half(net, "f16")) return rc;                // before any launch: both networks of these modes are 256 wide
     FineDraw fd{};
     if (p.coarse == Family::BF16 || p.coarse == Family::F16) {
         // the half kernel draws the stratified depths in its own prologue and writes z_c (one launch fewer: at a 512-ray shard a
@@ -495,7 +474,7 @@ int mi_nerf_time_mlp_rays(const mi_nerf_net* net, const void* packed, const floa
     if (int rc = mode_plan(mode, &p)) return rc;
     MN_CHECK_ARG(p.coarse == p.fine, "MI_NERF_MODE_* %d is two kernel families (mi_nerf_render_rays only): one network, one kernel family", mode);
     if (p.fine == Family::F16)
-        if (int rc = check_net_f16_variant(net)) return rc;                // before the events: no GPU call for a network the kernel cannot run
+        if (int rc = check_net_half(net, "f16")) return rc;                // before the events: no GPU call for a network the kernel cannot run
     hipEvent_t e0, e1;
     MN_HIP(hipEventCreate(&e0));
     MN_HIP(hipEventCreate(&e1));

@@ -303,7 +303,7 @@ int dgrad_f16s(const mi_nerf_net* net, const void* packed_bwd_f16s_dev, const fl
                const unsigned* mask_h, const unsigned* mask_g, float* delta_h, float* delta_f, float* delta_d, int64_t n_rays, int S, long long P_pitch,
                long long n_valid, const unsigned* absmax_dev, hipStream_t st) {
     using namespace f16s;
-    if (int rc = check_net(net)) return rc;
+    if (int rc = check_net_half(net, "f16-split")) return rc;
     MN_CHECK_ARG(n_rays >= 1 && S >= 1, "bad sizes n_rays=%lld S=%d", (long long)n_rays, S);
     MN_CHECK_ARG(packed_bwd_f16s_dev && color_w_dev && dens_w_dev && d_raw_dev && mask_h && mask_g && delta_h && delta_f && delta_d && absmax_dev, "NULL device pointer");
     DArgs a{};

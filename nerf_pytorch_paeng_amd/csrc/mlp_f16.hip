@@ -23,31 +23,19 @@
 //     prologue (once per point, on the VALU, not in the MFMA stream).
 // Launch structure, shapes (64 / 32 points per wave, chosen per launch), the in-kernel stratified draw of the coarse pass and the fused
 // render_rays middle of small coarse launches are the bf16 kernel's (mlp_half_core.h mlp_rays_half).
-#include "mlp_f16s_core.h"
 #include "mlp_half_core.h"
 
 namespace minerf {
 
-static int check_net_f16(const mi_nerf_net* net) {
-    MN_CHECK_ARG(net != nullptr, "net is NULL");
-    MN_CHECK_ARG(net->W == 256, "the f16 variant is built for W=256 only (got %d; weights.PackedNeRF pads narrower networks)", net->W);
-    MN_CHECK_ARG(net->D >= 2 && net->D <= 16 && net->L_x >= 0 && net->L_x <= KERNEL_LX && net->L_d >= 0 && net->L_d <= KERNEL_LD && net->skip >= -1,
-                 "unsupported network for the f16 variant (D=%d L_x=%d L_d=%d skip=%d)", net->D, net->L_x, net->L_d, net->skip);
-    return MI_NERF_OK;
-}
-int check_net_f16_variant(const mi_nerf_net* net) { return check_net_f16(net); }
-
-// the stream positions of both layouts are the same quads, 2 KiB apart here: 16 positions of padding short of the ring's last slot
-static_assert(TAIL_USED == f16s::TAIL_USED_P && TAIL_QUADS - f16s::TAIL_PAIRS == BSLOT_QUADS / 2 && f16s::KPE == enc_ksteps32(KERNEL_LX),
-              "the f16 kernel walks the split-precision blob's stream as the bf16 stream");
+// Both layouts share their stream positions, tail body and gamma(x) k-steps by construction (half_layout.h); what is left to hold is the
+// ring's side of it: the split-precision tail is half a slot of padding short of the 224 positions the ring walks (bring_next_fetch).
+static_assert(TAIL_QUADS - TAIL_PAIRS == BSLOT_QUADS / 2, "the f16 kernel walks the split-precision blob's stream as the bf16 stream");
 
 int mlp_rays_f16(const mi_nerf_net* net, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays, int S,
                  float* raw_dev, hipStream_t st, int points_per_wave, const StratDraw* strat, FineDraw* fine) {
     if (fine) fine->taken = false;
-    if (int rc = check_net_f16(net)) return rc;
-    const f16s::BlobLayoutS b = f16s::make_layout(net->D, net->W, net->skip);
-    const uint32_t walk = b.stream_bytes + (uint32_t)(TAIL_QUADS - f16s::TAIL_PAIRS) * 2 * QUAD_BYTES;
-    const HalfBlob L{b.stream_off, walk, b.side_off, b.side_floats, b.bias_trunk, b.bias_feat, b.bias_d, b.head_b, b.wdir_t};
+    if (int rc = check_net_half(net, "f16")) return rc;
+    const HalfLayout L = make_half_layout(net->D, net->W, net->skip, HalfStream::PAIRS);
     return mlp_rays_half<true>(net, L, packed_dev, rays_dev, z_dev, n_rays, S, raw_dev, st, points_per_wave, strat, fine);
 }
 

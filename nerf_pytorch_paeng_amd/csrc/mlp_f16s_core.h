@@ -1,12 +1,9 @@
-// mlp_f16s_core.h -- the split-precision machinery shared by the translation units of that variant (mlp_f16s.hip: host packers + the
-// inference launch; mlp_f16s_stash.hip: the training forward; dgrad_f16s.hip: the backward-data chain): constants, blob layout, the weight
+// mlp_f16s_core.h -- the split-precision machinery shared by the translation units of that variant (mlp_f16s.hip: the
+// inference launch; mlp_f16s_stash.hip: the training forward; dgrad_f16s.hip: the backward-data chain): constants, the weight
 // ring, the fragment file, MFMA wrappers, packing schedule, job(), and the forward kernel template.  See mlp_f16s.hip for the design.
 #pragma once
-#include <string.h>
 #include <type_traits>
-#include <vector>
-#include "common.h"
-#include "layout.h"
+#include "half_layout.h"
 
 // where the next unit's inputs are requested in the view-direction layer (job, k-step): behind a ring advance (pair 161 of the tail = slot 10, quad 2)
 namespace minerf {
@@ -17,49 +14,12 @@ typedef unsigned u32x4b __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2b __attribute__((ext_vector_type(2)));
 
 constexpr int NP = 2;                                      // point tiles (16 points each) per wave
-constexpr int MT = 16, KF = 32;                            // output features per job, k per MFMA
 constexpr int NBUF = 4, LA = NBUF - 1;                     // A-operand pipeline: quad PAIRS in flight (a body's pair count and the tail's padding jump are multiples of 4)
 constexpr int SLOT_QUADS_S = 32, SLOT_BYTES_S = SLOT_QUADS_S * QUAD_BYTES, NSLOT_S = 3, RING_BYTES_S = NSLOT_S * SLOT_BYTES_S;
 constexpr int DMA_PER_WAVE = SLOT_QUADS_S / 4;
-constexpr int KPE = 2, KH = 8, NT = 16;                    // k-steps over gamma(x) (63 -> 64 channels), over a 256-wide activation; output tiles of a 256-wide layer
-constexpr int TAIL_USED_P = 128 + 8 + 64 + 4;              // quad PAIRS of the tail body that carry weights
-constexpr int TAIL_PAIRS = 208;                            // ... padded to whole slots (416 quads = 13 slots)
-constexpr float SC_DN = 1.0f / 2048.0f, SC_UP = 2048.0f;   // 2^-11, 2^11
-
-struct BlobLayoutS {
-    uint32_t stream_off, stream_bytes, side_off, side_floats;
-    uint32_t bias_trunk, bias_feat, bias_d, head_b, wdir_t, total_bytes;
-};
-static BlobLayoutS make_layout(int D, int W, int skip) {
-    BlobLayoutS b{};
-    const int in_d = 3 + 6 * KERNEL_LD;
-    uint32_t pairs = KPE * NT;
-    for (int l = 1; l < D; ++l) pairs += KH * NT + ((skip >= 0 && l == skip + 1) ? KPE * NT : 0);
-    pairs += TAIL_PAIRS;
-    b.stream_off = HEADER_BYTES;
-    b.stream_bytes = pairs * 2 * QUAD_BYTES;
-    b.side_off = b.stream_off + b.stream_bytes;
-    uint32_t f = 0;
-    b.bias_trunk = f; f += (uint32_t)D * W;
-    b.bias_feat = f;  f += W;
-    b.bias_d = f;     f += W / 2;
-    b.head_b = f;     f += 4;                       // colour bias (3), density bias
-    b.wdir_t = f;     f += (uint32_t)in_d * (W / 2);
-    b.side_floats = round_up_u32(f, 4);
-    b.total_bytes = b.side_off + b.side_floats * 4;
-    return b;
-}
-
-// shapes this variant is built for
-static int check_net(const mi_nerf_net* net) {
-    MN_CHECK_ARG(net != nullptr, "net is NULL");
-    MN_CHECK_ARG(net->W == 256, "the f16-split variant is built for W=256 only (got %d)", net->W);
-    MN_CHECK_ARG(net->D >= 2 && net->D <= 16 && net->L_x >= 0 && net->L_x <= KERNEL_LX && net->L_d >= 0 && net->L_d <= KERNEL_LD && net->skip >= -1,
-                 "unsupported network for the f16-split variant (D=%d L_x=%d L_d=%d skip=%d)", net->D, net->L_x, net->L_d, net->skip);
-    return MI_NERF_OK;
-}
-static uint32_t bwd_stream_bytes_s(int D) { return (uint32_t)(NT * (KH / 2) + NT * KH * D) * 2u * QUAD_BYTES; }
-
+constexpr int KPE = enc_ksteps32(KERNEL_LX), KH = 8, NT = 16;      // k-steps over gamma(x) (63 -> 64 channels), over a 256-wide activation; output tiles of a 256-wide layer
+constexpr float SC_DN = 1.0f / SPLIT_SCALE, SC_UP = SPLIT_SCALE;   // 2^-11, 2^11
+// (MT = 16, KF = 32 and the tail -- TAIL_USED of TAIL_PAIRS quad PAIRS carry weights -- are the bf16 stream's: half_layout.h)
 
 // ---------------------------------------------------------------------------------------------
 // device
@@ -651,7 +611,7 @@ void mlp_f16s_kernel(const Args a) {
                     if constexpr (STASH && ks == 1 && (sub == 2 || sub == 3))
                         stash_tile<true, true, NT / 2 - 1>(pt[2 * (sub - 2)], pt[2 * (sub - 2) + 1], rowp[sub - 2], mw[sub - 2], nib_sh);
                 };
-                job<200, KH / 2, TAIL_USED_P, TAIL_PAIRS - TAIL_USED_P>(hch, hcl, cselh, bh_in, bl_in, aq, smem, ring, lane, hook);
+                job<200, KH / 2, TAIL_USED, TAIL_PAIRS - TAIL_USED>(hch, hcl, cselh, bh_in, bl_in, aq, smem, ring, lane, hook);
             }
             // the MFMAs are asm statements: hipcc does not know that the colour tile is still in flight (XDL write -> VALU read), nor that
             // the tiles' fourth registers, which nothing reads, are still to be WRITTEN: the whole tuples pass through the wait statement
@@ -684,11 +644,11 @@ template <bool STASH>
 static int launch_f16s(const mi_nerf_net* net, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays, int S,
                        float* raw_dev, const StashF16s* stash, hipStream_t st) {
     using namespace f16s;
-    if (int rc = check_net(net)) return rc;
+    if (int rc = check_net_half(net, "f16-split")) return rc;
     MN_CHECK_ARG(n_rays >= 0 && S >= 1, "bad sizes n_rays=%lld S=%d", (long long)n_rays, S);
     if (n_rays == 0) return MI_NERF_OK;
     MN_CHECK_ARG(packed_dev && rays_dev && z_dev && raw_dev, "NULL device pointer");
-    const BlobLayoutS L = make_layout(net->D, net->W, net->skip);
+    const HalfLayout L = make_half_layout(net->D, net->W, net->skip, HalfStream::PAIRS);
     Args a{};
     a.stream = (const char*)packed_dev + L.stream_off;
     a.side = (const float*)((const char*)packed_dev + L.side_off);

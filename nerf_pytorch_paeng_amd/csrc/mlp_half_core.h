@@ -3,11 +3,8 @@
 // element type is a template parameter (F16) decided with `if constexpr`; see mlp_bf16.hip for the design and mlp_f16.hip for what the
 // f16 instantiation changes.
 #pragma once
-#include <string.h>
 #include <type_traits>
-#include <vector>
-#include "common.h"
-#include "layout.h"
+#include "half_layout.h"
 #include "stage_dev.h"
 
 namespace minerf {
@@ -21,18 +18,13 @@ typedef unsigned u32x4b __attribute__((ext_vector_type(4)));
 // stream), 2 in the SMALL-LAUNCH shape (32 / 128): twice the LDS reads and weight stream per FLOP, chosen by the launcher only
 // where the 64-point shape would leave SIMDs idle (a 512-ray shard of BASELINE config #5's 8-GPU split: 128 + 384 workgroup
 // passes on 256 CUs become 256 + 768 half-size ones).  NP is a template parameter of everything below.
-constexpr int MT = 16;                                     // output features per job
-constexpr int KF = 32;                                     // k per MFMA
+// (MT = 16 output features per job, KF = 32 k per MFMA, the tail's TAIL_USED of TAIL_QUADS positions and enc_ksteps32: half_layout.h)
 constexpr int DA = 4;                                      // A-operand pipeline depth (fragments in flight)
 constexpr int BSLOT_QUADS = 32;
 constexpr int BSLOT_BYTES = BSLOT_QUADS * QUAD_BYTES;      // 32 KiB
 constexpr int BNSLOT = 3;
 constexpr int BRING_BYTES = BNSLOT * BSLOT_BYTES;
 __host__ __device__ constexpr int bdma_of(int nwv) { return BSLOT_QUADS / nwv; }      // DMAs per wave per slot (NWV waves per workgroup)
-constexpr int TAIL_USED = 128 + 8 + 64 + 4;                // quads of the tail body that carry weights
-constexpr int TAIL_QUADS = 224;                            // ... padded to whole slots
-
-__host__ __device__ constexpr int enc_ksteps32(int L) { return (3 + 6 * L + KF - 1) / KF; }
 
 // ---------------------------------------------------------------------------------------------
 // device
@@ -859,15 +851,12 @@ static int launch_half(MlpArgsB a, long long split, long long n_wtiles, hipStrea
     return MI_NERF_OK;
 }
 
-// The blob as the kernel reads it: where the stream and the side tables are, and the stream's length as the ring walks it (bf16: the
-// blob's stream; f16: body + 224 positions of 2 KiB, see bring_next_fetch).
-struct HalfBlob { uint32_t stream_off, stream_bytes, side_off, side_floats, bias_trunk, bias_feat, bias_d, head_b, wdir_t; };
-
-// The launch plan (mlp_rays_bf16 / mlp_rays_f16; the caller has checked the network).
+// The launch plan (mlp_rays_bf16 / mlp_rays_f16; the caller has checked the network).  L: the blob's layout (half_layout.h); the ring
+// walks L.walk_bytes of stream (bf16: the blob's stream; f16: body + 224 positions of 2 KiB, see bring_next_fetch).
 // points_per_wave: 0 = chosen per launch (pick_np), 64 / 32 = forced (A/B measurements, parity tests of each shape)
 // z_dev == NULL (strat != NULL): the kernel draws the stratified depths of render_rays' coarse pass itself and writes them to strat->z_out
 template <bool F16>
-static int mlp_rays_half(const mi_nerf_net* net, const HalfBlob& L, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays,
+static int mlp_rays_half(const mi_nerf_net* net, const HalfLayout& L, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays,
                          int S, float* raw_dev, hipStream_t st, int points_per_wave, const StratDraw* strat, FineDraw* fine) {
     MN_CHECK_ARG(n_rays >= 0 && S >= 1, "bad sizes n_rays=%lld S=%d", (long long)n_rays, S);
     MN_CHECK_ARG(points_per_wave == 0 || points_per_wave == 32 || points_per_wave == 64, "points_per_wave must be 0 (auto), 32 or 64 (got %d)",
@@ -889,7 +878,7 @@ static int mlp_rays_half(const mi_nerf_net* net, const HalfBlob& L, const void* 
     a.n_rays = (unsigned)n_rays;
     a.D = net->D;
     a.skip_layer = (net->skip >= 0 && net->skip + 1 < net->D) ? net->skip + 1 : -1;
-    a.stream_bytes = L.stream_bytes; a.side_floats = L.side_floats;
+    a.stream_bytes = L.walk_bytes; a.side_floats = L.side_floats;
     a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d; a.o_head_b = L.head_b; a.o_wdir_t = L.wdir_t;
     if (points_per_wave == 64) return launch_half<4, 0, 4, F16>(a, n_wtiles, n_wtiles, st);
     if (points_per_wave == 32) return launch_half<2, 0, 4, F16>(a, n_wtiles, n_wtiles, st);

@@ -5,9 +5,7 @@
 // Output: the blob described in layout.h (header | MFMA A-operand stream | natural-order side tables).
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include <vector>
-#include "common.h"
-#include "layout.h"
+#include "half_layout.h"
 
 namespace minerf {
 
@@ -223,29 +221,38 @@ int pack_bwd_fp32(const mi_nerf_net* net, const mi_nerf_params* p, void* blob, s
     return MI_NERF_OK;
 }
 
+// index-valued parameters (half_layout.h IndexParams): what every gather map is packed from
+int make_index_params(const mi_nerf_net* net, IndexParams& ip) {
+    const int D = net->D;
+    const ParamOffsets po = make_param_offsets(D, net->W, net->skip, net->L_x, net->L_d);
+    MN_CHECK_ARG(po.total < (1u << 24), "network too large for the index map (%u parameters)", po.total);
+    std::vector<float>& flat = ip.flat;
+    flat.resize(po.total);
+    for (uint32_t i = 0; i < po.total; ++i) flat[i] = (float)(i + 1);
+    ip.wx.resize(D); ip.bx.resize(D);
+    for (int l = 0; l < D; ++l) { ip.wx[l] = flat.data() + po.w_x[l]; ip.bx[l] = flat.data() + po.b_x[l]; }
+    mi_nerf_params& p = ip.p = mi_nerf_params{};
+    p.linear_x_w = ip.wx.data(); p.linear_x_b = ip.bx.data();
+    p.linear_density_w = flat.data() + po.w_dens; p.linear_density_b = flat.data() + po.b_dens;
+    p.linear_feat_w = flat.data() + po.w_feat; p.linear_feat_b = flat.data() + po.b_feat;
+    p.linear_d_w = flat.data() + po.w_d; p.linear_d_b = flat.data() + po.b_d;
+    p.linear_color_w = flat.data() + po.w_color; p.linear_color_b = flat.data() + po.b_color;
+    return MI_NERF_OK;
+}
+
 // Gather map for packing ON THE DEVICE (training re-packs after every optimiser step): run the host packer over a
 // parameter set whose values are their own flat indices + 1 (exact in fp32 below 2^24); every blob float then names
 // its source (0 = constant zero / header).  kind 0: forward blob, 1: backward-data blob.
 int pack_map(const mi_nerf_net* net, int kind, int32_t* map, size_t map_len) {
     const int D = net->D, W = net->W;
-    const ParamOffsets po = make_param_offsets(D, W, net->skip, net->L_x, net->L_d);
-    MN_CHECK_ARG(po.total < (1u << 24), "network too large for the index map (%u parameters)", po.total);
     MN_CHECK_ARG(kind == 0 || kind == 1, "kind must be 0 (forward) or 1 (backward)");
     MN_CHECK_ARG(kind == 0 || native_width(W), "the training kernels exist for W = 128 and 256 (got %d; inference pads narrower networks)", W);
     const size_t bytes = kind == 0 ? make_layout(D, W, net->skip, net->L_x, net->L_d).total_bytes : packed_bytes_bwd(net);
     MN_CHECK_ARG(map && map_len * 4 >= bytes, "map too small: %zu entries for %zu bytes", map_len, bytes);
-    std::vector<float> flat(po.total);
-    for (uint32_t i = 0; i < po.total; ++i) flat[i] = (float)(i + 1);
-    std::vector<const float*> wx(D), bx(D);
-    for (int l = 0; l < D; ++l) { wx[l] = flat.data() + po.w_x[l]; bx[l] = flat.data() + po.b_x[l]; }
-    mi_nerf_params p{};
-    p.linear_x_w = wx.data(); p.linear_x_b = bx.data();
-    p.linear_density_w = flat.data() + po.w_dens; p.linear_density_b = flat.data() + po.b_dens;
-    p.linear_feat_w = flat.data() + po.w_feat; p.linear_feat_b = flat.data() + po.b_feat;
-    p.linear_d_w = flat.data() + po.w_d; p.linear_d_b = flat.data() + po.b_d;
-    p.linear_color_w = flat.data() + po.w_color; p.linear_color_b = flat.data() + po.b_color;
+    IndexParams ip;
+    if (int rc = make_index_params(net, ip)) return rc;
     std::vector<float> blob(bytes / 4);
-    if (int rc = kind == 0 ? pack_fp32(net, &p, blob.data(), bytes) : pack_bwd_fp32(net, &p, blob.data(), bytes)) return rc;
+    if (int rc = kind == 0 ? pack_fp32(net, &ip.p, blob.data(), bytes) : pack_bwd_fp32(net, &ip.p, blob.data(), bytes)) return rc;
     for (size_t i = 0; i < HEADER_BYTES / 4; ++i) map[i] = 0;                   // header words are not floats
     for (size_t i = HEADER_BYTES / 4; i < bytes / 4; ++i) map[i] = (int32_t)blob[i];
     return MI_NERF_OK;

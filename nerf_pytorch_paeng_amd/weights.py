@@ -183,23 +183,37 @@ class PackedNeRF:
             return self._sd
         return {**padded_state_dict(self._sd, "model_coarse.", self.net, wide), **padded_state_dict(self._sd, "model_fine.", self.net, wide)}
 
+    def _half_blobs(self, kind: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(coarse, fine) blobs of a 16-bit ``kind`` ("bf16" / "f16s") for the padded 256-wide network: packed on the device through the
+        cached gather map when this PackedNeRF came from an nn.Module (``_flat``), on the host from the kept state dict otherwise."""
+        f16s = kind == "f16s"
+        wide = self.kernel_net(bf16=not f16s, f16s=f16s)
+        if self._flat is None:
+            if self._sd is None:
+                raise MiNerfError(f"{'f16-split' if f16s else 'bf16'} packing needs the state dict (keep_state=True)")
+            sd = self._wide_sd(wide)
+            return tuple(ops.pack_module(sd, prefix, wide, bf16=not f16s, f16s=f16s).to(self.device) for prefix in ("model_coarse.", "model_fine."))
+        gather = _gather_map(kind, wide, self.device)
+        if not f16s:
+            return tuple(ops.pack_apply_bf16(wide, gather, flat) for flat in self._wide_flats(wide))
+        self.f16s_out_of_range = torch.zeros(1, dtype=torch.int32, device=self.device)
+        blobs = tuple(ops.pack_apply_f16s(wide, gather, flat, self.f16s_out_of_range) for flat in self._wide_flats(wide))
+        # the 4-byte read synchronises the host: pay it once per parameter VERSION of the module, not once per render call
+        # (packed_for() makes a new PackedNeRF per call).  A write through p.data does not bump the version; a weight pushed
+        # out of range that way still cannot give a finite wrong colour -- it packs to NaN and the frame is NaN.
+        module, version_key = self._range_token if self._range_token is not None else (None, None)
+        if module is None or _f16s_verdicts.get(module) != version_key:
+            self.check_f16s_range()
+            if module is not None:
+                _f16s_verdicts[module] = version_key
+        return blobs
+
     def bf16(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """bf16-stream blobs for the bf16 MFMA variant, packed lazily: on the device from the flat parameter vectors when this
         PackedNeRF came from an nn.Module (packed_for() makes a new one per call, so a host round trip here would be paid per
         call), on the host from the kept state dict otherwise (once).  Pass them to the library with ``kernel_net(bf16=True)``."""
         if self._bf16 is None:
-            wide = self.kernel_net(bf16=True)
-            if self._flat is not None:
-                key = (tuple(getattr(wide, f) for f, _ in Net._fields_), str(self.device))
-                if key not in _maps_bf16:
-                    _maps_bf16[key] = ops.pack_map_bf16(wide).to(self.device)
-                self._bf16 = tuple(ops.pack_apply_bf16(wide, _maps_bf16[key], flat) for flat in self._wide_flats(wide))
-            else:
-                if self._sd is None:
-                    raise MiNerfError("bf16 packing needs the state dict (keep_state=True)")
-                sd = self._wide_sd(wide)
-                self._bf16 = (ops.pack_module(sd, "model_coarse.", wide, bf16=True).to(self.device),
-                              ops.pack_module(sd, "model_fine.", wide, bf16=True).to(self.device))
+            self._bf16 = self._half_blobs("bf16")
         return self._bf16
 
     def f16s(self) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -211,28 +225,7 @@ class PackedNeRF:
         parameters (a 4-byte device -> host read; later render calls on unchanged parameters reuse the verdict and do not synchronise;
         a frozen PackedNeRF pays it once): every caller of the split-precision mode gets the refusal the host packer gives."""
         if self._f16s is None:
-            wide = self.kernel_net(f16s=True)
-            if self._flat is not None:
-                key = (tuple(getattr(wide, f) for f, _ in Net._fields_), str(self.device))
-                if key not in _maps_f16s:
-                    _maps_f16s[key] = ops.pack_map_f16s(wide).to(self.device)
-                self.f16s_out_of_range = torch.zeros(1, dtype=torch.int32, device=self.device)
-                blobs = tuple(ops.pack_apply_f16s(wide, _maps_f16s[key], flat, self.f16s_out_of_range) for flat in self._wide_flats(wide))
-                # the 4-byte read synchronises the host: pay it once per parameter VERSION of the module, not once per render call
-                # (packed_for() makes a new PackedNeRF per call).  A write through p.data does not bump the version; a weight pushed
-                # out of range that way still cannot give a finite wrong colour -- it packs to NaN and the frame is NaN.
-                module, version_key = self._range_token if self._range_token is not None else (None, None)
-                if module is None or _f16s_verdicts.get(module) != version_key:
-                    self.check_f16s_range()
-                    if module is not None:
-                        _f16s_verdicts[module] = version_key
-                self._f16s = blobs
-            else:
-                if self._sd is None:
-                    raise MiNerfError("f16-split packing needs the state dict (keep_state=True)")
-                sd = self._wide_sd(wide)
-                self._f16s = (ops.pack_module(sd, "model_coarse.", wide, f16s=True).to(self.device),
-                              ops.pack_module(sd, "model_fine.", wide, f16s=True).to(self.device))
+            self._f16s = self._half_blobs("f16s")
         return self._f16s
 
     def check_f16s_range(self) -> int:
@@ -272,10 +265,16 @@ def packed_for(model, device=None) -> PackedNeRF:
 
 # module -> the parameter-version key ((data_ptr, _version) of every parameter) whose split-precision range check came back clean
 _f16s_verdicts: "weakref.WeakKeyDictionary[torch.nn.Module, tuple]" = weakref.WeakKeyDictionary()
-# gather maps per network shape (built once by the host packer, kept on the device)
+# gather maps (built once by the host packer, kept on the device), keyed by (blob kind, network fields, device)
 _maps: Dict[tuple, torch.Tensor] = {}
-_maps_bf16: Dict[tuple, torch.Tensor] = {}
-_maps_f16s: Dict[tuple, torch.Tensor] = {}
+_MAP_BUILDERS = {"fp32": lambda net: ops.pack_map(net, False), "bf16": ops.pack_map_bf16, "f16s": ops.pack_map_f16s}
+
+
+def _gather_map(kind: str, net: Net, device) -> torch.Tensor:
+    key = (kind, tuple(getattr(net, f) for f, _ in Net._fields_), str(device))
+    if key not in _maps:
+        _maps[key] = _MAP_BUILDERS[kind](net).to(device)
+    return _maps[key]
 
 
 def _pack_module_on_device(model: torch.nn.Module, device: torch.device) -> PackedNeRF:
@@ -286,11 +285,9 @@ def _pack_module_on_device(model: torch.nn.Module, device: torch.device) -> Pack
     fine_net = infer_net(sd, "model_fine.")
     if tuple(getattr(net, f) for f, _ in Net._fields_) != tuple(getattr(fine_net, f) for f, _ in Net._fields_):
         raise MiNerfError("coarse and fine networks differ in shape")
-    key = (tuple(getattr(net, f) for f, _ in Net._fields_), str(device))
-    if key not in _maps:
-        _maps[key] = ops.pack_map(net, False).to(device)
+    gather = _gather_map("fp32", net, device)
     flats = [ops.flatten_params(sd, prefix, net, device) for prefix in ("model_coarse.", "model_fine.")]
-    blobs = [ops.pack_apply(_maps[key], flat) for flat in flats]
+    blobs = [ops.pack_apply(gather, flat) for flat in flats]
     packed = PackedNeRF(net, blobs[0], blobs[1])
     packed._flat = (flats[0], flats[1])      # the bf16 variant is packed from these, lazily, on the device
     packed._range_token = (model, tuple((p.data_ptr(), p._version) for p in model.parameters()))

@@ -1,6 +1,6 @@
 """Lane-level numpy emulation of mlp_bf16.hip's dataflow, driven by a packed bf16 blob.
 
-Checks the host packer (pack_bf16 in mlp_bf16.hip) and the kernel's operand bookkeeping without a GPU: it walks the weight
+Checks the host packer (pack_bf16 in pack_half.hip) and the kernel's operand bookkeeping without a GPU: it walks the weight
 stream quad by quad in the kernel's order (output-tile-major jobs of 16 features, the density / colour tiles, the padded tail),
 applies v_mfma_f32_16x16x32_bf16 semantics
     A fragment: lane l (i = l&15, q = l>>4), element j -> A[i][k = 8q + j]

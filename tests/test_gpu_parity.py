@@ -838,7 +838,7 @@ def test_bf16_small_coarse_launch_does_the_middle_of_render_rays_itself(n, Sc, N
 def test_bf16_other_depths_and_skip_positions(D, skip, lego_rays):
     """The bf16 kernel addresses its B fragments by explicit AGPR number, with two statically unrolled polarities (which fragment
     set a layer reads) and a separate instantiation for the skip layer at odd / even l -- a polarity error would give silently
-    wrong colours.  check_net_bf16 accepts D = 2..16 and any skip position (config.py:54-57 --netDepth; NeRF.py:25 skips), so each
+    wrong colours.  check_net_half accepts D = 2..16 and any skip position (config.py:54-57 --netDepth; NeRF.py:25 skips), so each
     code path runs here against the bf16 oracle: odd D (tail reads set 0), even D (set 1), the skip layer at even l
     (skip = 3, 5: layer_10<SKIP>) and at odd l (skip = 0, 4: layer_01<SKIP>), no skip at all."""
     skips = (skip,) if skip >= 0 else ()
