@@ -16,6 +16,7 @@ from nerf_pytorch_paeng_amd import nerf_process as NP
 from nerf_pytorch_paeng_amd import ops, synthetic, weights
 from nerf_pytorch_paeng_amd._lib import MiNerfError
 from oracle import restate as R
+from tests import sampling_account as SA
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -191,8 +192,16 @@ def test_f16s_config2_all_rays_vs_oracle(packed_big, lego_rays, oracle_cache):
     e_c = float((a["rgb_c"].cpu() - ref["rgb_c"]).abs().max())
     e_dc = float((a["disp_c"].cpu() - ref["disp_c"]).abs().max())
     e_f = float((a["rgb_f"].cpu() - pin["rgb_f"]).abs().max())
-    bad = float(((a["rgb_f"].cpu() - ref["rgb_f"]).abs().max(-1)[0] > 1e-4).float().mean())
+    bad = float(SA.rays_beyond(a["rgb_f"], ref["rgb_f"]).float().mean())           # a non-finite colour counts
     mse = float(((a["rgb_f"].cpu() - ref["rgb_f"]) ** 2).mean())
+    # all 4096 x 128 samples: exactly fine_z of the run's own coarse depths, weights and uniforms, every one accounted for (no allowance)
+    z_f_own, z_s_own = ops.fine_z(a["_z_c"].contiguous(), a["_weights_c"].contiguous(), 128, False, a["_u"], want_samples=True)
+    assert torch.equal(z_f_own, a["_z_f"])
+    acc = SA.fine_account(a["_z_c"], a["_weights_c"], uu, z_s_own)
+    print(f"f16s config #2 fine depths: {acc.worst()}")
+    assert int(acc.bad.sum()) == 0, acc.bad.nonzero()[:8].tolist()
+    no_flip = SA.bad_rays_without_a_flip(a["rgb_f"], ref["rgb_f"], a["_z_f"], ref["_z_f"])       # a ray off by > 1e-4 has a fine depth off by > 5e-6
+    assert not bool(no_flip.any()), no_flip.nonzero().flatten().tolist()
     mse32 = float(((a["rgb_f"] - b["rgb_f"]) ** 2).mean())
     print(f"f16s config #2, 4096 rays vs oracle: rgb_c {e_c:.2e}, disp_c {e_dc:.2e}; pinned rgb_f {e_f:.2e}; un-pinned rays off by >1e-4: {bad:.4f}, "
           f"PSNR vs oracle {R.mse2psnr(mse):.1f} dB, vs the fp32 HIP path {R.mse2psnr(max(mse32, 1e-30)):.1f} dB")

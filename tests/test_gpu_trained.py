@@ -33,6 +33,7 @@ from nerf_pytorch_paeng_amd import harness, ops, synthetic, weights
 from nerf_pytorch_paeng_amd import nerf_process as NP
 from nerf_pytorch_paeng_amd.model import NeRF, get_positional_encoder
 from oracle import restate as R
+from tests import sampling_account as SA
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -196,7 +197,18 @@ def test_trained_render_rays_vs_oracle(trained):
     e_f = float((rgb_pin.cpu() - ref["rgb_f"]).abs().max())
     e_disp = float((disp_pin.cpu() - ref["disp_f"]).abs().max())
     per_ray = (got["rgb_f"].cpu() - ref["rgb_f"]).abs().max(-1)[0]
-    bad = float((per_ray > 1e-4).float().mean())
+    bad = float(SA.rays_beyond(got["rgb_f"], ref["rgb_f"]).float().mean())         # a non-finite colour counts
+    # every fine sample of the run: exactly fine_z of the run's own coarse depths, weights and uniforms, and accounted for (no allowance) --
+    # trained weights put most empty bins on sample_pdf's denom < 1e-5 threshold
+    det = cfg.perturb == 0.0
+    u_dev = None if det else u.to(DEV)
+    z_f_own, z_s_own = ops.fine_z(got["_z_c"].contiguous(), got["_weights_c"].contiguous(), geo.NF, det, u_dev, want_samples=True)
+    assert torch.equal(z_f_own, got["_z_f"])
+    sa = SA.fine_account(got["_z_c"], got["_weights_c"], None if det else u, z_s_own)
+    print(f"\n[{trained.scene}] fine depths: {sa.worst()}")
+    assert int(sa.bad.sum()) == 0, sa.bad.nonzero()[:8].tolist()
+    no_flip = SA.bad_rays_without_a_flip(got["rgb_f"], ref["rgb_f"], got["_z_f"], ref["_z_f"])   # a ray off by > 1e-4 has a fine depth off by > 5e-6
+    assert not bool(no_flip.any()), no_flip.nonzero().flatten().tolist()
     acc = ref["_acc_f"]
     print(f"\n[{trained.scene}] trained weights, {n} rays: rgb_c max err {e_c:.2e} (raw_c {e_raw_c:.2e}, max |raw| {float(ref['_raw_c'].abs().max()):.1f}), "
           f"rgb_f depth-pinned {e_f:.2e} (disp {e_disp:.2e}), un-pinned rays beyond 1e-4: {bad * 100:.2f} % (worst {float(per_ray.max()):.2e}); "
