@@ -1,4 +1,4 @@
-"""Build libmi_nerf.so and libmi_nerf_iqa.so with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libmi_nerf.so, libmi_nerf_iqa.so and libmi_nerf_occ.so with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m nerf_pytorch_paeng_amd.build [--force]          the shipped libraries (clean build: ~1 min 20 s on 8 cores)
     python -m nerf_pytorch_paeng_amd.build --variant TAG -DFOO -DBAR=1     an A/B variant (tools/ab_probe.py)
@@ -12,6 +12,8 @@ What lands where:
                                                     objects needed -- the GPU box gets neither).
   nerf_pytorch_paeng_amd/libmi_nerf_iqa.so (+ .stamp)   the image-quality metrics (include/mi_nerf_iqa.h, csrc/iqa.hip): a library of its own with a stamp
                                                     of its own; libmi_nerf.so's sources and stamp inputs do not know it.
+  nerf_pytorch_paeng_amd/libmi_nerf_occ.so (+ .stamp)   occupancy-grid rendering (include/mi_nerf_occ.h, csrc/occ.hip): a third library with a stamp of its
+                                                    own, linked against libmi_nerf.so (rpath $ORIGIN), whose public entries it calls.
   build_scratch/obj/                                objects of the shipped library (cache; tests/test_packing_cpu.py disassembles them)
   build_scratch/obj_TAG/, build_scratch/libmi_nerf_TAG.so    variants.  build_scratch/ is git-ignored AND gpurun-ignored: a variant is
                                                     built where it is used (tools/ab_probe.py builds the ones it is asked for on the box).
@@ -37,6 +39,10 @@ SOURCES = ["api.hip", "stages.hip", "mlp_fp32.hip", "mlp_fp32_wide.hip", "mlp_bf
 IQA_LIB = os.path.join(HERE, "libmi_nerf_iqa.so")
 IQA_STAMP = IQA_LIB + ".stamp"
 IQA_SOURCES = ["iqa.hip"]
+# libmi_nerf_occ.so: its own source and header; it includes mi_nerf.h (types, public entries) and links against libmi_nerf.so
+OCC_LIB = os.path.join(HERE, "libmi_nerf_occ.so")
+OCC_STAMP = OCC_LIB + ".stamp"
+OCC_SOURCES = ["occ.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          # the MLP kernel's register-resident design needs its k-loops FULLY unrolled (static register indices)
@@ -60,6 +66,10 @@ def _headers():
 
 def _iqa_headers():
     return [os.path.join(INCLUDE, "mi_nerf_iqa.h")]
+
+
+def _occ_headers():
+    return [os.path.join(INCLUDE, "mi_nerf_occ.h"), os.path.join(INCLUDE, "mi_nerf.h")]
 
 
 def _digest(paths, extra=()) -> str:
@@ -107,8 +117,8 @@ def ensure_object(src: str) -> str:
     return _compile(src, False)
 
 
-def _link(objs, lib: str) -> None:
-    r = subprocess.run([_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", lib], capture_output=True, text=True)
+def _link(objs, lib: str, extra=()) -> None:
+    r = subprocess.run([_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, *extra, "-o", lib], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
 
@@ -147,6 +157,30 @@ def build_iqa_library(force: bool = False, verbose: bool = False) -> str:
     if verbose:
         print(f"built {IQA_LIB} ({os.path.getsize(IQA_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
     return IQA_LIB
+
+
+OCC_LINK = ["-L" + HERE, "-lmi_nerf", "-Wl,-rpath,$ORIGIN"]
+
+
+def occ_source_stamp() -> str:
+    return _digest([os.path.join(CSRC, s) for s in OCC_SOURCES] + _occ_headers(), [FLAGS, OCC_LINK[1:]])
+
+
+def build_occ_library(force: bool = False, verbose: bool = False) -> str:
+    """libmi_nerf_occ.so, a no-op when its stamp matches (like build_library).  It links against libmi_nerf.so, which is built first."""
+    build_library()
+    want = occ_source_stamp()
+    if not force and os.path.exists(OCC_LIB) and os.path.exists(OCC_STAMP) and open(OCC_STAMP).read() == want:
+        if verbose:
+            print(f"up to date: {OCC_LIB} ({os.path.getsize(OCC_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+        return OCC_LIB
+    objs = [_compile(s, force, headers=_occ_headers()) for s in OCC_SOURCES]
+    _link(objs, OCC_LIB, OCC_LINK)
+    with open(OCC_STAMP, "w") as fh:
+        fh.write(want)
+    if verbose:
+        print(f"built {OCC_LIB} ({os.path.getsize(OCC_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+    return OCC_LIB
 
 
 def variant_path(tag: str) -> str:
@@ -194,3 +228,4 @@ if __name__ == "__main__":
     else:
         print(build_library(force="--force" in sys.argv, verbose=True))
         print(build_iqa_library(force="--force" in sys.argv, verbose=True))
+        print(build_occ_library(force="--force" in sys.argv, verbose=True))

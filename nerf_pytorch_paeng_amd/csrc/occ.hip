@@ -1,0 +1,513 @@
+// occ.hip -- libmi_nerf_occ.so (include/mi_nerf_occ.h): occupancy-grid rendering.  The networks of an object scene are evaluated only at the
+// samples a baked one-bit-per-cell density grid marks occupied; a skipped sample's raw output is (0,0,0,0), which post_process turns into
+// weight 0 exactly.  A library of its own: it links against libmi_nerf.so and reaches the networks and the stages through public entries only.
+//
+// occ_mark_kernel      one thread per sample: THE CELL RULE of the header, as a uint8 mask
+// occ_cull_kernel      one wave per ray: lookup per lane, ballot + prefix count -> compacted 32-sample tiles (pseudo-rays with S = 32), padded
+//                      with the ray's last survivor; tiles are reserved with one atomic add per ray (tile ORDER varies from run to run, a
+//                      sample's value does not: each lane of the network kernels evaluates its own point)
+// occ_scatter_kernel   one thread per sample: raw[ray, sample] = tile value of a survivor, zeros otherwise (every element written)
+// occ_bake_gen_kernel  sub-lattice rows along x as rays (origin on the box face, direction +x) with depths
+// occ_bake_reduce_kernel   OR of (density > sigma_min) over a cell's samples of one row, atomically ORed into the cell's bit
+// occ_dilate_kernel    one thread per cell, neighbourhood OR, words assembled by ballot
+// occ_count_kernel     popcount of the grid's cells
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include "../../include/mi_nerf_occ.h"
+
+namespace miocc {
+
+// ---- error plumbing (the conventions of api.hip) -----------------------------------------------------
+static thread_local char g_err[768] = "";
+static void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+static int hip_fail(hipError_t e, const char* what) {
+    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
+    return MI_OCC_EHIP;
+}
+// a failed call into libmi_nerf.so: its status becomes ours (EINVAL stays EINVAL), its text is carried over
+static int nerf_fail(int rc, const char* what) {
+    set_error("%s failed (status %d): %s", what, rc, mi_nerf_last_error());
+    return rc == MI_NERF_EINVAL ? MI_OCC_EINVAL : MI_OCC_EHIP;
+}
+#define OCC_CHECK_ARG(cond, ...)               \
+    do {                                       \
+        if (!(cond)) {                         \
+            ::miocc::set_error(__VA_ARGS__);   \
+            return MI_OCC_EINVAL;              \
+        }                                      \
+    } while (0)
+#define OCC_HIP(call)                                                   \
+    do {                                                                \
+        hipError_t e__ = (call);                                        \
+        if (e__ != hipSuccess) return ::miocc::hip_fail(e__, #call);    \
+    } while (0)
+#define OCC_LAUNCH_CHECK(name)                                              \
+    do {                                                                    \
+        hipError_t e__ = hipGetLastError();                                 \
+        if (e__ != hipSuccess) return ::miocc::hip_fail(e__, "launch " name); \
+    } while (0)
+#define OCC_NERF(call)                                          \
+    do {                                                        \
+        int rc__ = (call);                                      \
+        if (rc__ != MI_NERF_OK) return ::miocc::nerf_fail(rc__, #call); \
+    } while (0)
+
+constexpr int TILE = MI_OCC_TILE;
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- the grid as the kernels see it ----------------------------------------------------------------
+struct GridDev {
+    float lo[3], scale[3], fres[3];
+    int res[3];
+    int outside;
+    long long cells;
+};
+
+static int resolve_grid(const mi_occ_grid* g, GridDev* out) {
+    OCC_CHECK_ARG(g != nullptr, "grid is NULL");
+    GridDev G;
+    G.cells = 1;
+    for (int i = 0; i < 3; ++i) {
+        OCC_CHECK_ARG(g->res[i] >= 1 && g->res[i] <= MI_OCC_MAX_RES, "grid res[%d]=%d: 1..%d", i, g->res[i], MI_OCC_MAX_RES);
+        OCC_CHECK_ARG(isfinite(g->lo[i]) && isfinite(g->hi[i]) && g->lo[i] < g->hi[i], "grid box: lo[%d]=%g must be below hi[%d]=%g, both finite", i,
+                      (double)g->lo[i], i, (double)g->hi[i]);
+        const float ext = g->hi[i] - g->lo[i];
+        G.lo[i] = g->lo[i];
+        G.scale[i] = (float)g->res[i] / ext;
+        OCC_CHECK_ARG(isfinite(ext) && isfinite(G.scale[i]) && G.scale[i] > 0.0f, "grid box: extent %g of axis %d has no finite fp32 cell scale", (double)ext, i);
+        G.fres[i] = (float)g->res[i];
+        G.res[i] = g->res[i];
+        G.cells *= g->res[i];
+    }
+    G.outside = g->outside_occupied != 0;
+    *out = G;
+    return MI_OCC_OK;
+}
+
+static inline size_t grid_words(const GridDev& G) { return (size_t)((G.cells + 31) / 32); }
+
+// THE CELL RULE.  -ffp-contract=off: the product is rounded, then the sum (nerf_process.py:69-70).
+__device__ __forceinline__ bool occ_lookup(const GridDev& G, const uint32_t* __restrict__ bits, const float o[3], const float d[3], float z) {
+    float c[3];
+    bool inside = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float p = o[i] + d[i] * z;
+        c[i] = floorf((p - G.lo[i]) * G.scale[i]);
+        inside = inside && c[i] >= 0.0f && c[i] < G.fres[i];          // a NaN fails both
+    }
+    if (!inside) return G.outside != 0;
+    const int b = ((int)c[2] * G.res[1] + (int)c[1]) * G.res[0] + (int)c[0];
+    return (bits[b >> 5] >> (b & 31)) & 1u;
+}
+
+__global__ __launch_bounds__(256) void occ_mark_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
+                                                       const float* __restrict__ z, long long n_pts, int S, uint8_t* __restrict__ mask) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_pts) return;
+    const float* rp = rays + (i / S) * 6;
+    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
+    mask[i] = occ_lookup(G, bits, o, d, z[i]) ? 1 : 0;
+}
+
+// ---- cull + compact --------------------------------------------------------------------------------
+// One wave = one ray (4 per workgroup; no workgroup barrier).  Pass 1 counts the survivors, lane 0 reserves ceil(count / 32) tiles, pass 2
+// repeats the lookups and writes.  counters[0] += tiles, counters[1] += survivors.
+__global__ __launch_bounds__(256) void occ_cull_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
+                                                       const float* __restrict__ z, long long n, int S, float* __restrict__ tile_rays,
+                                                       float* __restrict__ tile_z, int* __restrict__ tile_src, int* __restrict__ slot,
+                                                       unsigned* __restrict__ counters) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n) return;
+    const float* rp = rays + ray * 6;
+    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
+    const float* zr = z + ray * S;
+    int cnt = 0;
+    for (int c = 0; c < S; c += 64) {
+        const int s = c + lane;
+        const bool occ = s < S && occ_lookup(G, bits, o, d, zr[s]);
+        cnt += __popcll(__ballot(occ));
+    }
+    const int ntiles = (cnt + TILE - 1) / TILE;
+    unsigned base = 0;
+    if (lane == 0 && ntiles > 0) {
+        base = atomicAdd(&counters[0], (unsigned)ntiles);
+        atomicAdd(&counters[1], (unsigned)cnt);
+    }
+    base = __shfl(base, 0, 64);
+    const int j0 = (int)base * TILE;                                  // first flat tile lane of this ray
+    int run = 0;
+    float last_z = 0.0f;
+    for (int c = 0; c < S; c += 64) {
+        const int s = c + lane;
+        const float zv = s < S ? zr[s] : 0.0f;
+        const bool occ = s < S && occ_lookup(G, bits, o, d, zv);
+        const unsigned long long m = __ballot(occ);
+        const int j = j0 + run + __popcll(m & ((1ull << lane) - 1ull));
+        if (s < S) slot[ray * S + s] = occ ? j : -1;
+        if (occ) {
+            tile_z[j] = zv;
+            tile_src[j] = (int)(ray * S + s);
+        }
+        run += __popcll(m);
+        if (m) last_z = __shfl(zv, 63 - __clzll((long long)m), 64);
+    }
+    const int pad = ntiles * TILE - cnt;                              // < 32
+    if (lane < pad) {
+        tile_z[j0 + cnt + lane] = last_z;
+        tile_src[j0 + cnt + lane] = -1;
+    }
+    for (int i = lane; i < ntiles * 6; i += 64) tile_rays[(long long)base * 6 + i] = rp[i % 6];
+}
+
+__global__ __launch_bounds__(256) void occ_scatter_kernel(const int* __restrict__ slot, const float4* __restrict__ tile_raw, long long n_pts,
+                                                          float4* __restrict__ raw) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_pts) return;
+    const int j = slot[i];
+    raw[i] = j >= 0 ? tile_raw[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// ---- bake ------------------------------------------------------------------------------------------
+struct BakeGeom {
+    float lo[3], step[3];
+    int rx, ry, rz, sub;        // cells per axis
+    int S;                      // rx * sub: lattice points of a row = depths of a ray
+    long long rows;             // ry * sub * rz * sub
+};
+
+__global__ __launch_bounds__(256) void occ_bake_gen_kernel(BakeGeom B, long long row0, long long n_rows, float* __restrict__ rays, float* __restrict__ z) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows * B.S) return;
+    const long long r = i / B.S;
+    const int jx = (int)(i - r * B.S);
+    z[i] = ((float)jx + 0.5f) * B.step[0];
+    if (jx == 0) {
+        const long long row = row0 + r;
+        const int ny = B.ry * B.sub;
+        const int jz = (int)(row / ny), jy = (int)(row - (long long)jz * ny);
+        float* rp = rays + r * 6;
+        rp[0] = B.lo[0];
+        rp[1] = B.lo[1] + ((float)jy + 0.5f) * B.step[1];
+        rp[2] = B.lo[2] + ((float)jz + 0.5f) * B.step[2];
+        rp[3] = 1.0f;
+        rp[4] = 0.0f;
+        rp[5] = 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(256) void occ_bake_reduce_kernel(BakeGeom B, long long row0, long long n_rows, const float* __restrict__ raw, float sigma_min,
+                                                              uint32_t* __restrict__ bits) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows * B.rx) return;
+    const long long r = i / B.rx;
+    const int ix = (int)(i - r * B.rx);
+    const float* p = raw + (r * B.S + (long long)ix * B.sub) * 4 + 3;
+    bool any = false;
+    for (int a = 0; a < B.sub; ++a) any = any || p[a * 4] > sigma_min;      // a NaN density is not above the threshold
+    if (!any) return;
+    const long long row = row0 + r;
+    const int ny = B.ry * B.sub;
+    const int jz = (int)(row / ny), jy = (int)(row - (long long)jz * ny);
+    const int b = ((jz / B.sub) * B.ry + jy / B.sub) * B.rx + ix;
+    atomicOr(&bits[b >> 5], 1u << (b & 31));
+}
+
+// ---- dilate, count ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void occ_dilate_kernel(GridDev G, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int radius) {
+    const long long cell = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool any = false;
+    if (cell < G.cells) {
+        const int rx = G.res[0], ry = G.res[1], rz = G.res[2];
+        const int cx = (int)(cell % rx), cy = (int)((cell / rx) % ry), cz = (int)(cell / ((long long)rx * ry));
+        for (int dz = -radius; dz <= radius; ++dz)
+            for (int dy = -radius; dy <= radius; ++dy)
+                for (int dx = -radius; dx <= radius; ++dx) {
+                    const int x = cx + dx, y = cy + dy, zz = cz + dz;
+                    if (x < 0 || x >= rx || y < 0 || y >= ry || zz < 0 || zz >= rz) continue;
+                    const int b = (zz * ry + y) * rx + x;
+                    any = any || ((in[b >> 5] >> (b & 31)) & 1u);
+                }
+    }
+    const unsigned long long m = __ballot(any);                        // 64 consecutive cells: two words
+    const int lane = threadIdx.x & 63;
+    const long long w0 = (cell - lane) >> 5;                           // cell - lane is a multiple of 64
+    const long long words = (G.cells + 31) >> 5;
+    if (lane == 0 && w0 < words) out[w0] = (uint32_t)m;
+    if (lane == 32 && w0 + 1 < words) out[w0 + 1] = (uint32_t)(m >> 32);
+}
+
+__global__ __launch_bounds__(256) void occ_count_kernel(GridDev G, const uint32_t* __restrict__ bits, unsigned long long* __restrict__ count) {
+    const long long words = (G.cells + 31) >> 5;
+    unsigned long long c = 0;
+    for (long long w = (long long)blockIdx.x * 256 + threadIdx.x; w < words; w += (long long)gridDim.x * 256) {
+        uint32_t v = bits[w];
+        const long long left = G.cells - w * 32;                       // cells this word holds; the bits beyond them are not cells
+        if (left < 32) v &= (1u << left) - 1u;
+        c += __popc(v);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+}
+
+// ---- host side -------------------------------------------------------------------------------------
+static inline unsigned blocks_for(long long n, int per) { return (unsigned)((n + per - 1) / per); }
+
+static int resolve_bake(const mi_occ_grid* grid, int sub, GridDev* G, BakeGeom* B) {
+    if (int rc = resolve_grid(grid, G)) return rc;
+    OCC_CHECK_ARG(sub >= 1 && sub <= MI_OCC_MAX_SUB, "sub=%d: 1..%d lattice points per cell and axis", sub, MI_OCC_MAX_SUB);
+    for (int i = 0; i < 3; ++i) {
+        B->lo[i] = grid->lo[i];
+        B->step[i] = (grid->hi[i] - grid->lo[i]) / (float)(grid->res[i] * sub);
+    }
+    B->rx = grid->res[0]; B->ry = grid->res[1]; B->rz = grid->res[2]; B->sub = sub;
+    B->S = B->rx * sub;
+    B->rows = (long long)B->ry * sub * B->rz * sub;
+    return MI_OCC_OK;
+}
+
+// bytes of a slab of R rows: rays [R,6], z [R,S], raw [R,S,4]
+static inline size_t bake_slab_bytes(long long R, int S) {
+    return align256((size_t)R * 24) + align256((size_t)R * S * 4) + align256((size_t)R * S * 16);
+}
+static inline long long bake_min_rows(const BakeGeom& B) {
+    const long long want = ((1LL << 22) + B.S - 1) / B.S;
+    return want < B.rows ? want : B.rows;
+}
+
+typedef int (*mlp_rays_fn)(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, void*);
+static int mlp_entry(int mode, mlp_rays_fn* fn) {
+    switch (mode) {
+        case MI_NERF_MODE_F32:  *fn = mi_nerf_mlp_rays; return MI_OCC_OK;
+        case MI_NERF_MODE_F16S: *fn = mi_nerf_mlp_rays_f16s; return MI_OCC_OK;
+        case MI_NERF_MODE_BF16: *fn = mi_nerf_mlp_rays_bf16; return MI_OCC_OK;
+    }
+    set_error("mode %d: the occupancy path runs MI_NERF_MODE_F32 (0), MI_NERF_MODE_BF16 (1) and MI_NERF_MODE_F16S (5)", mode);
+    return MI_OCC_EINVAL;
+}
+
+static int bake(const mi_occ_grid* grid, uint32_t* bits, const mi_nerf_net* net, const void* packed, int mode, int sub, float sigma_min, int accumulate,
+                void* scratch, size_t scratch_bytes, hipStream_t st) {
+    GridDev G;
+    BakeGeom B;
+    if (int rc = resolve_bake(grid, sub, &G, &B)) return rc;
+    mlp_rays_fn fn;
+    if (int rc = mlp_entry(mode, &fn)) return rc;
+    OCC_CHECK_ARG(bits && net && packed && scratch, "NULL pointer (bits, net, packed and scratch are required)");
+    OCC_CHECK_ARG(!isnan(sigma_min), "sigma_min is NaN");
+    OCC_CHECK_ARG(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
+    const size_t need = bake_slab_bytes(bake_min_rows(B), B.S);
+    OCC_CHECK_ARG(scratch_bytes >= need, "scratch too small: %zu < %zu (mi_occ_bake_scratch_bytes)", scratch_bytes, need);
+    // the largest slab the scratch holds (three regions, each rounded up to 256 bytes)
+    long long R = (long long)((scratch_bytes - 768) / ((size_t)24 + (size_t)B.S * 20));
+    if (R < bake_min_rows(B)) R = bake_min_rows(B);                    // fits: scratch_bytes >= need
+    if (R > B.rows) R = B.rows;
+    const long long r_cap = ((1LL << 31) - 1) / B.S;                   // a slab's R x S points stay below 2^31, the bound the render path keeps
+    if (R > r_cap) R = r_cap;                                          // (never below bake_min_rows: that is about 2^22 points)
+    char* w = (char*)scratch;
+    float* rays = (float*)w;
+    float* z = (float*)(w + align256((size_t)R * 24));
+    float* raw = (float*)(w + align256((size_t)R * 24) + align256((size_t)R * B.S * 4));
+    if (!accumulate) OCC_HIP(hipMemsetAsync(bits, 0, grid_words(G) * 4, st));
+    for (long long r0 = 0; r0 < B.rows; r0 += R) {
+        const long long nr = B.rows - r0 < R ? B.rows - r0 : R;
+        hipLaunchKernelGGL(occ_bake_gen_kernel, dim3(blocks_for(nr * B.S, 256)), dim3(256), 0, st, B, r0, nr, rays, z);
+        OCC_LAUNCH_CHECK("occ_bake_gen_kernel");
+        OCC_NERF(fn(net, packed, rays, z, nr, B.S, raw, (void*)st));
+        hipLaunchKernelGGL(occ_bake_reduce_kernel, dim3(blocks_for(nr * B.rx, 256)), dim3(256), 0, st, B, r0, nr, raw, sigma_min, bits);
+        OCC_LAUNCH_CHECK("occ_bake_reduce_kernel");
+    }
+    return MI_OCC_OK;
+}
+
+// ---- render ----------------------------------------------------------------------------------------
+static int render_layout(const mi_nerf_render_cfg* cfg, int64_t n, mi_occ_workspace_layout* L) {
+    OCC_CHECK_ARG(cfg && L, "NULL cfg/layout");
+    OCC_CHECK_ARG(n >= 0 && cfg->Sc >= 1 && cfg->Nf >= 0, "bad sizes n=%lld Sc=%d Nf=%d", (long long)n, cfg->Sc, cfg->Nf);
+    OCC_CHECK_ARG(cfg->Nf == 0 || cfg->Sc >= 3, "hierarchical sampling needs at least 3 coarse samples");
+    OCC_CHECK_ARG((long long)cfg->Sc + cfg->Nf <= 1024, "Sc + Nf = %lld: at most 1024 samples per ray (mi_nerf_composite)", (long long)cfg->Sc + cfg->Nf);
+    const size_t nn = (size_t)n, Sc = (size_t)cfg->Sc, Nf = (size_t)cfg->Nf, St = Sc + Nf;
+    OCC_CHECK_ARG((long long)n * (long long)(St + 31) < (1LL << 31), "n_rays=%lld x %zu samples: n_rays * (Sc + Nf + 31) must stay below 2^31", (long long)n, St);
+    const size_t T = nn * ((St + TILE - 1) / TILE);
+    size_t off = 0;
+    L->z_c = off;       off += align256(nn * Sc * 4);
+    L->raw_c = off;     off += align256(nn * Sc * 16);
+    L->weights_c = off; off += align256(nn * Sc * 4);
+    L->z_f = off;       off += Nf > 0 ? align256(nn * St * 4) : 0;
+    L->raw_f = off;     off += Nf > 0 ? align256(nn * St * 16) : 0;
+    L->t_rand = off;    off += align256(nn * Sc * 4);
+    L->u = off;         off += Nf > 0 ? align256(nn * Nf * 4) : 0;
+    L->slot = off;      off += align256(nn * St * 4);
+    L->tile_rays = off; off += align256(T * 6 * 4);
+    L->tile_z = off;    off += align256(T * TILE * 4);
+    L->tile_src = off;  off += align256(T * TILE * 4);
+    L->tile_raw = off;  off += align256(T * TILE * 16);
+    L->counters = off;  off += 256;
+    L->total = off;
+    return MI_OCC_OK;
+}
+
+struct Pass {
+    float* tile_rays; float* tile_z; int* tile_src; float* tile_raw; int* slot; unsigned* counters;
+};
+
+// cull -> count to the host -> network over the tiles -> scatter into raw [n,S,4]
+static int network_pass(const GridDev& G, const uint32_t* bits, mlp_rays_fn fn, const mi_nerf_net* net, const void* packed, const float* rays, const float* z,
+                        int64_t n, int S, const Pass& P, float* raw, int64_t* evaluated, int64_t* padded, hipStream_t st) {
+    static thread_local unsigned* pinned = nullptr;                    // 8 bytes of pinned host memory per calling thread, kept
+    if (!pinned) OCC_HIP(hipHostMalloc((void**)&pinned, 8, hipHostMallocPortable));       // portable: the thread may render on any device later; never freed
+    OCC_HIP(hipMemsetAsync(P.counters, 0, 8, st));
+    hipLaunchKernelGGL(occ_cull_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, st, G, bits, rays, z, (long long)n, S, P.tile_rays, P.tile_z, P.tile_src, P.slot,
+                       P.counters);
+    OCC_LAUNCH_CHECK("occ_cull_kernel");
+    OCC_HIP(hipMemcpyAsync(pinned, P.counters, 8, hipMemcpyDeviceToHost, st));
+    OCC_HIP(hipStreamSynchronize(st));
+    const int64_t tiles = pinned[0], survivors = pinned[1];
+    *evaluated = survivors;
+    *padded = tiles * TILE - survivors;
+    if (tiles > 0) OCC_NERF(fn(net, packed, P.tile_rays, P.tile_z, tiles, TILE, P.tile_raw, (void*)st));
+    hipLaunchKernelGGL(occ_scatter_kernel, dim3(blocks_for((long long)n * S, 256)), dim3(256), 0, st, P.slot, (const float4*)P.tile_raw, (long long)n * S,
+                       (float4*)raw);
+    OCC_LAUNCH_CHECK("occ_scatter_kernel");
+    return MI_OCC_OK;
+}
+
+static int render(const mi_nerf_net* net, const void* packed_c, const void* packed_f, const mi_nerf_render_cfg* cfg, const mi_occ_grid* grid,
+                  const uint32_t* bits_c, const uint32_t* bits_f, const float* rays, int64_t n, const float* t_rand, const float* u, void* ws, size_t ws_bytes,
+                  float* rgb_c, float* disp_c, float* rgb_f, float* disp_f, mi_occ_stats* stats, hipStream_t st) {
+    mi_occ_workspace_layout L;
+    if (int rc = render_layout(cfg, n, &L)) return rc;
+    GridDev G;
+    if (int rc = resolve_grid(grid, &G)) return rc;
+    mlp_rays_fn fn;
+    if (int rc = mlp_entry(cfg->mode, &fn)) return rc;
+    OCC_CHECK_ARG(cfg->reserved == 0, "mi_nerf_render_cfg.reserved must be 0");
+    OCC_CHECK_ARG(net != nullptr, "net is NULL");
+    OCC_CHECK_ARG(rays && rgb_c && disp_c && packed_c && bits_c && ws, "NULL pointer (rays, rgb_c, disp_c, packed_coarse, bits_coarse and workspace are required)");
+    OCC_CHECK_ARG(cfg->Nf == 0 || (packed_f && bits_f && rgb_f && disp_f), "the fine pass needs packed_fine, bits_fine and its outputs");
+    OCC_CHECK_ARG(ws_bytes >= L.total, "workspace too small: %zu < %zu", ws_bytes, L.total);
+    OCC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
+    if (stats) *stats = mi_occ_stats{0, 0, 0, 0, 0, 0};
+    if (n == 0) return MI_OCC_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    OCC_HIP(hipStreamIsCapturing(st, &cap));
+    OCC_CHECK_ARG(cap == hipStreamCaptureStatusNone, "the stream is being captured: mi_occ_render_rays synchronises it once per network pass and cannot be recorded into a graph");
+    char* w = (char*)ws;
+    float* z_c = (float*)(w + L.z_c);
+    float* raw_c = (float*)(w + L.raw_c);
+    float* wts_c = (float*)(w + L.weights_c);
+    const Pass P{(float*)(w + L.tile_rays), (float*)(w + L.tile_z), (int*)(w + L.tile_src), (float*)(w + L.tile_raw), (int*)(w + L.slot), (unsigned*)(w + L.counters)};
+    const int Sc = cfg->Sc, St = cfg->Sc + cfg->Nf;
+    mi_occ_stats s{0, 0, 0, 0, 0, 0};
+    if (!t_rand) {
+        float* tr = (float*)(w + L.t_rand);
+        OCC_NERF(mi_nerf_fill_uniform(cfg->seed, 0, cfg->ray_offset, n, Sc, tr, (void*)st));
+        t_rand = tr;
+    }
+    OCC_NERF(mi_nerf_stratified_z(n, Sc, cfg->near_, cfg->far_, t_rand, z_c, (void*)st));
+    s.total_c = n * Sc;
+    if (int rc = network_pass(G, bits_c, fn, net, packed_c, rays, z_c, n, Sc, P, raw_c, &s.evaluated_c, &s.padded_c, st)) return rc;
+    OCC_NERF(mi_nerf_composite(raw_c, z_c, rays, 6, n, Sc, rgb_c, disp_c, nullptr, wts_c, nullptr, (void*)st));
+    if (cfg->Nf > 0) {
+        float* z_f = (float*)(w + L.z_f);
+        float* raw_f = (float*)(w + L.raw_f);
+        if (!cfg->det && !u) {
+            float* ub = (float*)(w + L.u);
+            OCC_NERF(mi_nerf_fill_uniform(cfg->seed, 1, cfg->ray_offset, n, cfg->Nf, ub, (void*)st));
+            u = ub;
+        }
+        OCC_NERF(mi_nerf_fine_z(z_c, wts_c, n, Sc, cfg->Nf, cfg->det, cfg->det ? nullptr : u, z_f, nullptr, (void*)st));
+        s.total_f = n * St;
+        if (int rc = network_pass(G, bits_f, fn, net, packed_f, rays, z_f, n, St, P, raw_f, &s.evaluated_f, &s.padded_f, st)) return rc;
+        OCC_NERF(mi_nerf_composite(raw_f, z_f, rays, 6, n, St, rgb_f, disp_f, nullptr, nullptr, nullptr, (void*)st));
+    }
+    if (stats) *stats = s;
+    return MI_OCC_OK;
+}
+
+}  // namespace miocc
+
+using namespace miocc;
+
+extern "C" {
+
+int mi_occ_abi_version(void) { return MI_OCC_ABI_VERSION; }
+const char* mi_occ_last_error(void) { return g_err; }
+
+size_t mi_occ_grid_words(const mi_occ_grid* grid) {
+    GridDev G;
+    return resolve_grid(grid, &G) == MI_OCC_OK ? grid_words(G) : 0;
+}
+
+size_t mi_occ_bake_scratch_bytes(const mi_occ_grid* grid, int sub) {
+    GridDev G;
+    BakeGeom B;
+    if (resolve_bake(grid, sub, &G, &B) != MI_OCC_OK) return 0;
+    return bake_slab_bytes(bake_min_rows(B), B.S);
+}
+
+int mi_occ_bake(const mi_occ_grid* grid, uint32_t* bits, const mi_nerf_net* net, const void* packed, int mode, int sub, float sigma_min, int accumulate,
+                void* scratch, size_t scratch_bytes, void* stream) {
+    return bake(grid, bits, net, packed, mode, sub, sigma_min, accumulate, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int mi_occ_dilate(const mi_occ_grid* grid, const uint32_t* bits_in, uint32_t* bits_out, int radius, void* stream) {
+    GridDev G;
+    if (int rc = resolve_grid(grid, &G)) return rc;
+    OCC_CHECK_ARG(radius >= 0 && radius <= MI_OCC_MAX_RADIUS, "radius=%d: 0..%d", radius, MI_OCC_MAX_RADIUS);
+    OCC_CHECK_ARG(bits_in && bits_out, "NULL pointer");
+    OCC_CHECK_ARG(bits_in != bits_out, "mi_occ_dilate works out of place: bits_out must not be bits_in");
+    hipLaunchKernelGGL(occ_dilate_kernel, dim3(blocks_for(G.cells, 256)), dim3(256), 0, (hipStream_t)stream, G, bits_in, bits_out, radius);
+    OCC_LAUNCH_CHECK("occ_dilate_kernel");
+    return MI_OCC_OK;
+}
+
+int mi_occ_count(const mi_occ_grid* grid, const uint32_t* bits, uint64_t* count, void* stream) {
+    GridDev G;
+    if (int rc = resolve_grid(grid, &G)) return rc;
+    OCC_CHECK_ARG(bits && count, "NULL pointer");
+    OCC_CHECK_ARG(((uintptr_t)count & 7) == 0, "count must be 8-byte aligned");
+    OCC_HIP(hipMemsetAsync(count, 0, 8, (hipStream_t)stream));
+    const long long words = (long long)grid_words(G);
+    const unsigned nb = blocks_for(words, 256) < 1024 ? blocks_for(words, 256) : 1024;
+    hipLaunchKernelGGL(occ_count_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, G, bits, (unsigned long long*)count);
+    OCC_LAUNCH_CHECK("occ_count_kernel");
+    return MI_OCC_OK;
+}
+
+int mi_occ_mark(const mi_occ_grid* grid, const uint32_t* bits, const float* rays, const float* z, int64_t n_rays, int S, uint8_t* mask, void* stream) {
+    GridDev G;
+    if (int rc = resolve_grid(grid, &G)) return rc;
+    OCC_CHECK_ARG(n_rays >= 0 && S >= 1 && (long long)n_rays * S < (1LL << 38), "bad sizes n_rays=%lld S=%d", (long long)n_rays, S);
+    if (n_rays == 0) return MI_OCC_OK;
+    OCC_CHECK_ARG(bits && rays && z && mask, "NULL pointer");
+    hipLaunchKernelGGL(occ_mark_kernel, dim3(blocks_for((long long)n_rays * S, 256)), dim3(256), 0, (hipStream_t)stream, G, bits, rays, z, (long long)n_rays * S, S,
+                       mask);
+    OCC_LAUNCH_CHECK("occ_mark_kernel");
+    return MI_OCC_OK;
+}
+
+size_t mi_occ_render_workspace_bytes(const mi_nerf_render_cfg* cfg, int64_t n_rays) {
+    mi_occ_workspace_layout L;
+    return render_layout(cfg, n_rays, &L) == MI_OCC_OK ? L.total : 0;
+}
+
+int mi_occ_render_workspace_layout(const mi_nerf_render_cfg* cfg, int64_t n_rays, mi_occ_workspace_layout* out) { return render_layout(cfg, n_rays, out); }
+
+int mi_occ_render_rays(const mi_nerf_net* net, const void* packed_c, const void* packed_f, const mi_nerf_render_cfg* cfg, const mi_occ_grid* grid,
+                       const uint32_t* bits_c, const uint32_t* bits_f, const float* rays, int64_t n_rays, const float* t_rand, const float* u, void* ws,
+                       size_t ws_bytes, float* rgb_c, float* disp_c, float* rgb_f, float* disp_f, mi_occ_stats* stats, void* stream) {
+    return render(net, packed_c, packed_f, cfg, grid, bits_c, bits_f, rays, n_rays, t_rand, u, ws, ws_bytes, rgb_c, disp_c, rgb_f, disp_f, stats,
+                  (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -243,7 +243,9 @@ def _frozen(model, opts):
 def _render_pose(model, posenc, K, pose, hw, opts):
     img_h, img_w = hw
     rays_o, rays_d = make_o_d(img_w, img_h, K, pose[:3, :4])
-    rgb_c, disp_c, rgb_f, disp_f = NP.batchify_rays_and_render_by_chunk(rays_o, rays_d, model, posenc, img_h, img_w, K, opts, **_precision(opts))
+    # opts.occupancy (not a flag of the reference's config.py; absent = None): an occupancy.OccupancyGrid that test() / render() skip empty space with
+    rgb_c, disp_c, rgb_f, disp_f = NP.batchify_rays_and_render_by_chunk(rays_o, rays_d, model, posenc, img_h, img_w, K, opts, **_precision(opts),
+                                                                        occupancy=getattr(opts, "occupancy", None))
     return (rgb_c, disp_c) if int(opts.N_samples_f) == 0 else (rgb_f, disp_f)             # test.py:42-47
 
 

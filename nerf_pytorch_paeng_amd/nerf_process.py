@@ -3,7 +3,8 @@
 Same function names, positional arguments and return structures as the reference
 (``batchify_rays_and_render_by_chunk``, ``render_rays``, ``pre_process``, ``post_process``,
 ``sample_pdf``, ``ndc_rays``), executed by hand-written HIP kernels through ``libmi_nerf.so``.
-Keyword-only extras (``t_rand=``, ``u=``, ``seed=``, ``ray_offset=``) make the randomness explicit:
+Keyword-only extras (``t_rand=``, ``u=``, ``seed=``, ``ray_offset=``) make the randomness explicit;
+``occupancy=`` (an ``occupancy.OccupancyGrid``) skips the networks at samples the grid marks empty (inference only):
 the reference draws unseeded ``torch.rand`` (nerf_process.py:58-60,162-163); here the default is a
 counter-based generator keyed on (seed, global ray index, sample index), so a frame renders
 identically however its rays are chunked or sharded across GPUs.
@@ -26,6 +27,7 @@ from . import ops
 from ._lib import MiNerfError, as_f32_dev
 from .weights import PackedNeRF, packed_for
 from . import train_path
+from . import occupancy as occ
 
 # rays handed to one mi_nerf_render_rays call (workspace: 5.4 KB/ray at 64+128 samples -> ~5.6 GB)
 MAX_RAYS_PER_LAUNCH = 1 << 20
@@ -144,7 +146,7 @@ def run_network(model, embedded, is_fine: bool = False):
 
 # --------------------------------------------------------------------------------------------------
 def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, ray_offset: int, prec: ops.Precision,
-            intermediates: bool) -> Dict[str, torch.Tensor]:
+            intermediates: bool, occupancy=None) -> Dict[str, torch.Tensor]:
     n = rays.shape[0]
     dev = rays.device
     Sc, Nf = int(opts.N_samples_c), int(opts.N_samples_f)
@@ -165,15 +167,37 @@ def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, 
     else:
         u = None
     net, blob_c, blob_f = packed.kernel_blobs(prec)
-    rgb_c, disp_c, rgb_f, disp_f, ws = ops.render_rays(net, blob_c, blob_f if Nf > 0 else None, cfg, rays, t_rand, u)
+    stats = None
+    if occupancy is None:
+        rgb_c, disp_c, rgb_f, disp_f, ws = ops.render_rays(net, blob_c, blob_f if Nf > 0 else None, cfg, rays, t_rand, u)
+        views = ops.workspace_views
+    else:
+        rgb_c, disp_c, rgb_f, disp_f, ws, stats = occ.render_rays(net, blob_c, blob_f if Nf > 0 else None, cfg, occupancy, rays, t_rand, u)
+        occupancy.last_stats = occ.add_stats(occupancy.last_stats, stats)
+        views = occ.workspace_views
     out = {"rgb_c": rgb_c, "disp_c": disp_c}                        # nerf_process.py:215-216
     if Nf > 0:
         out["rgb_f"], out["disp_f"] = rgb_f, disp_f
     if intermediates:
-        for k, v in ops.workspace_views(cfg, n, ws).items():
+        for k, v in views(cfg, n, ws).items():
             out["_" + k] = v
         out["_t_rand"], out["_u"] = t_rand, u
+        if stats is not None:
+            out["_occ_stats"] = stats
     return out
+
+
+def _occupancy_arg(occupancy, training: bool, prec: ops.Precision):
+    """``occupancy=``: None (today's path), or an OccupancyGrid -- inference only, one kernel family (fp32 / f16s / bf16) for both networks."""
+    if occupancy is None:
+        return None
+    if training:
+        raise MiNerfError("occupancy= is an inference feature: training with a grid is not supported (call under torch.no_grad(), or freeze the model)")
+    if not isinstance(occupancy, occ.OccupancyGrid):
+        raise MiNerfError(f"occupancy must be an occupancy.OccupancyGrid, got {type(occupancy).__name__}")
+    occ.check_precision(prec)
+    occupancy.last_stats = None
+    return occupancy
 
 
 def _train_f16s(prec: ops.Precision, intermediates: bool = False) -> bool:
@@ -184,11 +208,14 @@ def _train_f16s(prec: ops.Precision, intermediates: bool = False) -> bool:
 
 
 def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ray_offset: int = 0, bf16: bool = False,
-                return_intermediates: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False):
+                return_intermediates: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False,
+                occupancy=None):
     """Coarse pass -> composite -> resample -> fine pass (nerf_process.py:185-216) as one fused launch
     sequence.  Returns ``{'rgb_c','disp_c'[,'rgb_f','disp_f']}``.  ``bf16`` / ``f16s`` / ``coarse_f16s`` / ``f16`` / ``coarse_f16`` select
-    the networks' precision mode (ops.precision(); fp32 MFMA by default).  With gradients: fp32 or f16s."""
+    the networks' precision mode (ops.precision(); fp32 MFMA by default).  With gradients: fp32 or f16s.  ``occupancy``: an OccupancyGrid
+    (occupancy.py) -- the networks skip the samples it marks empty; ``return_intermediates`` then also returns ``_occ_stats``."""
     prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
+    occupancy = _occupancy_arg(occupancy, train_path.wants_grad(model), prec)
     if train_path.wants_grad(model):
         train_f16s = _train_f16s(prec, return_intermediates)
         if rays.dim() != 2 or rays.shape[1] != 6:
@@ -198,20 +225,24 @@ def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ra
     rays = as_f32_dev(rays, packed.device)
     if rays.dim() != 2 or rays.shape[1] != 6:
         raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
-    return _render(rays, packed, opts, t_rand, u, _next_seed(seed), int(ray_offset), prec, return_intermediates)
+    if occupancy is not None and rays.shape[0] > occ.MAX_RAYS_PER_LAUNCH:
+        raise MiNerfError(f"render_rays with a grid takes at most {occ.MAX_RAYS_PER_LAUNCH} rays per call (batchify_rays_and_render_by_chunk slabs them)")
+    return _render(rays, packed, opts, t_rand, u, _next_seed(seed), int(ray_offset), prec, return_intermediates, occupancy)
 
 
 def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts, *, t_rand=None, u=None, seed=None,
                                       ray_offset: int = 0, bf16: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False,
-                                      coarse_f16: bool = False):
+                                      coarse_f16: bool = False, occupancy=None):
     """Drop-in entry point (nerf_process.py:220-252): flatten, optional NDC warp for llff, render.
     Returns ``(rgb_c [N,3], disp_c [N], rgb_f [N,3] | None, disp_f [N] | None)``.
 
     ``opts.chunk_rays`` bounded the reference's activation memory; the fused kernels keep activations in
     registers, so rays are launched in slabs of up to MAX_RAYS_PER_LAUNCH.  The result does not depend on
-    the slab size because the jitter is keyed on the global ray index (``ray_offset`` + position)."""
+    the slab size because the jitter is keyed on the global ray index (``ray_offset`` + position).
+    ``occupancy``: an OccupancyGrid (occupancy.py); its ``last_stats`` then holds the sample counts of this call."""
     prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
     training = train_path.wants_grad(model)
+    occupancy = _occupancy_arg(occupancy, training, prec)
     train_f16s = _train_f16s(prec) if training else False
     packed = None if training else packed_for(model)
     dev = next(model.parameters()).device if training else packed.device
@@ -228,7 +259,7 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
     seed = _next_seed(seed)
     Nf = int(opts.N_samples_f)
     parts = []
-    slab = train_path.MAX_TRAIN_RAYS if training else MAX_RAYS_PER_LAUNCH
+    slab = train_path.MAX_TRAIN_RAYS if training else (MAX_RAYS_PER_LAUNCH if occupancy is None else occ.MAX_RAYS_PER_LAUNCH)
     for i in range(0, N, slab):
         j = min(N, i + slab)
         tr, uu = (None if t_rand is None else t_rand[i:j]), (None if u is None else u[i:j])
@@ -236,7 +267,7 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
             parts.append(train_path.render_train(rays[i:j].contiguous(), model, opts, t_rand=tr, u=uu, seed=seed,
                                                  ray_offset=int(ray_offset) + i, f16s=train_f16s))
         else:
-            parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False))
+            parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False, occupancy))
     def cat(key):
         return parts[0][key] if len(parts) == 1 else torch.cat([p[key] for p in parts], dim=0)
     if Nf > 0:
