@@ -3,6 +3,10 @@ standing in for the dataset loaders (no dataset ships with either repository).  
 reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap the imports back and the same script drives the reference.
 
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
+                                             [--scene teacher|solid]
+
+``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
+mi_scene_render -- instead of views of a random network.
 """
 import argparse
 import os
@@ -14,7 +18,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from nerf_pytorch_paeng_amd import harness, synthetic                                          # noqa: E402
+from nerf_pytorch_paeng_amd import harness, scenes, synthetic                                  # noqa: E402
 from nerf_pytorch_paeng_amd.model import NeRF, get_positional_encoder                          # noqa: E402  (model/NeRF.py, model/PositionalEncoding.py)
 
 
@@ -27,6 +31,7 @@ def main(argv=None):
     ap.add_argument("--precision", default="fp32", choices=["fp32", "f16s"])
     ap.add_argument("--net-width", type=int, default=256)
     ap.add_argument("--render-views", type=int, default=8)
+    ap.add_argument("--scene", default="teacher", choices=["teacher", "solid"], help="teacher: views of a random network; solid: scenes.SolidScene.default()")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -40,10 +45,13 @@ def main(argv=None):
     posenc = get_positional_encoder(10), get_positional_encoder(4)                               # main.py:133
     poses = harness.get_render_pose(n_angle=a.views + 2, phi=-30.0, nf=4.0)                      # stand-in for load_blender's camera list
     # the "dataset": views of a fixed random NeRF rendered by the inference kernels (the teacher); the last two views are the test set
-    teacher = NeRF(8, 256, 63, 27).to(dev)
-    teacher.load_state_dict({k: torch.as_tensor(v) for k, v in synthetic.make_state_dict(77, 8, 256).items()})
-    with torch.no_grad():
-        images = torch.stack([harness._render_pose(teacher, posenc, K, poses[i].to(dev), (H, W), opts)[0].reshape(H, W, 3) for i in range(a.views + 2)], 0)
+    if a.scene == "solid":                                                                       # the same cameras, the analytic scene
+        images = scenes.SolidScene.default().render_views(poses, K, (H, W), opts.near, opts.far, 1024, dev)
+    else:
+        teacher = NeRF(8, 256, 63, 27).to(dev)
+        teacher.load_state_dict({k: torch.as_tensor(v) for k, v in synthetic.make_state_dict(77, 8, 256).items()})
+        with torch.no_grad():
+            images = torch.stack([harness._render_pose(teacher, posenc, K, poses[i].to(dev), (H, W), opts)[0].reshape(H, W, 3) for i in range(a.views + 2)], 0)
     i_train, i_test = list(range(a.views)), [a.views, a.views + 1]
 
     model = NeRF(8, a.net_width, 63, 27, skips=[4]).to(dev)                                      # main.py:67-73

@@ -1,4 +1,4 @@
-"""Build libmi_nerf.so, libmi_nerf_iqa.so and libmi_nerf_occ.so with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libmi_nerf.so, libmi_nerf_iqa.so, libmi_nerf_occ.so and libmi_nerf_scene.so with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m nerf_pytorch_paeng_amd.build [--force]          the shipped libraries (clean build: ~1 min 20 s on 8 cores)
     python -m nerf_pytorch_paeng_amd.build --variant TAG -DFOO -DBAR=1     an A/B variant (tools/ab_probe.py)
@@ -14,6 +14,8 @@ What lands where:
                                                     of its own; libmi_nerf.so's sources and stamp inputs do not know it.
   nerf_pytorch_paeng_amd/libmi_nerf_occ.so (+ .stamp)   occupancy-grid rendering (include/mi_nerf_occ.h, csrc/occ.hip): a third library with a stamp of its
                                                     own, linked against libmi_nerf.so (rpath $ORIGIN), whose public entries it calls.
+  nerf_pytorch_paeng_amd/libmi_nerf_scene.so (+ .stamp) procedural solid scenes (include/mi_nerf_scene.h, csrc/scene.hip): a fourth library with a stamp
+                                                    of its own; it includes no other header and links against no other library of the project.
   build_scratch/obj/                                objects of the shipped library (cache; tests/test_packing_cpu.py disassembles them)
   build_scratch/obj_TAG/, build_scratch/libmi_nerf_TAG.so    variants.  build_scratch/ is git-ignored AND gpurun-ignored: a variant is
                                                     built where it is used (tools/ab_probe.py builds the ones it is asked for on the box).
@@ -43,6 +45,10 @@ IQA_SOURCES = ["iqa.hip"]
 OCC_LIB = os.path.join(HERE, "libmi_nerf_occ.so")
 OCC_STAMP = OCC_LIB + ".stamp"
 OCC_SOURCES = ["occ.hip"]
+# libmi_nerf_scene.so: its own source and its own header, nothing else
+SCENE_LIB = os.path.join(HERE, "libmi_nerf_scene.so")
+SCENE_STAMP = SCENE_LIB + ".stamp"
+SCENE_SOURCES = ["scene.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          # the MLP kernel's register-resident design needs its k-loops FULLY unrolled (static register indices)
@@ -70,6 +76,10 @@ def _iqa_headers():
 
 def _occ_headers():
     return [os.path.join(INCLUDE, "mi_nerf_occ.h"), os.path.join(INCLUDE, "mi_nerf.h")]
+
+
+def _scene_headers():
+    return [os.path.join(INCLUDE, "mi_nerf_scene.h")]
 
 
 def _digest(paths, extra=()) -> str:
@@ -183,6 +193,26 @@ def build_occ_library(force: bool = False, verbose: bool = False) -> str:
     return OCC_LIB
 
 
+def scene_source_stamp() -> str:
+    return _digest([os.path.join(CSRC, s) for s in SCENE_SOURCES] + _scene_headers(), [FLAGS])
+
+
+def build_scene_library(force: bool = False, verbose: bool = False) -> str:
+    """libmi_nerf_scene.so, a no-op when its stamp matches (like build_library)."""
+    want = scene_source_stamp()
+    if not force and os.path.exists(SCENE_LIB) and os.path.exists(SCENE_STAMP) and open(SCENE_STAMP).read() == want:
+        if verbose:
+            print(f"up to date: {SCENE_LIB} ({os.path.getsize(SCENE_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+        return SCENE_LIB
+    objs = [_compile(s, force, headers=_scene_headers()) for s in SCENE_SOURCES]
+    _link(objs, SCENE_LIB)
+    with open(SCENE_STAMP, "w") as fh:
+        fh.write(want)
+    if verbose:
+        print(f"built {SCENE_LIB} ({os.path.getsize(SCENE_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+    return SCENE_LIB
+
+
 def variant_path(tag: str) -> str:
     return os.path.join(SCRATCH, f"libmi_nerf_{tag}.so")
 
@@ -229,3 +259,4 @@ if __name__ == "__main__":
         print(build_library(force="--force" in sys.argv, verbose=True))
         print(build_iqa_library(force="--force" in sys.argv, verbose=True))
         print(build_occ_library(force="--force" in sys.argv, verbose=True))
+        print(build_scene_library(force="--force" in sys.argv, verbose=True))
