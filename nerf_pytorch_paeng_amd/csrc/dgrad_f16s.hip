@@ -93,7 +93,7 @@ void dgrad_f16s_kernel(const DArgs a) {
     asm volatile("" ::: "a255");
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");       // FP16_OVFL: a conversion beyond the f16 range saturates
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* cw = (float*)(smem + RING_BYTES_S);                 // colour head [3][W/2], then the density head [W], then a mask block per wave
+    float* cw = (float*)(smem + HRING_BYTES);                 // colour head [3][W/2], then the density head [W], then a mask block per wave
     float* dwl = cw + 3 * (W / 2);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -107,20 +107,12 @@ void dgrad_f16s_kernel(const DArgs a) {
     if (ex > 100) ex = 100;
     const float sc = __uint_as_float((unsigned)(127 + 7 - ex) << 23), inv_sc = __uint_as_float((unsigned)(127 - 7 + ex) << 23);
 
-    Ring ring;
-    ring.sbase = a.stream + wave * (DMA_PER_WAVE * QUAD_BYTES);
-    ring.voff = lane * 16;
-    ring.fetch_off = 0;
-    ring.stream_bytes = a.stream_bytes;
-    ring.lds_lo = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * (DMA_PER_WAVE * QUAD_BYTES);
-    ring.lds_hi = ring.lds_lo + RING_BYTES_S;
-    ring.fetch_lds = ring.lds_lo;
-    ring.read_slot = NSLOT_S - 1;
+    Ring ring = ring_start(a.stream, a.stream_bytes, smem, wave, lane);
 #pragma unroll
-    for (int i = 0; i < DMA_PER_WAVE; ++i) ring_dma(ring, i);
+    for (int i = 0; i < RING_DMAS; ++i) ring_dma(ring, i);
     ring_next_fetch(ring);
 #pragma unroll
-    for (int i = 0; i < DMA_PER_WAVE; ++i) ring_dma(ring, i);
+    for (int i = 0; i < RING_DMAS; ++i) ring_dma(ring, i);
     u32x4b aq[NBUF][2];
     ring_advance(ring);                                             // also publishes the head tables (barrier)
 #pragma unroll
@@ -137,7 +129,7 @@ void dgrad_f16s_kernel(const DArgs a) {
     const int sh4 = 4 * (q4 >> 1);                                  // this lane's nibble of a mask byte pair (see stash_tile)
     float dmax = 0.0f;                                              // largest scaled gradient this lane stored
     const char* mlds = (const char*)(dwl + W) + wave * (a.D * 1024);
-    const unsigned mlds_m0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + RING_BYTES_S + (3 * (W / 2) + W) * 4 + wave * (a.D * 1024);
+    const unsigned mlds_m0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + HRING_BYTES + (3 * (W / 2) + W) * 4 + wave * (a.D * 1024);
 
     for (unsigned it = 0; it < a.n_iter; ++it) {
         const unsigned n_tile = unit_of(it);
@@ -150,8 +142,8 @@ void dgrad_f16s_kernel(const DArgs a) {
         unsigned msh[NP][4];
         u32x4b bdh[NP][KG0], bdl[NP][KG0];
         // ---- this tile's ReLU' words, all layers: [D][64 lanes][16 bytes] straight into the wave's LDS block.  The ring's own DMAs are in mid
-        // slot here (five of the slot's eight issued: the A pipeline runs three pairs ahead), and they set M0 only at their first and fifth:
-        // M0 goes back to what the sixth expects.
+        // slot here (five of the slot's eight issued: the A pipeline runs three pairs ahead), and they set M0 only at their first and fifth
+        // (hring_dma, wstream_ring.h: this borrow depends on that schedule): M0 goes back to what the sixth expects.
         {
             const char* mg = (const char*)a.mask_h + ((size_t)tcur * 64 + lane) * 16;
             const size_t layer_bytes = (size_t)a.n_wtiles * 1024;
@@ -319,7 +311,7 @@ int dgrad_f16s(const mi_nerf_net* net, const void* packed_bwd_f16s_dev, const fl
     a.n_wtiles = (unsigned)n_wtiles;
     a.absmax_bits = absmax_dev;
     a.delta_absmax_bits = const_cast<unsigned*>(absmax_dev) + 1;    // second word of the same slot (zeroed with the first)
-    const size_t lds = RING_BYTES_S + (size_t)(3 * 128 + 256) * 4 + (size_t)4 * net->D * 1024;      // ring | heads | per wave: D layers of mask words
+    const size_t lds = HRING_BYTES + (size_t)(3 * 128 + 256) * 4 + (size_t)4 * net->D * 1024;      // ring | heads | per wave: D layers of mask words
     MN_CHECK_ARG(lds <= 160 * 1024, "the split-precision backward-data kernel keeps a tile's ReLU' words of all layers in LDS: D = %d does not fit (D <= 15)", net->D);
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)dgrad_f16s_kernel)) return rc;

@@ -28,7 +28,7 @@ struct HalfLayout {
     uint32_t bias_trunk, bias_feat, bias_d, head_b, wdir_t, total_bytes;      // side-table sub-offsets in floats from side start
     // The stream's length as the ring of mlp_half_core.h walks it: TAIL_QUADS tail positions of this stream's size.  The blob's own stream
     // for QUADS; for PAIRS (the f16 kernel on the split-precision blob) TAIL_QUADS - TAIL_PAIRS positions more than the blob holds -- the
-    // last slot re-reads data it never uses instead (bring_next_fetch).
+    // last slot re-reads data it never uses instead (hring_next_fetch).
     uint32_t walk_bytes;
 };
 inline HalfLayout make_half_layout(int D, int W, int skip, HalfStream kind) {

@@ -110,6 +110,30 @@ __device__ __forceinline__ f32x4 ring_read(const char* smem, const WRing& r, int
     return *(const f32x4*)(smem + r.read_slot * SLOT_BYTES + lane * 16 + qs * QUAD_BYTES);
 }
 
+// Start-up: a wave's view of the ring at the head of `stream` (smem: the ring's LDS), then slots 0..2 in bursts; from the first
+// ring_advance on (the caller's: its barrier also publishes the caller's LDS tables) slot p+3 streams in, one DMA per group, while slot p
+// is consumed.
+__device__ __forceinline__ WRing ring_start(const char* stream, unsigned stream_bytes, const char* smem, int wave, int lane) {
+    WRing r;
+    r.sbase = stream + wave * (4 * QUAD_BYTES);
+    r.voff = lane * 16;
+    r.fetch_off = 0;
+    r.stream_bytes = stream_bytes;
+    r.lds_lo = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)smem + wave * (4 * QUAD_BYTES);
+    r.lds_hi = r.lds_lo + RING_BYTES;
+    r.fetch_lds = r.lds_lo;
+    r.read_slot = NSLOT - 1;            // the first ring_advance moves to slot 0
+#ifdef MN_DIAG
+    r.dlog = nullptr; r.dcnt = 0;
+#endif
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+        if (sl) ring_next_fetch(r);
+        ring_dma<0>(r); ring_dma<1>(r); ring_dma<2>(r); ring_dma<3>(r);
+    }
+    return r;
+}
+
 // ---------------------------------------------------------------------------------------------
 // one GEMM part: acc[0..NT) += A(stream) x B, B = KS per-lane registers b[0..KS).
 // `a` is the A-operand pipeline: on entry it holds this part's quads (kq=0, t<NT), already read from

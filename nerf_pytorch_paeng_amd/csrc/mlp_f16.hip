@@ -9,7 +9,7 @@
 //   * WEIGHTS from the split-precision blob (mi_nerf_pack_weights_f16s / mi_nerf_pack_apply_f16s / PackedNeRF.f16s()), hi halves only:
 //     that stream is the bf16 stream's quad order with each 1 KiB quad replaced by a (hi, lo) pair, so a stream position is 2 KiB of the
 //     blob and the DMA reads every other quad (the same bytes per pass as bf16).  Its tail is 208 pairs where bf16 has 224 quads: the
-//     ring walks 224 positions and, in the last slot, re-reads data it never uses instead of running past the blob (bring_next_fetch).
+//     ring walks 224 positions and, in the last slot, re-reads data it never uses instead of running past the blob (hring_next_fetch).
 //     No packer of its own: the f16s packers' weight check (|w| < 65 504, not NaN; the device packer's out-of-range count) applies.
 //   * ACTIVATIONS packed by v_cvt_pk_f16_f32 (round to nearest even), then v_pk_fma_f16 h * 0 + h -- +-inf (an activation at or beyond
 //     65 520) becomes NaN, a finite h stays h -- and the ReLU as v_pk_maximum3_f16, NaN-propagating.  (bf16's v_pk_max_i16 would turn a
@@ -28,8 +28,8 @@
 namespace minerf {
 
 // Both layouts share their stream positions, tail body and gamma(x) k-steps by construction (half_layout.h); what is left to hold is the
-// ring's side of it: the split-precision tail is half a slot of padding short of the 224 positions the ring walks (bring_next_fetch).
-static_assert(TAIL_QUADS - TAIL_PAIRS == BSLOT_QUADS / 2, "the f16 kernel walks the split-precision blob's stream as the bf16 stream");
+// ring's side of it: the split-precision tail is half a slot of padding short of the 224 positions the ring walks (hring_next_fetch).
+static_assert(TAIL_QUADS - TAIL_PAIRS == HSLOT_QUADS / 2, "the f16 kernel walks the split-precision blob's stream as the bf16 stream");
 
 int mlp_rays_f16(const mi_nerf_net* net, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays, int S,
                  float* raw_dev, hipStream_t st, int points_per_wave, const StratDraw* strat, FineDraw* fine) {

@@ -1,22 +1,18 @@
 // mlp_f16s_core.h -- the split-precision machinery shared by the translation units of that variant (mlp_f16s.hip: the
 // inference launch; mlp_f16s_stash.hip: the training forward; dgrad_f16s.hip: the backward-data chain): constants, the weight
-// ring, the fragment file, MFMA wrappers, packing schedule, job(), and the forward kernel template.  See mlp_f16s.hip for the design.
+// ring's aliases, the fragment file, packing schedule, job(), and the forward kernel template.  See mlp_f16s.hip for the design.
 #pragma once
-#include <type_traits>
-#include "half_layout.h"
+#include "wstream_ring.h"
 
 // where the next unit's inputs are requested in the view-direction layer (job, k-step): behind a ring advance (pair 161 of the tail = slot 10, quad 2)
 namespace minerf {
 namespace f16s {
 constexpr int PF_T = 3, PF_KS = 1;
 
-typedef unsigned u32x4b __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2b __attribute__((ext_vector_type(2)));
 
 constexpr int NP = 2;                                      // point tiles (16 points each) per wave
 constexpr int NBUF = 4, LA = NBUF - 1;                     // A-operand pipeline: quad PAIRS in flight (a body's pair count and the tail's padding jump are multiples of 4)
-constexpr int SLOT_QUADS_S = 32, SLOT_BYTES_S = SLOT_QUADS_S * QUAD_BYTES, NSLOT_S = 3, RING_BYTES_S = NSLOT_S * SLOT_BYTES_S;
-constexpr int DMA_PER_WAVE = SLOT_QUADS_S / 4;
 constexpr int KPE = enc_ksteps32(KERNEL_LX), KH = 8, NT = 16;      // k-steps over gamma(x) (63 -> 64 channels), over a 256-wide activation; output tiles of a 256-wide layer
 constexpr float SC_DN = 1.0f / SPLIT_SCALE, SC_UP = SPLIT_SCALE;   // 2^-11, 2^11
 // (MT = 16, KF = 32 and the tail -- TAIL_USED of TAIL_PAIRS quad PAIRS carry weights -- are the bf16 stream's: half_layout.h)
@@ -45,80 +41,23 @@ struct Args {
     long long stash_rows;       // P
 };
 
-struct Ring {
-    const char* sbase;      // stream + wave's 8 KiB share
-    unsigned voff;          // lane*16
-    unsigned fetch_off, stream_bytes;
-    unsigned fetch_lds, lds_lo, lds_hi;
-    unsigned read_slot;
-};
-// LDS-DMA of the weight stream (see mlp_bf16.hip): M0 is ours alone in this kernel
-__device__ __forceinline__ void set_m0(unsigned lds_in) {
-    const unsigned lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(lds_addr) : "memory");
+// The weight ring is wstream_ring.h's, four waves per workgroup over a stream of 1 KiB quads read in order (hi and lo quads alternate: a
+// quad PAIR is two ring positions).  M0 is the ring's alone in these kernels but for dgrad_f16s.hip's mask DMAs (see there).
+using Ring = HRing;
+__device__ __forceinline__ Ring ring_start(const char* stream, unsigned stream_bytes, const char* smem, int wave, int lane) {
+    return hring_start<4, false>(stream, stream_bytes, smem, wave, lane);
 }
-template <int IMM>
-__device__ __forceinline__ void dma16(const char* gaddr_lane) {
-    asm volatile("global_load_lds_dwordx4 %0, off offset:%1" ::"v"(gaddr_lane), "i"(IMM) : "memory");
-}
-__device__ __forceinline__ void ring_dma(const Ring& r, int i) {
-    const char* g = r.sbase + r.fetch_off + r.voff + (i >= 4 ? 4096 : 0);
-    if (i == 0) set_m0(r.fetch_lds);
-    if (i == 4) set_m0(r.fetch_lds + 4096);
-    if ((i & 3) == 0) dma16<0>(g);
-    else if ((i & 3) == 1) dma16<1024>(g);
-    else if ((i & 3) == 2) dma16<2048>(g);
-    else dma16<3072>(g);
-}
-__device__ __forceinline__ void ring_next_fetch(Ring& r) {
-    r.fetch_off += SLOT_BYTES_S;
-    if (r.fetch_off >= r.stream_bytes) r.fetch_off = 0;
-    r.fetch_lds += SLOT_BYTES_S;
-    if (r.fetch_lds >= r.lds_hi) r.fetch_lds = r.lds_lo;
-}
-__device__ __forceinline__ void ring_advance(Ring& r) {
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    __syncthreads();
-    ring_next_fetch(r);
-    r.read_slot = (r.read_slot + 1 == NSLOT_S) ? 0 : r.read_slot + 1;
-}
-// quad at slot position qs; positions 1..8 also issue one of the slot's DMAs (never a burst)
-__device__ __forceinline__ u32x4b ring_read(const char* smem, const Ring& r, int lane, int qs) {
-    if (qs >= 1 && qs <= DMA_PER_WAVE) ring_dma(r, qs - 1);
-    return *(const u32x4b*)(smem + r.read_slot * SLOT_BYTES_S + lane * 16 + qs * QUAD_BYTES);
-}
+constexpr int RING_DMAS = hring_dmas(4);
+__device__ __forceinline__ void ring_dma(const Ring& r, int i) { hring_dma<4, false>(r, i); }
+__device__ __forceinline__ void ring_next_fetch(Ring& r) { hring_next_fetch<false>(r); }
+__device__ __forceinline__ void ring_advance(Ring& r) { hring_advance<4, false>(r); }
+__device__ __forceinline__ u32x4b ring_read(const char* smem, const Ring& r, int lane, int qs) { return hring_read<4, false>(smem, r, lane, qs); }
 
-template <int I> using IC = std::integral_constant<int, I>;
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) { f(IC<B>{}); static_for<B + 1, E>(f); }
-}
 // THE FRAGMENT FILE (all 256 AGPRs, hand-numbered; see mlp_bf16.hip): set, point tile, fragment, part (0 hi, 1 lo)
 __host__ __device__ constexpr int frag_reg(int set, int p, int f, int part) { return ((((set * NP + p) * 8 + f) * 2) + part) * 4; }
 __host__ __device__ constexpr int tile_reg(int set, int p, int t, int part) { return frag_reg(set, p, t >> 1, part) + 2 * (t & 1); }
 
-// MFMAs as asm statements (hipcc allocates only the VGPR side).  B operand: a fragment-file register (IC<R>) or a VGPR fragment.
-template <int R>
-__device__ __forceinline__ void mfma_c(f32x4& acc, const u32x4b& afrag, IC<R>, const f32x4& c) {          // acc = A B + c
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, a[%3:%4], %2" : "=&v"(acc) : "v"(afrag), "v"(c), "n"(R), "n"(R + 3));
-}
-__device__ __forceinline__ void mfma_c(f32x4& acc, const u32x4b& afrag, const u32x4b& bfrag, const f32x4& c) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(acc) : "v"(afrag), "v"(bfrag), "v"(c));
-}
-template <int R>
-__device__ __forceinline__ void mfma_z(f32x4& acc, const u32x4b& afrag, IC<R>) {                          // acc = A B
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, a[%2:%3], 0" : "=&v"(acc) : "v"(afrag), "n"(R), "n"(R + 3));
-}
-__device__ __forceinline__ void mfma_z(f32x4& acc, const u32x4b& afrag, const u32x4b& bfrag) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(afrag), "v"(bfrag));
-}
-template <int R>
-__device__ __forceinline__ void mfma_a(f32x4& acc, const u32x4b& afrag, IC<R>) {                          // acc += A B
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, a[%2:%3], %0" : "+v"(acc) : "v"(afrag), "n"(R), "n"(R + 3));
-}
-__device__ __forceinline__ void mfma_a(f32x4& acc, const u32x4b& afrag, const u32x4b& bfrag) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(afrag), "v"(bfrag));
-}
+// (the MFMAs: wstream_ring.h's asm wrappers with F16 = true -- mfma_first: acc = A B + c, mfma_zero: acc = A B, mfma_acc: acc += A B)
 
 // ---- packing: a pair of accumulator elements (registers 2e, 2e+1 of a finished tile) -> one dword of the hi fragment, one of the lo
 // fragment.  Six stages of two instructions (one stage per MFMA gap), or as one block where a job has more work than gaps.
@@ -230,15 +169,15 @@ __device__ __forceinline__ void job(f32x4 (&ah)[NP], f32x4 (&al)[NP], CSel csel,
         static_for<0, 6>([&](auto s_c) __attribute__((always_inline)) {
             constexpr int sub = decltype(s_c)::value, p = sub & 1;
             if constexpr (sub < 2) {
-                if constexpr (ks == 0) mfma_c(ah[p], a[cur][0], bh(IC<p>{}, ks_c), csel(p));
-                else mfma_a(ah[p], a[cur][0], bh(IC<p>{}, ks_c));
-                if constexpr (sub == 0 && (2 * qn) % SLOT_QUADS_S == 0) ring_advance(ring);
-                a[q0 % NBUF][sub] = ring_read(smem, ring, lane, (2 * qn + sub) % SLOT_QUADS_S);
+                if constexpr (ks == 0) mfma_first<true>(ah[p], a[cur][0], bh(IC<p>{}, ks_c), csel(p));
+                else mfma_acc<true>(ah[p], a[cur][0], bh(IC<p>{}, ks_c));
+                if constexpr (sub == 0 && (2 * qn) % HSLOT_QUADS == 0) ring_advance(ring);
+                a[q0 % NBUF][sub] = ring_read(smem, ring, lane, (2 * qn + sub) % HSLOT_QUADS);
             } else if constexpr (sub < 4) {
-                if constexpr (ks == 0) mfma_z(al[p], a[cur][0], bl(IC<p>{}, ks_c));
-                else mfma_a(al[p], a[cur][0], bl(IC<p>{}, ks_c));
+                if constexpr (ks == 0) mfma_zero<true>(al[p], a[cur][0], bl(IC<p>{}, ks_c));
+                else mfma_acc<true>(al[p], a[cur][0], bl(IC<p>{}, ks_c));
             } else {
-                mfma_a(al[p], a[cur][1], bh(IC<p>{}, ks_c));
+                mfma_acc<true>(al[p], a[cur][1], bh(IC<p>{}, ks_c));
             }
             hook(ks_c, s_c);
             asm volatile("" ::: "memory");
@@ -256,7 +195,7 @@ void mlp_f16s_kernel(const Args a) {
     constexpr int BIG = 1 << 30;
     asm volatile("" ::: "a255");                             // reserve the whole accumulation-register file
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* side = (float*)(smem + RING_BYTES_S);
+    float* side = (float*)(smem + HRING_BYTES);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, q4 = lane >> 4, pq = q4 & 1;  // lane quarters 2, 3 duplicate the encoding work of 0, 1
@@ -266,20 +205,12 @@ void mlp_f16s_kernel(const Args a) {
     char* pe_wave = (char*)(side + a.side_floats + 4 * (W / 2)) + wave * (2 * NP * KPE * QUAD_BYTES);   // parked gamma(x) fragments [part][p][ks]
     char* pe_lds = pe_wave + lane * 16;
 
-    Ring ring;
-    ring.sbase = a.stream + wave * (DMA_PER_WAVE * QUAD_BYTES);
-    ring.voff = lane * 16;
-    ring.fetch_off = 0;
-    ring.stream_bytes = a.stream_bytes;
-    ring.lds_lo = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * (DMA_PER_WAVE * QUAD_BYTES);
-    ring.lds_hi = ring.lds_lo + RING_BYTES_S;
-    ring.fetch_lds = ring.lds_lo;
-    ring.read_slot = NSLOT_S - 1;
+    Ring ring = ring_start(a.stream, a.stream_bytes, smem, wave, lane);
 #pragma unroll
-    for (int i = 0; i < DMA_PER_WAVE; ++i) ring_dma(ring, i);       // slot 0
+    for (int i = 0; i < RING_DMAS; ++i) ring_dma(ring, i);       // slot 0
     ring_next_fetch(ring);
 #pragma unroll
-    for (int i = 0; i < DMA_PER_WAVE; ++i) ring_dma(ring, i);       // slot 1; slot p+2 streams in while slot p is consumed
+    for (int i = 0; i < RING_DMAS; ++i) ring_dma(ring, i);       // slot 1; slot p+2 streams in while slot p is consumed
     u32x4b aq[NBUF][2];
     ring_advance(ring);                                             // also publishes the side tables (barrier)
 #pragma unroll
@@ -661,7 +592,7 @@ static int launch_f16s(const mi_nerf_net* net, const void* packed_dev, const flo
     a.skip_layer = (net->skip >= 0 && net->skip + 1 < net->D) ? net->skip + 1 : -1;
     a.stream_bytes = L.stream_bytes; a.side_floats = L.side_floats;
     a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d; a.o_head_b = L.head_b; a.o_wdir_t = L.wdir_t;
-    const size_t lds = RING_BYTES_S + (size_t)a.side_floats * 4 + 4 * (256 / 2) * 4 + (size_t)4 * 2 * NP * KPE * QUAD_BYTES;
+    const size_t lds = HRING_BYTES + (size_t)a.side_floats * 4 + 4 * (256 / 2) * 4 + (size_t)4 * 2 * NP * KPE * QUAD_BYTES;
     MN_CHECK_ARG(lds <= 160 * 1024, "LDS budget exceeded: %zu bytes", lds);
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)mlp_f16s_kernel<STASH>)) return rc;

@@ -159,20 +159,7 @@ void mlp_fp32_wide_kernel(const WideArgs a) {
     for (unsigned i = tid * 4; i < a.side_floats; i += 256 * 4) *(f32x4*)(side + i) = *(const f32x4*)(a.side + i);
     if ((long long)blockIdx.x >= ((a.n_wtiles + 3) >> 2)) return;     // host never launches such a block
 
-    WRing ring;
-    ring.sbase = a.stream + wave * (4 * QUAD_BYTES);
-    ring.voff = lane * 16;
-    ring.fetch_off = 0;
-    ring.stream_bytes = a.stream_bytes;
-    ring.lds_lo = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * (4 * QUAD_BYTES);
-    ring.lds_hi = ring.lds_lo + RING_BYTES;
-    ring.fetch_lds = ring.lds_lo;
-    ring.read_slot = NSLOT - 1;
-#pragma unroll
-    for (int sl = 0; sl < 3; ++sl) {
-        if (sl) ring_next_fetch(ring);
-        ring_dma<0>(ring); ring_dma<1>(ring); ring_dma<2>(ring); ring_dma<3>(ring);
-    }
+    WRing ring = ring_start(a.stream, a.stream_bytes, smem, wave, lane);
 
     f32x4 acc[32];
     f32x4 aq[8];

@@ -1,10 +1,9 @@
 // mlp_half_core.h -- the one-MFMA-per-product kernel shared by the bf16 (mlp_bf16.hip) and f16 (mlp_f16.hip) variants: constants, the
-// weight ring, the fragment file, MFMA wrappers, packing schedule, job(), the forward kernel body, its launcher and launch plan.  The
-// element type is a template parameter (F16) decided with `if constexpr`; see mlp_bf16.hip for the design and mlp_f16.hip for what the
-// f16 instantiation changes.
+// fragment file, packing schedule, job(), the forward kernel body, its launcher and launch plan (the weight ring and the MFMA wrappers:
+// wstream_ring.h).  The element type is a template parameter (F16) decided with `if constexpr`; see mlp_bf16.hip for the design and
+// mlp_f16.hip for what the f16 instantiation changes.
 #pragma once
-#include <type_traits>
-#include "half_layout.h"
+#include "wstream_ring.h"
 #include "stage_dev.h"
 
 namespace minerf {
@@ -12,19 +11,13 @@ namespace minerf {
 // where the next unit's inputs are requested in the view-direction layer: (job, k-step)
 constexpr int BF16_PF_T = 3, BF16_PF_KS = 2;
 
-typedef unsigned u32x4b __attribute__((ext_vector_type(4)));
-
 // Point tiles (16 points each) per wave: 4 in the standard shape (64 points per wave, 256 per workgroup and pass of the weight
 // stream), 2 in the SMALL-LAUNCH shape (32 / 128): twice the LDS reads and weight stream per FLOP, chosen by the launcher only
 // where the 64-point shape would leave SIMDs idle (a 512-ray shard of BASELINE config #5's 8-GPU split: 128 + 384 workgroup
 // passes on 256 CUs become 256 + 768 half-size ones).  NP is a template parameter of everything below.
 // (MT = 16 output features per job, KF = 32 k per MFMA, the tail's TAIL_USED of TAIL_QUADS positions and enc_ksteps32: half_layout.h)
 constexpr int DA = 4;                                      // A-operand pipeline depth (fragments in flight)
-constexpr int BSLOT_QUADS = 32;
-constexpr int BSLOT_BYTES = BSLOT_QUADS * QUAD_BYTES;      // 32 KiB
-constexpr int BNSLOT = 3;
-constexpr int BRING_BYTES = BNSLOT * BSLOT_BYTES;
-__host__ __device__ constexpr int bdma_of(int nwv) { return BSLOT_QUADS / nwv; }      // DMAs per wave per slot (NWV waves per workgroup)
+// (the ring: HSLOT_QUADS = 32 quads per slot, HNSLOT = 3 slots, hring_dmas(NWV) DMAs per wave and slot: wstream_ring.h)
 
 // ---------------------------------------------------------------------------------------------
 // device
@@ -70,81 +63,8 @@ __device__ __forceinline__ unsigned long long bstamp() {
 #define BSTAMP(i) do {} while (0)
 #endif
 
-struct BRing {
-    const char* sbase;      // stream + wave's 8 KiB share (f16: 16 KiB of the f16s blob's stream)
-    unsigned voff;          // lane*16
-    unsigned fetch_off, stream_bytes;
-    unsigned fetch_lds, lds_lo, lds_hi;
-    unsigned read_slot;
-    unsigned fetch_src, src_lim;    // f16 only: where this wave's share of the slot being fetched is read (see bring_next_fetch)
-};
-
-// ELEMENT TYPE.  Every template below takes `bool F16`: false = bf16 operands (mlp_bf16.hip, v_mfma_f32_16x16x32_bf16, a bf16 stream of
-// 1 KiB quads), true = f16 operands (mlp_f16.hip, v_mfma_f32_16x16x32_f16) read from the split-precision blob (mlp_f16s.hip), whose
-// stream is the bf16 stream's quad order with every quad replaced by a (hi, lo) PAIR: the f16 kernel reads the hi quads only, so a stream
-// position is 2 KiB of the blob instead of 1 KiB (the same bytes per pass of the ring), and the blob's tail is 208 pairs where the bf16
-// stream has 224 quads -- the 16 quads of padding at the end of the last slot are not in the blob (see bring_next_fetch).
-
-// LDS-DMA of the weight stream.  One global_load_lds_dwordx4 moves 64 lanes x 16 B = one 1 KiB quad: global address = per-lane
-// VGPR pair + instruction offset, LDS destination = M0 + instruction offset + lane * 16.  M0 is written twice per slot (each
-// wave's 8 KiB share = two 4 KiB halves, the 13-bit offset reaches 4 KiB) and is NOT saved / restored around each DMA: nothing
-// else in this kernel touches M0 (hipcc uses it only for LDS-direct / GWS / sendmsg / movrel instructions, none of which occur
-// here; tests/test_packing_cpu.py disassembles the object and checks that every M0 write is ours).
-__device__ __forceinline__ void bdma_set_m0(unsigned lds_in) {
-    const unsigned lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_in);      // wave-uniform by construction; pin to an SGPR
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(lds_addr) : "memory");
-}
-template <int IMM>
-__device__ __forceinline__ void bdma16(const char* gaddr_lane) {
-    asm volatile("global_load_lds_dwordx4 %0, off offset:%1" ::"v"(gaddr_lane), "i"(IMM) : "memory");
-}
-// DMA number i (0 .. BSLOT_QUADS / NWV - 1) of the slot being fetched: a wave's share of a slot is 8 KiB (4 waves per workgroup: two
-// 4 KiB halves, M0 set twice) or 4 KiB (8 waves)
-// f16: the instruction offset moves the LDS destination by 1 KiB per quad and the global address by the same 1 KiB, so the per-lane
-// address carries the other half of the 2 KiB blob stride: quad i of the share is read at 2 KiB * i.  (Mirror: tests/test_f16_mode_cpu.py.)
-template <int NWV, bool F16>
-__device__ __forceinline__ void bring_dma(const BRing& r, int i) {
-    const char* g;
-    if constexpr (F16) g = r.sbase + r.fetch_src + r.voff + (i & 3) * 1024 + (i >= 4 ? 8192 : 0);
-    else g = r.sbase + r.fetch_off + r.voff + (i >= 4 ? 4096 : 0);
-    if (i == 0) bdma_set_m0(r.fetch_lds);
-    if (i == 4) bdma_set_m0(r.fetch_lds + 4096);
-    if ((i & 3) == 0) bdma16<0>(g);
-    else if ((i & 3) == 1) bdma16<1024>(g);
-    else if ((i & 3) == 2) bdma16<2048>(g);
-    else bdma16<3072>(g);
-}
-// f16: stream_bytes is the stream as the kernel walks it (body + 224 positions of 2 KiB); the blob ends 16 positions (32 KiB) earlier.  In
-// the last slot the shares of waves 2 and 3 are that padding -- never read from LDS -- and re-read the 32 KiB in front of it instead of
-// running past the blob (src_lim: the largest fetch_off whose share is inside the blob).
-// MIRRORED in numpy by tests/test_f16_mode_cpu.py _ring_reads (with bring_dma's f16 address and the src_lim set-up in mlp_half_body):
-// that test checks the f16 addressing against the blobs, so a change to any of the three must be made there too.
-template <bool F16>
-__device__ __forceinline__ void bring_next_fetch(BRing& r) {
-    r.fetch_off += F16 ? 2 * BSLOT_BYTES : BSLOT_BYTES;
-    if (r.fetch_off >= r.stream_bytes) r.fetch_off = 0;
-    if constexpr (F16) r.fetch_src = r.fetch_off > r.src_lim ? r.fetch_off - BSLOT_BYTES : r.fetch_off;
-    r.fetch_lds += BSLOT_BYTES;
-    if (r.fetch_lds >= r.lds_hi) r.fetch_lds = r.lds_lo;
-}
-// consume the next slot: everything but the DMAs issued during the phase that ends here has landed (slot p+1 was
-// issued two phases ago); barrier; slot p+2 streams into ring[(p+2)%3] == ring[(p-1)%3] during the new phase.
-// Other vector-memory operations of the wave (input prefetches, result stores) share the counter and retire in order:
-// they can only make this wait stricter.
-template <int NWV, bool F16>
-__device__ __forceinline__ void bring_advance(BRing& r) {
-    if constexpr (NWV == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    __syncthreads();
-    bring_next_fetch<F16>(r);
-    r.read_slot = (r.read_slot + 1 == BNSLOT) ? 0 : r.read_slot + 1;
-}
-// fragment at slot position qs; positions 1 .. BSLOT_QUADS / NWV also issue one of the slot's DMAs (never a burst)
-template <int NWV, bool F16>
-__device__ __forceinline__ u32x4b bring_read(const char* smem, const BRing& r, int lane, int qs) {
-    if (qs >= 1 && qs <= bdma_of(NWV)) bring_dma<NWV, F16>(r, qs - 1);
-    return *(const u32x4b*)(smem + r.read_slot * BSLOT_BYTES + lane * 16 + qs * QUAD_BYTES);
-}
+// ELEMENT TYPE.  Every template below takes `bool F16`: false = bf16 operands (mlp_bf16.hip), true = f16 operands (mlp_f16.hip) read from
+// the split-precision blob; what that means for the weight stream is written at the ring (wstream_ring.h).
 
 // two floats -> one dword of a B fragment (round to nearest even).  Pinned where it is written.
 // f16: a value at or beyond 65520 converts to +-inf; h * 0 + h turns that into NaN (finite h: h exactly) before anything can clamp it
@@ -180,34 +100,8 @@ __device__ __forceinline__ unsigned pack2(float lo, float hi) {
 //   * the C operand of a job's first MFMAs is kept allocated until the next group (the matrix pipe reads it after issue);
 //   * VGPR operands (A fragments, biases, gamma(x)) come from LDS reads the compiler tracks (s_waitcnt before the asm).
 // ---------------------------------------------------------------------------------------------
-template <int I> using IC = std::integral_constant<int, I>;
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) { f(IC<B>{}); static_for<B + 1, E>(f); }
-}
+// (the MFMA wrappers themselves -- mfma_first<F16>: a job's first MFMA, C operand = the bias; mfma_acc<F16>: accumulate -- are wstream_ring.h's)
 __host__ __device__ constexpr int frag_reg(int np, int set, int p, int f) { return ((set * np + p) * 8 + f) * 4; }
-
-// first MFMA of a job (C operand = bias) / accumulate; B operand from the fragment file (IC<R>) or from a VGPR fragment
-template <bool F16, int R>
-__device__ __forceinline__ void mfma_first(f32x4& acc, const u32x4b& afrag, IC<R>, const f32x4& c) {
-    if constexpr (F16) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, a[%3:%4], %2" : "=&v"(acc) : "v"(afrag), "v"(c), "n"(R), "n"(R + 3));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, a[%3:%4], %2" : "=&v"(acc) : "v"(afrag), "v"(c), "n"(R), "n"(R + 3));
-}
-template <bool F16>
-__device__ __forceinline__ void mfma_first(f32x4& acc, const u32x4b& afrag, const u32x4b& bfrag, const f32x4& c) {
-    if constexpr (F16) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(acc) : "v"(afrag), "v"(bfrag), "v"(c));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(acc) : "v"(afrag), "v"(bfrag), "v"(c));
-}
-template <bool F16, int R>
-__device__ __forceinline__ void mfma_acc(f32x4& acc, const u32x4b& afrag, IC<R>) {
-    if constexpr (F16) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, a[%2:%3], %0" : "+v"(acc) : "v"(afrag), "n"(R), "n"(R + 3));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, a[%2:%3], %0" : "+v"(acc) : "v"(afrag), "n"(R), "n"(R + 3));
-}
-template <bool F16>
-__device__ __forceinline__ void mfma_acc(f32x4& acc, const u32x4b& afrag, const u32x4b& bfrag) {
-    if constexpr (F16) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(afrag), "v"(bfrag));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(afrag), "v"(bfrag));
-}
 
 // A finished 16x16 tile (4 accumulator registers per lane) -> two packed dwords -> registers R, R + 1 of the fragment file
 // (tile t of a layer is dwords 2(t&1), 2(t&1)+1 of fragment t>>1).  ReLU on the packed pair: as signed 16-bit integers every
@@ -267,7 +161,7 @@ __device__ __forceinline__ void pack_sched(const f32x4 (&prev)[NP], unsigned (&t
 // QEND/QPAD: stream positions >= QEND skip QPAD quads (the padding at the end of the tail body).
 // ---------------------------------------------------------------------------------------------
 template <bool F16, int NP, int NWV, int Q0, int KS, int QEND, int QPAD, typename CSel, typename BSrc, typename Hook>
-__device__ __forceinline__ void job(f32x4 (&acc)[NP], CSel csel, BSrc bsrc, u32x4b (&a)[DA], const char* smem, BRing& ring, int lane, Hook hook) {
+__device__ __forceinline__ void job(f32x4 (&acc)[NP], CSel csel, BSrc bsrc, u32x4b (&a)[DA], const char* smem, HRing& ring, int lane, Hook hook) {
     static_for<0, KS>([&](auto ks_c) __attribute__((always_inline)) {
         constexpr int ks = decltype(ks_c)::value;
         constexpr int q0 = Q0 + ks + DA - 1;                              // stream position being read into register q0 % DA
@@ -277,8 +171,8 @@ __device__ __forceinline__ void job(f32x4 (&acc)[NP], CSel csel, BSrc bsrc, u32x
             if constexpr (ks == 0) mfma_first<F16>(acc[p], a[(Q0 + ks) % DA], bsrc(p_c, ks_c), csel(p));
             else mfma_acc<F16>(acc[p], a[(Q0 + ks) % DA], bsrc(p_c, ks_c));
             if constexpr (p == 0) {
-                if constexpr (qn % BSLOT_QUADS == 0) bring_advance<NWV, F16>(ring);
-                a[q0 % DA] = bring_read<NWV, F16>(smem, ring, lane, qn % BSLOT_QUADS);
+                if constexpr (qn % HSLOT_QUADS == 0) hring_advance<NWV, F16>(ring);
+                a[q0 % DA] = hring_read<NWV, F16>(smem, ring, lane, qn % HSLOT_QUADS);
             }
             hook(ks_c, p_c);
             asm volatile("" ::: "memory");
@@ -301,7 +195,7 @@ __device__ __forceinline__ void job(f32x4 (&acc)[NP], CSel csel, BSrc bsrc, u32x
 // (one shape) or two (whole rounds of the 64-point shape, then the remainder as one round of the 32-point shape): the weight
 // ring and the A-fragment pipeline run on across the phase boundary (every unit ends at stream position 0).
 template <int W, int LX, int LD, int NP, int NWV, bool F16>
-__device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, char* smem, float* side, float* scr_base, char* pe_base, BRing& ring,
+__device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, char* smem, float* side, float* scr_base, char* pe_base, HRing& ring,
                                           u32x4b (&aq)[DA], const int lane, const int wave
 #ifdef MN_DIAG
                                           , unsigned long long (&seg)[8], unsigned long long& tprev
@@ -684,36 +578,24 @@ __device__ __forceinline__ void mlp_half_body(const MlpArgsB& a) {
     if constexpr (NWV == 4) asm volatile("" ::: "a255");
     else asm volatile("" ::: "a127");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* side = (float*)(smem + BRING_BYTES);
+    float* side = (float*)(smem + HRING_BYTES);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (unsigned i = tid * 4; i < a.side_floats; i += 64 * NWV * 4) *(f32x4*)(side + i) = *(const f32x4*)(a.side + i);
     float* scr_base = side + a.side_floats;
     char* pe_base = (char*)(scr_base + NWV * (NPM / 2) * (W / 2));
 
-    BRing ring;
-    ring.sbase = a.stream + wave * (bdma_of(NWV) * QUAD_BYTES * (F16 ? 2 : 1));
-    ring.voff = lane * 16;
-    ring.fetch_off = 0;
-    ring.stream_bytes = a.stream_bytes;
-    if constexpr (F16) {
-        ring.fetch_src = 0;
-        ring.src_lim = a.stream_bytes - BSLOT_BYTES - (unsigned)(wave + 1) * (bdma_of(NWV) * 2 * QUAD_BYTES);      // mirror: tests/test_f16_mode_cpu.py
-    }
-    ring.lds_lo = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * (bdma_of(NWV) * QUAD_BYTES);
-    ring.lds_hi = ring.lds_lo + BRING_BYTES;
-    ring.fetch_lds = ring.lds_lo;
-    ring.read_slot = BNSLOT - 1;
+    HRing ring = hring_start<NWV, F16>(a.stream, a.stream_bytes, smem, wave, lane);
 #pragma unroll
-    for (int i = 0; i < bdma_of(NWV); ++i) bring_dma<NWV, F16>(ring, i);       // slot 0
-    bring_next_fetch<F16>(ring);
+    for (int i = 0; i < hring_dmas(NWV); ++i) hring_dma<NWV, F16>(ring, i);       // slot 0
+    hring_next_fetch<F16>(ring);
 #pragma unroll
-    for (int i = 0; i < bdma_of(NWV); ++i) bring_dma<NWV, F16>(ring, i);       // slot 1; slot p+2 streams in while slot p is consumed
+    for (int i = 0; i < hring_dmas(NWV); ++i) hring_dma<NWV, F16>(ring, i);       // slot 1; slot p+2 streams in while slot p is consumed
 
     u32x4b aq[DA];
-    bring_advance<NWV, F16>(ring);                           // also publishes the side tables (barrier)
+    hring_advance<NWV, F16>(ring);                           // also publishes the side tables (barrier)
 #pragma unroll
-    for (int i = 0; i < DA - 1; ++i) aq[i] = bring_read<NWV, F16>(smem, ring, lane, i);      // position q is read while group q - (DA - 1) computes
+    for (int i = 0; i < DA - 1; ++i) aq[i] = hring_read<NWV, F16>(smem, ring, lane, i);      // position q is read while group q - (DA - 1) computes
 
 #ifdef MN_DIAG
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -799,7 +681,7 @@ static PhaseB make_phase(const MlpArgsB& a, long long tile0, long long tile_end,
 template <int NPA, int NPB, int NWV, bool F16>
 static int launch_half(MlpArgsB a, long long split, long long n_wtiles, hipStream_t st) {
     constexpr int NPM = NPA > NPB ? NPA : NPB;
-    const size_t lds = BRING_BYTES + (size_t)a.side_floats * 4 + (size_t)NWV * (NPM / 2) * (256 / 2) * 4 + (size_t)NWV * NPM * enc_ksteps32(10) * QUAD_BYTES;
+    const size_t lds = HRING_BYTES + (size_t)a.side_floats * 4 + (size_t)NWV * (NPM / 2) * (256 / 2) * 4 + (size_t)NWV * NPM * enc_ksteps32(10) * QUAD_BYTES;
     MN_CHECK_ARG(lds <= 160 * 1024, "LDS budget exceeded: %zu bytes", lds);
     auto kern = [] {                                         // only the element type of this translation unit is instantiated
         if constexpr (F16) return mlp_f16_kernel<256, 10, 4, NPA, NPB, NWV>;
@@ -852,7 +734,7 @@ static int launch_half(MlpArgsB a, long long split, long long n_wtiles, hipStrea
 }
 
 // The launch plan (mlp_rays_bf16 / mlp_rays_f16; the caller has checked the network).  L: the blob's layout (half_layout.h); the ring
-// walks L.walk_bytes of stream (bf16: the blob's stream; f16: body + 224 positions of 2 KiB, see bring_next_fetch).
+// walks L.walk_bytes of stream (bf16: the blob's stream; f16: body + 224 positions of 2 KiB, see hring_next_fetch).
 // points_per_wave: 0 = chosen per launch (pick_np), 64 / 32 = forced (A/B measurements, parity tests of each shape)
 // z_dev == NULL (strat != NULL): the kernel draws the stratified depths of render_rays' coarse pass itself and writes them to strat->z_out
 template <bool F16>
@@ -900,7 +782,7 @@ static int mlp_rays_half(const mi_nerf_net* net, const HalfLayout& L, const void
         int n2 = 2;
         while (n2 < S + fine->Nf) n2 <<= 1;
         const size_t scratch = (size_t)slices * (S + 2 * (S - 1) + n2) * sizeof(float);
-        if (scratch > (size_t)BRING_BYTES || n2 > 512) return;
+        if (scratch > (size_t)HRING_BYTES || n2 > 512) return;
         a.fz_on = 1; a.fz_Nf = fine->Nf; a.fz_n2 = n2; a.fz_det = fine->det;
         a.fz_u = Jitter{fine->u, fine->seed, 1u, (long long)fine->ray0};
         a.fz_rgb = fine->rgb_c; a.fz_disp = fine->disp_c; a.fz_w = fine->w_c; a.fz_zf = fine->z_f;

@@ -75,23 +75,7 @@ void mlp_dgrad_kernel(const DgradArgs a) {
     const long long n_wg_tiles = (a.n_wtiles + 3) >> 2;
     if ((long long)blockIdx.x >= n_wg_tiles) return;
 
-    WRing ring;
-    ring.sbase = a.stream + wave * (4 * QUAD_BYTES);
-    ring.voff = lane * 16;
-    ring.fetch_off = 0;
-    ring.stream_bytes = a.stream_bytes;
-    ring.lds_lo = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * (4 * QUAD_BYTES);
-    ring.lds_hi = ring.lds_lo + RING_BYTES;
-    ring.fetch_lds = ring.lds_lo;
-    ring.read_slot = NSLOT - 1;
-#ifdef MN_DIAG
-    ring.dlog = nullptr; ring.dcnt = 0;
-#endif
-#pragma unroll
-    for (int sl = 0; sl < 3; ++sl) {
-        if (sl) ring_next_fetch(ring);
-        ring_dma<0>(ring); ring_dma<1>(ring); ring_dma<2>(ring); ring_dma<3>(ring);
-    }
+    WRing ring = ring_start(a.stream, a.stream_bytes, smem, wave, lane);
 
     f32x16 acc[8];
     f32x4 aq[8];

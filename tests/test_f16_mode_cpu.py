@@ -198,9 +198,9 @@ def _exact_state_dict(D, skip):
 
 
 def _ring_reads(walk_bytes, real_bytes):
-    """Blob offsets the f16 kernel's weight ring reads for every stream position, in the order mlp_half_core.h issues them: slot s (32
+    """Blob offsets the f16 kernel's weight ring reads for every stream position, in the order wstream_ring.h issues them: slot s (32
     positions), wave w (8 positions each), DMA i: fetch_off + 16 KiB w + 2 KiB i, the last slot's shares past the blob moved 32 KiB back.
-    A restatement of bring_dma<.., true> / bring_next_fetch<true> / the src_lim set-up in mlp_half_body (the kernel's comments point here):
+    A restatement of hring_dma<.., true> / hring_next_fetch<true> / the src_lim set-up in hring_start<.., true> (wstream_ring.h, whose comments point here):
     it checks that this arithmetic fits the blobs, not that the kernel still does this arithmetic -- the GPU parity tests do that."""
     n_slots = walk_bytes // (2 * SLOT_QUADS * QUAD)
     pos = {}

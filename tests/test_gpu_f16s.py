@@ -294,10 +294,17 @@ def test_f16s_device_pack_is_the_host_pack(D, skip):
     assert int(bad) > 0
 
 
-@pytest.mark.parametrize("n,S", [(300, 64), (77, 65), (64, 192)])
+def _one_tile_more_than_the_grid_has_waves():
+    """Rays of 32 samples (one 32-point tile = one unit each) for which some wave of the split-precision kernels' grid (a workgroup of four
+    waves per CU) runs a SECOND unit: only then is the weight ring's wrap to the head of the stream consumed (wstream_ring.h)."""
+    return 4 * torch.cuda.get_device_properties(0).multi_processor_count + 1
+
+
+@pytest.mark.parametrize("n,S", [(300, 64), (77, 65), (64, 192), (0, 32)])
 def test_f16s_training_forward_leaves_the_fp32_stash(n, S, lego_rays):
     """Same raw outputs (fp32 grade), same activation rows, same ReLU' bits in the backward kernel's own lane order: the masks may differ
-    only where a pre-activation is within rounding of zero."""
+    only where a pre-activation is within rounding of zero.  (n = 0: one tile more than the grid has waves.)"""
+    n = n or _one_tile_more_than_the_grid_has_waves()
     sd = synthetic.make_state_dict(3, 8, 256)
     net = weights.infer_net(sd)
     rays = lego_rays[:n].contiguous()
@@ -393,10 +400,12 @@ def test_f16s_backward_stream_device_pack_is_the_host_pack(D, skip):
     assert torch.equal(dev.cpu(), host) and int(bad) == 0
 
 
-@pytest.mark.parametrize("D,skip,n,S", [(8, 4, 200, 64), (8, 4, 64, 192), (3, 0, 77, 65), (2, -1, 40, 33)])
+@pytest.mark.parametrize("D,skip,n,S", [(8, 4, 200, 64), (8, 4, 64, 192), (3, 0, 77, 65), (2, -1, 40, 33), (8, 4, 0, 32)])
 def test_f16s_backward_data_chain_matches_the_fp32_kernel(D, skip, n, S, lego_rays):
     """dgrad_f16s_kernel against mlp_dgrad_kernel on the same stash and the same (tiny) d_raw: every pre-activation gradient row --
-    delta_d, delta_f, delta_h[l] -- within 2e-5 of the tensor's largest entry (two fp32-grade evaluations of the same chain)."""
+    delta_d, delta_f, delta_h[l] -- within 2e-5 of the tensor's largest entry (two fp32-grade evaluations of the same chain).
+    (n = 0: one tile more than the grid has waves.)"""
+    n = n or _one_tile_more_than_the_grid_has_waves()
     sd = synthetic.make_state_dict(8, D, 256, skips=() if skip < 0 else (skip,))
     net = weights.infer_net(sd)
     rays = lego_rays[:n].contiguous()

@@ -11,7 +11,7 @@ For an asm MFMA nothing is inserted, so these are the kernels' own obligation:
               result lands.  The second case is what took down round 3's `-DMN_F16S_NOPACK` ablation build: with the packing elided the
               accumulators were dead on arrival, the allocator reused their registers at once (`v_mfma v[54:57]` ... `v_lshl_add_u64
               v[54:55]` ... `global_load_lds_dwordx4 v[54:55]`, and `v_mfma v[12:15]` ... barrier ... `v_add_u32 v12, 0x8000, v74` =
-              the ring's fetch offset), and the late matrix write turned an address into float bits: a page fault.
+              the ring's fetch offset, hring_next_fetch in wstream_ring.h), and the late matrix write turned an address into float bits: a page fault.
   WAR on C    the pipe reads srcC late: a VALU write of srcC needs 7 (8-pass) / 13 (16-pass) wait states after the MFMA.
   MFMA A / B  an MFMA reading another MFMA's vdst as A or B needs the same P + 4 (C -> C of the same shape is forwarded by hardware).
   operands    an AGPR written by `v_accvgpr_write` (a packed fragment) may be an MFMA operand 2 wait states later at the earliest.
@@ -44,8 +44,9 @@ NO_VDST = ("global_store", "ds_write", "ds_store", "global_load_lds", "buffer_st
            "v_readfirstlane", "v_readlane", "global_atomic", "buffer_atomic", "ds_add", "ds_max", "ds_min", "ds_or", "ds_and", "global_wb", "global_inv", "buffer_wbl2", "buffer_inv")
 
 
-def device_asm(path: str) -> str:
-    """Disassembly of the gfx950 code object inside a host object / shared library built by hipcc."""
+def device_asm(path: str, tool=(OBJDUMP, "-d")) -> str:
+    """Disassembly of the gfx950 code object inside a host object / shared library built by hipcc (or what another llvm tool, given as
+    its command line, prints for that code object: tools/codegen_diff.py reads the kernels' metadata notes this way)."""
     work = tempfile.mkdtemp()
     try:
         local = os.path.join(work, "k.o")
@@ -57,7 +58,7 @@ def device_asm(path: str) -> str:
         if not dev:
             return ""                                           # a host-only object (pack.cpp.o): no device code, nothing to check
         assert len(dev) == 1, os.listdir(work)
-        return subprocess.run([OBJDUMP, "-d", os.path.join(work, dev[0])], check=True, capture_output=True, text=True).stdout
+        return subprocess.run([*tool, os.path.join(work, dev[0])], check=True, capture_output=True, text=True).stdout
     finally:
         shutil.rmtree(work)
 
