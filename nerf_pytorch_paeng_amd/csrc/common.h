@@ -102,9 +102,13 @@ __device__ __forceinline__ float stratified_depth(long long ray, int i, int S, f
 // ---------------------------------------------------------------------------------------------
 // accurate sin / cos for positional encoding.  Arguments are 2^k * x (exact in fp32) and reach
 // ~3e3 rad for lego, so the reduction matters: 3-term Cody-Waite with FMA (pi/2 = HI + MID + LO),
-// then the Cephes single-precision minimax polynomials on [-pi/4, pi/4].  |error| <~ 1.5e-7.
+// then the Cephes single-precision minimax polynomials on [-pi/4, pi/4].
 // quad_shift 0 -> sin(y), 1 -> cos(y) (cos y = sin(y + pi/2): same reduction, next quadrant).
-// Beyond 2^22 the float multiple count is no longer exact: fall back to the libm path.
+// Accuracy: |error| <= 1.3e-7 for |y| < 2^20 (measured against float64, tests/test_gpu_far_points.py: 9.3e-8 up to 2^19, 1.2e-7 in
+// [2^19, 2^20)).  The weak point is the multiple count: nf = rint(y * 2/pi) is an fp32 product, whose ulp is 2^-5 at 2^19 and 0.25 at
+// 4e6, so nf is off by one over a growing share of each quadrant, |r| exceeds pi/4 (0.88 at 2^20, 0.97 at 2^21, 1.14 at 4e6) and the
+// polynomials leave their interval: 3.7e-7 in [2^20, 2^21), 2.8e-6 up to 4e6.  The subtraction itself stays exact far beyond.
+// Hence the limit below: from 2^20 on callers take the libm path.
 // ---------------------------------------------------------------------------------------------
 // The three stages are separate functions so that a caller can spread one evaluation over several instruction groups
 // (mlp_fp32.hip computes the NEXT tile's gamma(x) under the current tile's MFMAs); sin_cos_fast is their composition.
@@ -142,9 +146,9 @@ __device__ __forceinline__ float sin_cos_fast(float y, int quad_shift) {
     sc_poly(r, sp, cp);
     return sc_select(sp, cp, q);
 }
-// |y| below this bound keeps the float multiple count exact; callers branch ONCE per point on the largest
-// argument and use the libm path (sinf/cosf, Payne-Hanek) for anything bigger or non-finite.
-constexpr float SINCOS_FAST_LIMIT = 4.0e6f;
+// |y| below this bound keeps the multiple count close enough for the accuracy stated above; callers branch ONCE per point on the
+// largest argument and use the libm path (sinf/cosf, Payne-Hanek) for anything bigger or non-finite.  (4e6 until the far-point tests.)
+constexpr float SINCOS_FAST_LIMIT = 1048576.0f;      // 2^20
 __device__ __forceinline__ float sin_cos_slow(float y, int quad_shift) { return quad_shift ? cosf(y) : sinf(y); }
 
 }  // namespace minerf

@@ -11,7 +11,7 @@
 //   * OUTPUT-TILE-MAJOR order ("t-outer").  A layer is 16 jobs; job t computes output features 16t..16t+15 over ALL
 //     k-steps with ONE small accumulator per point tile.  Tiles 2s, 2s+1 of layer l are exactly B fragment s of layer
 //     l+1, which that layer does not touch before its k-step s -- so the packing of job j's accumulators
-//     (v_cvt_pk_bf16_f32 + ReLU as v_pk_max_i16 on the packed pair) is dealt out over the groups of job j+1, across
+//     (v_cvt_pk_bf16_f32 + ReLU as v_pk_maximum3_f16 on the packed pair's bit patterns: mlp_half_core.h pack_stage) is dealt out over the groups of job j+1, across
 //     layer boundaries as well: there IS no layer boundary.  The bias is the C operand of a job's first MFMA.
 //   * 64 POINTS PER WAVE (four point tiles of 16, one wave per SIMD): every A fragment (one ds_read_b128 per lane)
 //     feeds four MFMAs (64 matrix cycles), so LDS reads and the L2 -> LDS stream are half of the 32-points-per-wave

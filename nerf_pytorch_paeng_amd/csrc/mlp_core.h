@@ -193,13 +193,16 @@ __device__ __forceinline__ void acc_init(f32x16 (&acc)[8], const float* vec_lds,
         }
 }
 
-// ReLU as ONE integer instruction, pinned where it is written (volatile): max_i32(bits, 0) keeps every non-negative
-// float (and +NaN) and maps negatives and -0.0 to +0.0.  A plain fmaxf() costs two instructions (hipcc canonicalises
-// the MFMA output first) and hipcc defers them to directly in front of the MFMA that consumes the value, which then
-// waits out the VALU latency plus hazard nops: ~20 cycles per k-step in the trunk layers (MN_DIAG stamps).
+// ReLU as ONE instruction, pinned where it is written (volatile): gfx950's NaN-PROPAGATING maximum (v_maximum3_f32, IEEE 754-2019, as the
+// split-precision kernel): negatives and -0.0 become +0.0, a NaN of EITHER sign stays a NaN.  (Until the far-point tests this was
+// v_max_i32(bits, 0), which keeps +NaN but turns a NaN with its sign bit set -- 0 / 0 of a zero view direction, inf * 0 -- into 0: the
+// network went on with zeros and returned plausible finite colours, tests/test_gpu_far_points.py.)  A plain fmaxf() costs two
+// instructions (hipcc canonicalises the MFMA output first), returns the OTHER operand for a NaN, and hipcc defers it to directly in
+// front of the MFMA that consumes the value, which then waits out the VALU latency plus hazard nops: ~20 cycles per k-step in the
+// trunk layers (MN_DIAG stamps).
 __device__ __forceinline__ float relu_pinned(float x) {
     float r;
-    asm volatile("v_max_i32 %0, 0, %1" : "=v"(r) : "v"(x));
+    asm volatile("v_maximum3_f32 %0, %1, 0, 0" : "=v"(r) : "v"(x));
     return r;
 }
 
@@ -252,7 +255,7 @@ __device__ __forceinline__ void store_chunk(const float (&h)[NB], int q, float* 
 }
 
 // ReLU' bit masks.  Registers are packed in order, each word shifted left by one per value: register 4q+e lands in bit
-// 31 - (4*(q&7)+e) of word q>>3 (words always fill: 8 chunks each).  The registers are post-ReLU (+0.0 or positive,
+// 31 - (4*(q&7)+e) of word q>>3 (words always fill: 8 chunks each).  The registers are post-ReLU (+0.0, positive or NaN,
 // relu_pinned), so "non-zero bit pattern" == "> 0": min(bits, 1) shifted in, 2 VALU per value.  Pinned with asm volatile:
 // written in C++, hipcc defers all 128 packs of a layer to the end of the GEMM (~2200 exposed cycles per layer).
 template <int NB>

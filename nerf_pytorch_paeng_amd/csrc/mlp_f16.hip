@@ -12,11 +12,11 @@
 //     ring walks 224 positions and, in the last slot, re-reads data it never uses instead of running past the blob (hring_next_fetch).
 //     No packer of its own: the f16s packers' weight check (|w| < 65 504, not NaN; the device packer's out-of-range count) applies.
 //   * ACTIVATIONS packed by v_cvt_pk_f16_f32 (round to nearest even), then v_pk_fma_f16 h * 0 + h -- +-inf (an activation at or beyond
-//     65 520) becomes NaN, a finite h stays h -- and the ReLU as v_pk_maximum3_f16, NaN-propagating.  (bf16's v_pk_max_i16 would turn a
+//     65 520) becomes NaN, a finite h stays h -- and the ReLU as v_pk_maximum3_f16, NaN-propagating.  (an integer maximum would turn a
 //     NaN with its sign bit set into 0, and a ReLU after an inf would turn -inf into 0.)  So the RANGE CONTRACT of the split-precision mode
 //     holds (include/mi_nerf.h): an activation beyond the f16 range gives NaN in every output that depends on it, never a finite value.
 //     Two or four packed VALU instructions per tile and pair where bf16 has zero or two.
-//   * gamma(x) is evaluated PER CHANNEL (Cody-Waite + Cephes, libm beyond 4e6 rad: the split-precision kernel's code), not by angle
+//   * gamma(x) is evaluated PER CHANNEL (Cody-Waite + Cephes, libm from 2^20 rad on: the split-precision kernel's code), not by angle
 //     doubling.  Doubling is up to ~5e-5 off at the top octave: below bf16's half-ulp (~2e-3 at 1.0) by two orders, but a fifth of f16's
 //     (2.4e-4 at 1.0), so it would flip the f16 rounding of a share of the top octaves' channels against the oracle's exact sin / cos -- an
 //     error of the kernel's own making, on top of the f16 rounding the mode is about.  The cost is 27 more sin / cos per point in the

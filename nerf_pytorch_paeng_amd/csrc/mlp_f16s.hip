@@ -21,7 +21,7 @@
 //   * packing a pair of accumulator elements (12 VALU): y = fma(lo, 2^-11, hi); Y = fma(hi, 2^11, lo) (= 2^11 y); hi_pk =
 //     v_cvt_pk_f16_f32(y0, y1) [v_pk_maximum3_f16 for ReLU, Y = maximum(Y, 0): NaN-propagating]; lo halves by v_fma_mixlo/hi_f16(hi_half, -2^11, Y): the
 //     residual (y - hi) 2^11 computed exactly and rounded once; two v_accvgpr_write;
-//   * gamma(x) is evaluated in full precision per channel (Cody-Waite + Cephes like the fp32 kernel, libm beyond 4e6 rad), not by
+//   * gamma(x) is evaluated in full precision per channel (Cody-Waite + Cephes like the fp32 kernel, libm from 2^20 rad on), not by
 //     angle doubling: this variant's contract is fp32-grade output.
 // The packers of the (hi, lo) stream (host and device; forward and the backward-data chain) are pack_half.hip's; half_layout.h has the layout.
 // Ranges: |weights| and |activations| must stay below the f16 maximum (65 504).  The packer refuses larger weights; an activation beyond it

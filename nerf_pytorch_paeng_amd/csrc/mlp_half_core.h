@@ -104,11 +104,17 @@ __device__ __forceinline__ unsigned pack2(float lo, float hi) {
 __host__ __device__ constexpr int frag_reg(int np, int set, int p, int f) { return ((set * np + p) * 8 + f) * 4; }
 
 // A finished 16x16 tile (4 accumulator registers per lane) -> two packed dwords -> registers R, R + 1 of the fragment file
-// (tile t of a layer is dwords 2(t&1), 2(t&1)+1 of fragment t>>1).  ReLU on the packed pair: as signed 16-bit integers every
-// negative bf16 (and -0.0) is below zero.  In three stages of two independent instructions each, one stage per MFMA gap (a 16-cycle
+// (tile t of a layer is dwords 2(t&1), 2(t&1)+1 of fragment t>>1).  ReLU on the packed pair, one instruction per dword.  bf16: the
+// NaN-propagating f16 maximum v_pk_maximum3_f16 on the bf16 BIT PATTERNS -- the sign bit is the same bit, so every negative bf16 (and
+// -0.0) reads as a negative f16 and becomes +0, every non-negative one is returned unchanged, and a bf16 NaN of either sign reads as a
+// QUIET f16 NaN (bits 14..7 set, bit 9 among them) and is returned unchanged.  (v_pk_max_i16, used until the far-point tests, turned a
+// NaN with its sign bit set into 0 and the network returned finite colours for NaN inputs.)  Two patterns differ from the integer
+// maximum: bf16 -inf reads as an f16 NaN and STAYS -inf (the next layer turns it into inf / NaN instead of treating the unit as off), and
+// |x| >= 2^121 with bit 9 clear reads as a signalling f16 NaN and is quieted (another value of that size); neither occurs for finite
+// inputs.  In three stages of two independent instructions each, one stage per MFMA gap (a 16-cycle
 // MFMA leaves room for two VALU issues), or as one statement where there are more gaps than work.
 // f16 (stage 1 carries two or four instructions): the ReLU as gfx950's NaN-PROPAGATING maximum (v_pk_maximum3_f16, as the split-precision
-// kernel; v_pk_max_i16 would turn a NaN with its sign bit set into 0), then +-inf -> NaN as in pack2.  In that order a pre-activation
+// kernel), then +-inf -> NaN as in pack2.  In that order a pre-activation
 // <= -65520 in front of a ReLU is an exact 0 (the unit is off, as in fp32) and +inf, or -inf out of linear_feat (no ReLU), is NaN.
 template <bool F16, bool RELU, int R, int STAGE>
 __device__ __forceinline__ void pack_stage(const f32x4& acc, unsigned (&t)[2]) {
@@ -121,7 +127,7 @@ __device__ __forceinline__ void pack_stage(const f32x4& acc, unsigned (&t)[2]) {
         else asm volatile("v_accvgpr_write_b32 a[%2], %0\n\tv_accvgpr_write_b32 a[%3], %1" ::"v"(t[0]), "v"(t[1]), "n"(R), "n"(R + 1));
     } else {
         if constexpr (STAGE == 0) asm volatile("v_cvt_pk_bf16_f32 %0, %2, %3\n\tv_cvt_pk_bf16_f32 %1, %4, %5" : "=&v"(t[0]), "=&v"(t[1]) : "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]));
-        else if constexpr (STAGE == 1) { if (RELU) asm volatile("v_pk_max_i16 %0, %0, 0\n\tv_pk_max_i16 %1, %1, 0" : "+v"(t[0]), "+v"(t[1])); }
+        else if constexpr (STAGE == 1) { if (RELU) asm volatile("v_pk_maximum3_f16 %0, %0, 0, 0\n\tv_pk_maximum3_f16 %1, %1, 0, 0" : "+v"(t[0]), "+v"(t[1])); }
         else asm volatile("v_accvgpr_write_b32 a[%2], %0\n\tv_accvgpr_write_b32 a[%3], %1" ::"v"(t[0]), "v"(t[1]), "n"(R), "n"(R + 1));
     }
 }
@@ -338,9 +344,11 @@ __device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, ch
             } else
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                // octave 0: Cody-Waite + Cephes as in the fp32 kernel.  Beyond 4e6 rad the multiple count is no longer exact (and
-                // an fp32 argument with ulp >= 0.25 rad has no meaningful sine): the remainder is clamped so that finite inputs
-                // give finite, bounded encodings; NaN / Inf still come out as NaN.  (The fp32 kernel takes the libm path there.)
+                // octave 0: Cody-Waite + Cephes as in the fp32 kernel, with no libm path.  The multiple count rint(y * 2/pi) is an fp32
+                // product: from about 2^20 rad on it is off by one often enough that |r| leaves the polynomials' interval (common.h),
+                // and beyond 2^22 it is no longer an integer count at all (an fp32 argument with ulp >= 0.25 rad has no meaningful sine
+                // anyway): the remainder is clamped so that finite inputs give finite, bounded encodings (|gamma| <= 1.1 after nine
+                // doublings, tests/test_gpu_far_points.py); NaN / Inf still come out as NaN.  (The fp32 kernel takes the libm path there.)
                 float r, sp, cp; int q;
                 sc_reduce(pt[c], 0, r, q);
                 r = __builtin_fminf(__builtin_fmaxf(r, -0.8f), 0.8f) + (r - r);      // (r - r): 0, or NaN for a non-finite remainder
