@@ -3,10 +3,12 @@ standing in for the dataset loaders (no dataset ships with either repository).  
 reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap the imports back and the same script drives the reference.
 
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
-                                             [--scene teacher|solid]
+                                             [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
-mi_scene_render -- instead of views of a random network.
+mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
++-``--mesh-box`` is turned into a triangle mesh at the level ``--mesh-iso`` (mesh.extract: marching tetrahedra on the device), coloured by the
+network and written as a binary PLY.  No counterpart in the reference.
 """
 import argparse
 import os
@@ -32,6 +34,10 @@ def main(argv=None):
     ap.add_argument("--net-width", type=int, default=256)
     ap.add_argument("--render-views", type=int, default=8)
     ap.add_argument("--scene", default="teacher", choices=["teacher", "solid"], help="teacher: views of a random network; solid: scenes.SolidScene.default()")
+    ap.add_argument("--mesh", default=None, metavar="PATH", help="write the trained scene's surface as a coloured PLY")
+    ap.add_argument("--mesh-res", type=int, default=128, help="lattice cells per axis (1..512)")
+    ap.add_argument("--mesh-iso", type=float, default=10.0, help="raw density of the surface")
+    ap.add_argument("--mesh-box", type=float, default=1.5, help="the lattice spans +-this on every axis")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -71,6 +77,15 @@ def main(argv=None):
           f"(mean {res['mean_ssim']:.4f}); PNGs and _result.txt in {a.out}/test_result")
     rgbs, disps = harness.render(a.steps, posenc, fresh, K, None, (H, W), opts, log_dir=a.out, save_dir=os.path.join(a.out, "render_result"))   # main.py:150-158
     print(f"render: {rgbs.shape[0]} frames {rgbs.shape[1]}x{rgbs.shape[2]} in {a.out}/render_result")
+    if a.mesh:
+        from nerf_pytorch_paeng_amd import mesh
+        with torch.no_grad():
+            field = mesh.density_lattice(fresh, -a.mesh_box, a.mesh_box, a.mesh_res, network="fine", precision=a.precision)
+            m = mesh.extract(field, -a.mesh_box, a.mesh_box, a.mesh_iso).colorize(fresh, network="fine")
+        os.makedirs(os.path.dirname(os.path.abspath(a.mesh)), exist_ok=True)
+        m.save_ply(a.mesh)
+        print(f"mesh: {m.verts.shape[0]} vertices, {m.tris.shape[0]} triangles at density {a.mesh_iso:g} on a {a.mesh_res}^3 lattice of +-{a.mesh_box:g}; "
+              f"area {m.area():.3f}, enclosed volume {m.volume():.4f}; {a.mesh}")
     return res
 
 

@@ -1,4 +1,4 @@
-"""Build libmi_nerf.so, libmi_nerf_iqa.so, libmi_nerf_occ.so and libmi_nerf_scene.so with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libmi_nerf.so, libmi_nerf_iqa.so, libmi_nerf_occ.so, libmi_nerf_scene.so and libmi_nerf_mesh.so with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m nerf_pytorch_paeng_amd.build [--force]          the shipped libraries (clean build: ~1 min 20 s on 8 cores)
     python -m nerf_pytorch_paeng_amd.build --variant TAG -DFOO -DBAR=1     an A/B variant (tools/ab_probe.py)
@@ -16,6 +16,8 @@ What lands where:
                                                     own, linked against libmi_nerf.so (rpath $ORIGIN), whose public entries it calls.
   nerf_pytorch_paeng_amd/libmi_nerf_scene.so (+ .stamp) procedural solid scenes (include/mi_nerf_scene.h, csrc/scene.hip): a fourth library with a stamp
                                                     of its own; it includes no other header and links against no other library of the project.
+  nerf_pytorch_paeng_amd/libmi_nerf_mesh.so (+ .stamp)  mesh extraction (include/mi_nerf_mesh.h, csrc/mesh.hip): a fifth library with a stamp of its own,
+                                                    linked against libmi_nerf.so (rpath $ORIGIN) like libmi_nerf_occ.so.
   build_scratch/obj/                                objects of the shipped library (cache; tests/test_packing_cpu.py disassembles them)
   build_scratch/obj_TAG/, build_scratch/libmi_nerf_TAG.so    variants.  build_scratch/ is git-ignored AND gpurun-ignored: a variant is
                                                     built where it is used (tools/ab_probe.py builds the ones it is asked for on the box).
@@ -49,6 +51,10 @@ OCC_SOURCES = ["occ.hip"]
 SCENE_LIB = os.path.join(HERE, "libmi_nerf_scene.so")
 SCENE_STAMP = SCENE_LIB + ".stamp"
 SCENE_SOURCES = ["scene.hip"]
+# libmi_nerf_mesh.so: its own source and header; it includes mi_nerf.h (types, three public entries) and links against libmi_nerf.so
+MESH_LIB = os.path.join(HERE, "libmi_nerf_mesh.so")
+MESH_STAMP = MESH_LIB + ".stamp"
+MESH_SOURCES = ["mesh.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          # the MLP kernel's register-resident design needs its k-loops FULLY unrolled (static register indices)
@@ -80,6 +86,10 @@ def _occ_headers():
 
 def _scene_headers():
     return [os.path.join(INCLUDE, "mi_nerf_scene.h")]
+
+
+def _mesh_headers():
+    return [os.path.join(INCLUDE, "mi_nerf_mesh.h"), os.path.join(INCLUDE, "mi_nerf.h")]
 
 
 def _digest(paths, extra=()) -> str:
@@ -213,6 +223,27 @@ def build_scene_library(force: bool = False, verbose: bool = False) -> str:
     return SCENE_LIB
 
 
+def mesh_source_stamp() -> str:
+    return _digest([os.path.join(CSRC, s) for s in MESH_SOURCES] + _mesh_headers(), [FLAGS, OCC_LINK[1:]])
+
+
+def build_mesh_library(force: bool = False, verbose: bool = False) -> str:
+    """libmi_nerf_mesh.so, a no-op when its stamp matches (like build_library).  It links against libmi_nerf.so, which is built first."""
+    build_library()
+    want = mesh_source_stamp()
+    if not force and os.path.exists(MESH_LIB) and os.path.exists(MESH_STAMP) and open(MESH_STAMP).read() == want:
+        if verbose:
+            print(f"up to date: {MESH_LIB} ({os.path.getsize(MESH_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+        return MESH_LIB
+    objs = [_compile(s, force, headers=_mesh_headers()) for s in MESH_SOURCES]
+    _link(objs, MESH_LIB, OCC_LINK)
+    with open(MESH_STAMP, "w") as fh:
+        fh.write(want)
+    if verbose:
+        print(f"built {MESH_LIB} ({os.path.getsize(MESH_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+    return MESH_LIB
+
+
 def variant_path(tag: str) -> str:
     return os.path.join(SCRATCH, f"libmi_nerf_{tag}.so")
 
@@ -260,3 +291,4 @@ if __name__ == "__main__":
         print(build_iqa_library(force="--force" in sys.argv, verbose=True))
         print(build_occ_library(force="--force" in sys.argv, verbose=True))
         print(build_scene_library(force="--force" in sys.argv, verbose=True))
+        print(build_mesh_library(force="--force" in sys.argv, verbose=True))
