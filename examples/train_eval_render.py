@@ -4,11 +4,14 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
 
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10]]
+                                             [--train-occupancy WARMUP:EVERY]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
 +-``--mesh-box`` is turned into a triangle mesh at the level ``--mesh-iso`` (mesh.extract: marching tetrahedra on the device), coloured by the
-network and written as a binary PLY.  No counterpart in the reference.
+network and written as a binary PLY.  No counterpart in the reference.  ``--train-occupancy WARMUP:EVERY``: WARMUP full steps, then an
+occupancy grid is baked from the model (128^3 cells; ``--scene solid``: the box +-1.5 with everything outside it skipped, otherwise a box that
+holds every sample) and the remaining steps skip the samples it marks empty (occupancy_train.py), re-baking every EVERY steps (0: never).
 """
 import argparse
 import os
@@ -38,7 +41,16 @@ def main(argv=None):
     ap.add_argument("--mesh-res", type=int, default=128, help="lattice cells per axis (1..512)")
     ap.add_argument("--mesh-iso", type=float, default=10.0, help="raw density of the surface")
     ap.add_argument("--mesh-box", type=float, default=1.5, help="the lattice spans +-this on every axis")
+    ap.add_argument("--train-occupancy", default=None, metavar="WARMUP:EVERY", help="train with an occupancy grid baked after WARMUP full steps, re-baked every EVERY steps")
     a = ap.parse_args(argv)
+    occ_warmup = occ_every = None
+    if a.train_occupancy is not None:
+        try:
+            occ_warmup, occ_every = (int(v) for v in a.train_occupancy.split(":"))
+        except ValueError:
+            ap.error("--train-occupancy takes WARMUP:EVERY, two integers")
+        if occ_warmup < 0 or occ_every < 0:
+            ap.error("--train-occupancy takes two non-negative integers")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     H = W = a.size
@@ -66,10 +78,22 @@ def main(argv=None):
     getter = harness.global_batch(images, K, poses, i_train, (H, W), dev)                        # main.py:92-106
     t0 = time.perf_counter()
     for i in range(1, a.steps + 1):                                                              # main.py:136-139
+        if occ_warmup is not None and i == occ_warmup + 1:                                       # the warm-up is over: bake, and train with the grid from here on
+            from nerf_pytorch_paeng_amd import occupancy
+            box, outside = (1.5, False) if a.scene == "solid" else (4.5, True)
+            with torch.no_grad():
+                opts.train_occupancy = occupancy.OccupancyGrid(-box, box, 128, outside_occupied=outside).bake(model, f16s=a.precision == "f16s")
+            opts.occupancy_rebake_every = occ_every
+            opts.occupancy_bake_args = {"f16s": a.precision == "f16s"}
+            print(f"step {i:6d}  occupancy grid baked: {opts.train_occupancy.fraction():.4f} of the cells occupied", flush=True)
         out = harness.train(i, i_train, images, (K, poses.numpy()), (H, W), model, criterion, posenc, optimizer, getter, None, opts, log_dir=a.out)
         if i % opts.idx_print == 0:
             torch.cuda.synchronize()
             print(f"step {i:6d}  loss {float(out['loss']):.5f}  psnr_f {float(out['psnr_f']):.2f} dB  {(time.perf_counter() - t0) / i * 1e3:.1f} ms/step", flush=True)
+            grid = getattr(opts, "train_occupancy", None)
+            if grid is not None and grid.last_stats:
+                from nerf_pytorch_paeng_amd import occupancy
+                print(f"             evaluated share {occupancy.evaluated_share(grid.last_stats):.3f}, padded share {occupancy.padded_share(grid.last_stats):.3f}", flush=True)
     fresh = NeRF(8, a.net_width, 63, 27, skips=[4]).to(dev)                                      # test() loads the checkpoint train() saved (test.py:20-21)
     res = harness.test(a.steps, i_test, posenc, fresh, images[i_test], K, poses[i_test].to(dev), (H, W), opts, log_dir=a.out,
                        save_dir=os.path.join(a.out, "test_result"), ssim=True)                   # main.py:140-149

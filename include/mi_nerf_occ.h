@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MI_OCC_ABI_VERSION 1
+#define MI_OCC_ABI_VERSION 2
 
 /* status codes (the values of mi_nerf.h) */
 #define MI_OCC_OK 0
@@ -90,6 +90,35 @@ int mi_occ_count(const mi_occ_grid* grid, const uint32_t* bits_dev, uint64_t* co
 /* rays [n,6] (o, d), z [n,S] -> mask [n,S] uint8: 1 where the sample is evaluated under THE CELL RULE above, 0 where it is skipped. */
 int mi_occ_mark(const mi_occ_grid* grid, const uint32_t* bits_dev, const float* rays_dev, const float* z_dev, int64_t n_rays, int S,
                 uint8_t* mask_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The compaction as an entry of its own, with a REPRODUCIBLE tile order -- what the training path (occupancy_train.py) is built on: it
+ * drives the networks itself (mi_nerf_mlp_rays_train / mi_nerf_mlp_backward on the tiles as pseudo-rays with S = 32) between these entries.
+ * THE COMPACTION RULE (THE CELL RULE above decides what survives):
+ *     ray r has k_r survivors, in sample order, and owns t_r = ceil(k_r / 32) tiles starting at base_r = sum of t_q over q < r
+ *     tile base_r + j holds survivors 32 j .. 32 j + 31: tile_z their depths, tile_src = r * S + s; the padding lanes of a ray's last tile
+ *     repeat the ray's last surviving depth and carry tile_src = -1
+ *     slot[r, s] = 32 * (base_r + j) + lane of a survivor, -1 of a skipped sample;  tile_rays[base_r + j] = rays[r]
+ *     counts_dev (uint32 [2]) = (sum of t_r, sum of k_r)
+ * Three passes -- count (one wave per ray), exclusive scan of t_r, emit -- and NO atomic: every output is a function of the input, so two
+ * calls give identical bytes.  The caller sizes tile_rays [T,6], tile_z [T,32], tile_src int32 [T,32] for T = n_rays * ceil(S / 32) tiles;
+ * only the first counts[0] tiles are written.  1 <= S <= 1024, n_rays * ceil(S / 32) * 32 < 2^31.  scratch_dev: 256-byte aligned,
+ * mi_occ_compact_scratch_bytes(n_rays) bytes (0 + error text if n_rays is refused).  NO host synchronisation: the entry may be recorded
+ * into a graph; reading counts_dev is the caller's.  n_rays == 0 writes counts = (0, 0) and nothing else.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi_occ_compact_scratch_bytes(int64_t n_rays);
+int mi_occ_compact(const mi_occ_grid* grid, const uint32_t* bits_dev, const float* rays_dev, const float* z_dev, int64_t n_rays, int S,
+                   float* tile_rays_dev, float* tile_z_dev, int32_t* tile_src_dev, int32_t* slot_dev, uint32_t* counts_dev, void* scratch_dev,
+                   size_t scratch_bytes, void* stream);
+
+/* tile_vals [T,32,4], slot int32 [n,S] -> out [n,S,4]: EVERY element is written, tile_vals[slot] of a survivor, (0,0,0,0) where slot = -1.
+ * Same size limits as mi_occ_compact; tile_vals_dev and out_dev 16-byte aligned. */
+int mi_occ_scatter_raw(const float* tile_vals_dev, const int32_t* slot_dev, int64_t n_rays, int S, float* out_dev, void* stream);
+
+/* The inverse, for the gradient of raw: src [n,S,4], tile_src int32 [T,32] -> out [T,32,4] = src[tile_src] per lane, exact zeros where
+ * tile_src = -1.  A padding lane evaluates a real point with d_raw = 0 and so adds exactly zero to every weight-gradient and bias sum.
+ * n_tiles * 32 < 2^31; src_dev and out_dev 16-byte aligned. */
+int mi_occ_gather_raw(const float* src_dev, const int32_t* tile_src_dev, int64_t n_tiles, float* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * render_rays with a grid.  The arguments of mi_nerf_render_rays plus the grid, one bitfield per network (bits_coarse_dev and

@@ -15,7 +15,7 @@ from ._lib import MiNerfError, Net, RenderCfg
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmi_nerf_occ.so")
-ABI_VERSION = 1
+ABI_VERSION = 2
 MAX_RES, MAX_SUB, MAX_RADIUS, TILE = 512, 4, 2, 32          # MI_OCC_MAX_RES, MI_OCC_MAX_SUB, MI_OCC_MAX_RADIUS, MI_OCC_TILE
 
 
@@ -45,6 +45,10 @@ SIGNATURES = {
     "mi_occ_dilate": (_I, [_GRIDP, _P, _P, _I, _P]),
     "mi_occ_count": (_I, [_GRIDP, _P, _P, _P]),
     "mi_occ_mark": (_I, [_GRIDP, _P, _P, _P, _I64, _I, _P, _P]),
+    "mi_occ_compact_scratch_bytes": (_SZ, [_I64]),
+    "mi_occ_compact": (_I, [_GRIDP, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mi_occ_scatter_raw": (_I, [_P, _P, _I64, _I, _P, _P]),
+    "mi_occ_gather_raw": (_I, [_P, _P, _I64, _P, _P]),
     "mi_occ_render_workspace_bytes": (_SZ, [_CFGP, _I64]),
     "mi_occ_render_workspace_layout": (_I, [_CFGP, _I64, C.POINTER(WorkspaceLayout)]),
     "mi_occ_render_rays": (_I, [_NETP, _P, _P, _CFGP, _GRIDP, _P, _P, _P, _I64, _P, _P, _P, _SZ, _P, _P, _P, _P, C.POINTER(Stats), _P]),

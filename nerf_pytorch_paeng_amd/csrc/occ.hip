@@ -7,6 +7,9 @@
 //                      with the ray's last survivor; tiles are reserved with one atomic add per ray (tile ORDER varies from run to run, a
 //                      sample's value does not: each lane of the network kernels evaluates its own point)
 // occ_scatter_kernel   one thread per sample: raw[ray, sample] = tile value of a survivor, zeros otherwise (every element written)
+// occ_compact_*_kernel the same compaction WITHOUT an atomic (mi_occ_compact): count per ray | exclusive scan of the tile counts | emit, so
+//                      the tile order is a function of the input; cscan_*_kernel is the scan (block sums | one block over them | apply)
+// occ_gather_kernel    one thread per tile lane: the inverse of the scatter (d_raw of the training path), zeros on padding lanes
 // occ_bake_gen_kernel  sub-lattice rows along x as rays (origin on the box face, direction +x) with depths
 // occ_bake_reduce_kernel   OR of (density > sigma_min) over a cell's samples of one row, atomically ORed into the cell's bit
 // occ_dilate_kernel    one thread per cell, neighbourhood OR, words assembled by ballot
@@ -174,6 +177,153 @@ __global__ __launch_bounds__(256) void occ_scatter_kernel(const int* __restrict_
     if (i >= n_pts) return;
     const int j = slot[i];
     raw[i] = j >= 0 ? tile_raw[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// ---- deterministic compaction ------------------------------------------------------------------------
+// count | exclusive scan | emit.  One 64-bit word per ray carries both counts through ONE scan: tiles t_r in the low half, survivors k_r in
+// the high half (sum t < 2^26 and sum k < 2^31 under the entry's size limit, so neither half carries into the other).
+constexpr int CSCAN_TILE = 1024;                                       // 256 threads x 4 rays
+
+__global__ __launch_bounds__(256) void occ_compact_count_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
+                                                                const float* __restrict__ z, long long n, int S, unsigned long long* __restrict__ per_ray) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n) return;
+    const float* rp = rays + ray * 6;
+    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
+    const float* zr = z + ray * S;
+    int cnt = 0;
+    for (int c = 0; c < S; c += 64) {
+        const int s = c + lane;
+        const bool occ = s < S && occ_lookup(G, bits, o, d, zr[s]);
+        cnt += __popcll(__ballot(occ));
+    }
+    if (lane == 0) per_ray[ray] = ((unsigned long long)cnt << 32) | (unsigned long long)((cnt + TILE - 1) / TILE);
+}
+
+// exclusive scan of one value per thread over a block of NT threads; *total = the block's sum.  lds: NT / 64 + 1 words.
+template <int NT>
+__device__ __forceinline__ unsigned long long cscan_block(unsigned long long v, unsigned long long* total, unsigned long long* lds) {
+    constexpr int NW = NT / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long t = __shfl_up(x, d, 64);
+        if (lane >= d) x += t;
+    }
+    if (lane == 63) lds[wave] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long run = 0;
+        for (int w = 0; w < NW; ++w) {
+            const unsigned long long s = lds[w];
+            lds[w] = run;
+            run += s;
+        }
+        lds[NW] = run;
+    }
+    __syncthreads();
+    const unsigned long long r = x - v + lds[wave];
+    *total = lds[NW];
+    __syncthreads();                                                   // lds is reused by the caller's next round
+    return r;
+}
+
+__global__ __launch_bounds__(256) void cscan_reduce_kernel(const unsigned long long* __restrict__ data, long long n, unsigned long long* __restrict__ bsum) {
+    __shared__ unsigned long long lds[4];
+    const long long base = (long long)blockIdx.x * CSCAN_TILE + threadIdx.x * 4;
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (base + k < n) s += data[base + k];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) bsum[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+// one block: block sums -> their exclusive prefix sums in place; counts[0] = tiles, counts[1] = survivors of the whole batch
+__global__ __launch_bounds__(1024) void cscan_sums_kernel(unsigned long long* __restrict__ bsum, int nb, unsigned* __restrict__ counts) {
+    __shared__ unsigned long long lds[17];
+    unsigned long long carry = 0;
+    for (int c = 0; c < nb; c += 1024) {
+        const int i = c + (int)threadIdx.x;
+        const unsigned long long v = i < nb ? bsum[i] : 0ull;
+        unsigned long long sum;
+        const unsigned long long ex = cscan_block<1024>(v, &sum, lds);
+        if (i < nb) bsum[i] = carry + ex;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) {
+        counts[0] = (unsigned)(carry & 0xffffffffull);
+        counts[1] = (unsigned)(carry >> 32);
+    }
+}
+
+__global__ __launch_bounds__(256) void cscan_apply_kernel(unsigned long long* __restrict__ data, long long n, const unsigned long long* __restrict__ bsum) {
+    __shared__ unsigned long long lds[5];
+    const long long base = (long long)blockIdx.x * CSCAN_TILE + threadIdx.x * 4;
+    unsigned long long v[4], s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[k] = base + k < n ? data[base + k] : 0ull;
+        s += v[k];
+    }
+    unsigned long long sum;
+    unsigned long long run = bsum[blockIdx.x] + cscan_block<256>(s, &sum, lds);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (base + k < n) data[base + k] = run;
+        run += v[k];
+    }
+}
+
+// One wave = one ray, as occ_cull_kernel's second pass; the ray's first tile comes from the scan (low half of first[ray]).
+__global__ __launch_bounds__(256) void occ_compact_emit_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
+                                                               const float* __restrict__ z, long long n, int S,
+                                                               const unsigned long long* __restrict__ first, float* __restrict__ tile_rays,
+                                                               float* __restrict__ tile_z, int* __restrict__ tile_src, int* __restrict__ slot) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n) return;
+    const float* rp = rays + ray * 6;
+    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
+    const float* zr = z + ray * S;
+    const long long base = (long long)(first[ray] & 0xffffffffull);
+    const int j0 = (int)base * TILE;                                  // first flat tile lane of this ray
+    int run = 0;
+    float last_z = 0.0f;
+    for (int c = 0; c < S; c += 64) {
+        const int s = c + lane;
+        const float zv = s < S ? zr[s] : 0.0f;
+        const bool occ = s < S && occ_lookup(G, bits, o, d, zv);
+        const unsigned long long m = __ballot(occ);
+        const int j = j0 + run + __popcll(m & ((1ull << lane) - 1ull));
+        if (s < S) slot[ray * S + s] = occ ? j : -1;
+        if (occ) {
+            tile_z[j] = zv;
+            tile_src[j] = (int)(ray * S + s);
+        }
+        run += __popcll(m);
+        if (m) last_z = __shfl(zv, 63 - __clzll((long long)m), 64);
+    }
+    const int ntiles = (run + TILE - 1) / TILE;
+    const int pad = ntiles * TILE - run;                              // < 32
+    if (lane < pad) {
+        tile_z[j0 + run + lane] = last_z;
+        tile_src[j0 + run + lane] = -1;
+    }
+    for (int i = lane; i < ntiles * 6; i += 64) tile_rays[base * 6 + i] = rp[i % 6];
+}
+
+__global__ __launch_bounds__(256) void occ_gather_kernel(const int* __restrict__ tile_src, const float4* __restrict__ src, long long n_lanes,
+                                                         float4* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_lanes) return;
+    const int j = tile_src[i];
+    out[i] = j >= 0 ? src[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // ---- bake ------------------------------------------------------------------------------------------
@@ -434,6 +584,54 @@ static int render(const mi_nerf_net* net, const void* packed_c, const void* pack
     return MI_OCC_OK;
 }
 
+// ---- deterministic compaction, scatter, gather (host side) -------------------------------------------
+static inline size_t compact_scratch_bytes(int64_t n) {
+    const size_t nb = ((size_t)n + CSCAN_TILE - 1) / CSCAN_TILE;
+    return align256((size_t)n * 8) + align256(nb * 8) + 256;         // never 0: 0 is the refusal
+}
+
+// the sizes every entry of the training surface accepts: int32 tile lanes
+static int check_tile_sizes(int64_t n, int S) {
+    OCC_CHECK_ARG(n >= 0, "bad size n_rays=%lld", (long long)n);
+    OCC_CHECK_ARG(S >= 1 && S <= 1024, "S=%d: 1..1024 samples per ray", S);
+    OCC_CHECK_ARG((long long)n * ((S + TILE - 1) / TILE) * TILE < (1LL << 31), "n_rays=%lld x %d samples: n_rays * ceil(S / 32) * 32 must stay below 2^31",
+                  (long long)n, S);
+    return MI_OCC_OK;
+}
+
+static int compact(const mi_occ_grid* grid, const uint32_t* bits, const float* rays, const float* z, int64_t n, int S, float* tile_rays, float* tile_z,
+                   int* tile_src, int* slot, unsigned* counts, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    GridDev G;
+    if (int rc = resolve_grid(grid, &G)) return rc;
+    if (int rc = check_tile_sizes(n, S)) return rc;
+    OCC_CHECK_ARG(counts != nullptr, "counts is NULL");
+    OCC_CHECK_ARG(((uintptr_t)counts & 3) == 0, "counts must be 4-byte aligned");
+    if (n == 0) {
+        OCC_HIP(hipMemsetAsync(counts, 0, 8, st));
+        return MI_OCC_OK;
+    }
+    OCC_CHECK_ARG(bits && rays && z && tile_rays && tile_z && tile_src && slot && scratch,
+                  "NULL pointer (bits, rays, z, tile_rays, tile_z, tile_src, slot, counts and scratch are required)");
+    OCC_CHECK_ARG(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
+    const size_t need = compact_scratch_bytes(n);
+    OCC_CHECK_ARG(scratch_bytes >= need, "scratch too small: %zu < %zu (mi_occ_compact_scratch_bytes)", scratch_bytes, need);
+    unsigned long long* per_ray = (unsigned long long*)scratch;
+    unsigned long long* sums = (unsigned long long*)((char*)scratch + align256((size_t)n * 8));
+    const unsigned nb = blocks_for(n, CSCAN_TILE);
+    hipLaunchKernelGGL(occ_compact_count_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, st, G, bits, rays, z, (long long)n, S, per_ray);
+    OCC_LAUNCH_CHECK("occ_compact_count_kernel");
+    hipLaunchKernelGGL(cscan_reduce_kernel, dim3(nb), dim3(256), 0, st, per_ray, (long long)n, sums);
+    OCC_LAUNCH_CHECK("cscan_reduce_kernel");
+    hipLaunchKernelGGL(cscan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, (int)nb, counts);
+    OCC_LAUNCH_CHECK("cscan_sums_kernel");
+    hipLaunchKernelGGL(cscan_apply_kernel, dim3(nb), dim3(256), 0, st, per_ray, (long long)n, sums);
+    OCC_LAUNCH_CHECK("cscan_apply_kernel");
+    hipLaunchKernelGGL(occ_compact_emit_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, st, G, bits, rays, z, (long long)n, S, per_ray, tile_rays, tile_z, tile_src,
+                       slot);
+    OCC_LAUNCH_CHECK("occ_compact_emit_kernel");
+    return MI_OCC_OK;
+}
+
 }  // namespace miocc
 
 using namespace miocc;
@@ -493,6 +691,41 @@ int mi_occ_mark(const mi_occ_grid* grid, const uint32_t* bits, const float* rays
     hipLaunchKernelGGL(occ_mark_kernel, dim3(blocks_for((long long)n_rays * S, 256)), dim3(256), 0, (hipStream_t)stream, G, bits, rays, z, (long long)n_rays * S, S,
                        mask);
     OCC_LAUNCH_CHECK("occ_mark_kernel");
+    return MI_OCC_OK;
+}
+
+size_t mi_occ_compact_scratch_bytes(int64_t n_rays) {
+    if (n_rays < 0 || n_rays >= (1LL << 26)) {
+        set_error("n_rays=%lld: 0 .. 2^26 - 1 rays (n_rays * 32 tile lanes stay below 2^31)", (long long)n_rays);
+        return 0;
+    }
+    return compact_scratch_bytes(n_rays);
+}
+
+int mi_occ_compact(const mi_occ_grid* grid, const uint32_t* bits, const float* rays, const float* z, int64_t n_rays, int S, float* tile_rays, float* tile_z,
+                   int32_t* tile_src, int32_t* slot, uint32_t* counts, void* scratch, size_t scratch_bytes, void* stream) {
+    return compact(grid, bits, rays, z, n_rays, S, tile_rays, tile_z, tile_src, slot, counts, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int mi_occ_scatter_raw(const float* tile_vals, const int32_t* slot, int64_t n_rays, int S, float* out, void* stream) {
+    if (int rc = check_tile_sizes(n_rays, S)) return rc;
+    if (n_rays == 0) return MI_OCC_OK;
+    OCC_CHECK_ARG(tile_vals && slot && out, "NULL pointer (tile_vals, slot and out are required)");
+    OCC_CHECK_ARG((((uintptr_t)tile_vals | (uintptr_t)out) & 15) == 0, "tile_vals and out must be 16-byte aligned");
+    const long long n_pts = (long long)n_rays * S;
+    hipLaunchKernelGGL(occ_scatter_kernel, dim3(blocks_for(n_pts, 256)), dim3(256), 0, (hipStream_t)stream, slot, (const float4*)tile_vals, n_pts, (float4*)out);
+    OCC_LAUNCH_CHECK("occ_scatter_kernel");
+    return MI_OCC_OK;
+}
+
+int mi_occ_gather_raw(const float* src, const int32_t* tile_src, int64_t n_tiles, float* out, void* stream) {
+    OCC_CHECK_ARG(n_tiles >= 0 && n_tiles * TILE < (1LL << 31), "n_tiles=%lld: n_tiles * 32 must stay below 2^31", (long long)n_tiles);
+    if (n_tiles == 0) return MI_OCC_OK;
+    OCC_CHECK_ARG(src && tile_src && out, "NULL pointer (src, tile_src and out are required)");
+    OCC_CHECK_ARG((((uintptr_t)src | (uintptr_t)out) & 15) == 0, "src and out must be 16-byte aligned");
+    const long long n_lanes = (long long)n_tiles * TILE;
+    hipLaunchKernelGGL(occ_gather_kernel, dim3(blocks_for(n_lanes, 256)), dim3(256), 0, (hipStream_t)stream, tile_src, (const float4*)src, n_lanes, (float4*)out);
+    OCC_LAUNCH_CHECK("occ_gather_kernel");
     return MI_OCC_OK;
 }
 

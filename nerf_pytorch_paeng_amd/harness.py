@@ -470,7 +470,10 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
     ``opts.idx_save`` steps when ``log_dir`` is given (train.py:105-114).  ``vis`` (visdom) is accepted and unused.
     Returns the losses and PSNRs as 0-dim device tensors (no host synchronisation).  With ``opts.precision == "f16s"`` the dict also
     carries ``f16s`` = train_path.f16s_status(model) every ``opts.idx_print`` steps (one device -> host read): the share of the f16 range
-    the scaled backward used and the packer's out-of-range count; the training path itself raises when either says a step was clipped."""
+    the scaled backward used and the packer's out-of-range count; the training path itself raises when either says a step was clipped.
+    ``opts.train_occupancy`` (absent = None): an occupancy.OccupancyGrid the step skips empty space with (occupancy_train.py);
+    ``opts.occupancy_rebake_every`` (absent = 0: never): the grid is re-baked from the model, under no_grad and with its bake defaults,
+    before every step whose ``idx`` is a multiple of it."""
     model.train()
     img_h, img_w = hw
     gt_intrinsic, gt_extrinsic = gt_cam_param
@@ -484,8 +487,13 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
         target_full = as_f32_dev(torch.as_tensor(images[i_img]), dev)
         pose = torch.as_tensor(np.asarray(gt_extrinsic[i_img]) if not isinstance(gt_extrinsic, torch.Tensor) else gt_extrinsic[i_img])
         rays_o, rays_d, target_img = sample_rays_and_pixel(idx, img_w, img_h, gt_intrinsic, pose[:3, :4], target_full, opts, generator)
+    train_grid = getattr(opts, "train_occupancy", None)
+    rebake = int(getattr(opts, "occupancy_rebake_every", 0) or 0)
+    if train_grid is not None and rebake > 0 and idx % rebake == 0:
+        with torch.no_grad():
+            train_grid.bake(model, **getattr(opts, "occupancy_bake_args", {}))
     rgb_c, _, rgb_f, _ = NP.batchify_rays_and_render_by_chunk(rays_o.contiguous(), rays_d.contiguous(), model, posenc, img_h, img_w,
-                                                              gt_intrinsic, opts, **_precision(opts))      # train.py:53
+                                                              gt_intrinsic, opts, **_precision(opts), train_occupancy=train_grid)      # train.py:53
     optimizer.zero_grad()
     target_img = target_img.contiguous()
     loss = criterion(rgb_c, target_img)                                                       # train.py:60

@@ -4,7 +4,8 @@ Same function names, positional arguments and return structures as the reference
 (``batchify_rays_and_render_by_chunk``, ``render_rays``, ``pre_process``, ``post_process``,
 ``sample_pdf``, ``ndc_rays``), executed by hand-written HIP kernels through ``libmi_nerf.so``.
 Keyword-only extras (``t_rand=``, ``u=``, ``seed=``, ``ray_offset=``) make the randomness explicit;
-``occupancy=`` (an ``occupancy.OccupancyGrid``) skips the networks at samples the grid marks empty (inference only):
+``occupancy=`` (an ``occupancy.OccupancyGrid``) skips the networks at samples the grid marks empty (inference only;
+``train_occupancy=`` is the same grid for the training path, occupancy_train.py):
 the reference draws unseeded ``torch.rand`` (nerf_process.py:58-60,162-163); here the default is a
 counter-based generator keyed on (seed, global ray index, sample index), so a frame renders
 identically however its rays are chunked or sharded across GPUs.
@@ -28,6 +29,7 @@ from ._lib import MiNerfError, as_f32_dev
 from .weights import PackedNeRF, packed_for
 from . import train_path
 from . import occupancy as occ
+from . import occupancy_train
 
 # rays handed to one mi_nerf_render_rays call (workspace: 5.4 KB/ray at 64+128 samples -> ~5.6 GB)
 MAX_RAYS_PER_LAUNCH = 1 << 20
@@ -192,12 +194,28 @@ def _occupancy_arg(occupancy, training: bool, prec: ops.Precision):
     if occupancy is None:
         return None
     if training:
-        raise MiNerfError("occupancy= is an inference feature: training with a grid is not supported (call under torch.no_grad(), or freeze the model)")
+        raise MiNerfError("occupancy= is an inference feature (call under torch.no_grad(), or freeze the model); to train with a grid pass it as "
+                          "train_occupancy=")
     if not isinstance(occupancy, occ.OccupancyGrid):
         raise MiNerfError(f"occupancy must be an occupancy.OccupancyGrid, got {type(occupancy).__name__}")
     occ.check_precision(prec)
     occupancy.last_stats = None
     return occupancy
+
+
+def _train_occupancy_arg(grid, training: bool, prec: ops.Precision):
+    """``train_occupancy=``: None, or an OccupancyGrid for the training path (occupancy_train.py) -- gradients enabled, fp32 or f16s."""
+    if grid is None:
+        return None
+    if not isinstance(grid, occ.OccupancyGrid):
+        raise MiNerfError(f"train_occupancy must be an occupancy.OccupancyGrid, got {type(grid).__name__}")
+    if not training:
+        raise MiNerfError("train_occupancy= is a training feature: gradients are disabled or no parameter of the model requires them "
+                          "(under torch.no_grad() render with occupancy=)")
+    if prec.coarse != prec.fine or prec.fine not in ("fp32", "f16s"):
+        raise MiNerfError(f"training with a grid runs fp32 or f16s for both networks (got coarse {prec.coarse}, fine {prec.fine})")
+    grid.last_stats = None
+    return grid
 
 
 def _train_f16s(prec: ops.Precision, intermediates: bool = False) -> bool:
@@ -209,17 +227,22 @@ def _train_f16s(prec: ops.Precision, intermediates: bool = False) -> bool:
 
 def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ray_offset: int = 0, bf16: bool = False,
                 return_intermediates: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False,
-                occupancy=None):
+                occupancy=None, train_occupancy=None):
     """Coarse pass -> composite -> resample -> fine pass (nerf_process.py:185-216) as one fused launch
     sequence.  Returns ``{'rgb_c','disp_c'[,'rgb_f','disp_f']}``.  ``bf16`` / ``f16s`` / ``coarse_f16s`` / ``f16`` / ``coarse_f16`` select
     the networks' precision mode (ops.precision(); fp32 MFMA by default).  With gradients: fp32 or f16s.  ``occupancy``: an OccupancyGrid
-    (occupancy.py) -- the networks skip the samples it marks empty; ``return_intermediates`` then also returns ``_occ_stats``."""
+    (occupancy.py) -- the networks skip the samples it marks empty; ``return_intermediates`` then also returns ``_occ_stats``.
+    ``train_occupancy``: the same for the training path (gradients enabled; fp32 or f16s); the counts are in the grid's ``last_stats``."""
     prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
     occupancy = _occupancy_arg(occupancy, train_path.wants_grad(model), prec)
+    train_occupancy = _train_occupancy_arg(train_occupancy, train_path.wants_grad(model), prec)
     if train_path.wants_grad(model):
         train_f16s = _train_f16s(prec, return_intermediates)
         if rays.dim() != 2 or rays.shape[1] != 6:
             raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
+        if train_occupancy is not None:
+            return occupancy_train.render_train(rays, model, opts, train_occupancy, t_rand=t_rand, u=u, seed=_next_seed(seed),
+                                                ray_offset=int(ray_offset), f16s=train_f16s)
         return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=_next_seed(seed), ray_offset=int(ray_offset), f16s=train_f16s)
     packed = packed_for(model)
     rays = as_f32_dev(rays, packed.device)
@@ -232,17 +255,19 @@ def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ra
 
 def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts, *, t_rand=None, u=None, seed=None,
                                       ray_offset: int = 0, bf16: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False,
-                                      coarse_f16: bool = False, occupancy=None):
+                                      coarse_f16: bool = False, occupancy=None, train_occupancy=None):
     """Drop-in entry point (nerf_process.py:220-252): flatten, optional NDC warp for llff, render.
     Returns ``(rgb_c [N,3], disp_c [N], rgb_f [N,3] | None, disp_f [N] | None)``.
 
     ``opts.chunk_rays`` bounded the reference's activation memory; the fused kernels keep activations in
     registers, so rays are launched in slabs of up to MAX_RAYS_PER_LAUNCH.  The result does not depend on
     the slab size because the jitter is keyed on the global ray index (``ray_offset`` + position).
-    ``occupancy``: an OccupancyGrid (occupancy.py); its ``last_stats`` then holds the sample counts of this call."""
+    ``occupancy``: an OccupancyGrid (occupancy.py); its ``last_stats`` then holds the sample counts of this call.  ``train_occupancy``: the
+    same for the training path (occupancy_train.py)."""
     prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
     training = train_path.wants_grad(model)
     occupancy = _occupancy_arg(occupancy, training, prec)
+    train_occupancy = _train_occupancy_arg(train_occupancy, training, prec)
     train_f16s = _train_f16s(prec) if training else False
     packed = None if training else packed_for(model)
     dev = next(model.parameters()).device if training else packed.device
@@ -259,15 +284,22 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
     seed = _next_seed(seed)
     Nf = int(opts.N_samples_f)
     parts = []
+    train_stats = None
     slab = train_path.MAX_TRAIN_RAYS if training else (MAX_RAYS_PER_LAUNCH if occupancy is None else occ.MAX_RAYS_PER_LAUNCH)
     for i in range(0, N, slab):
         j = min(N, i + slab)
         tr, uu = (None if t_rand is None else t_rand[i:j]), (None if u is None else u[i:j])
-        if training:                                                # train.py:53-54: one autograd node per slab
+        if train_occupancy is not None:
+            parts.append(occupancy_train.render_train(rays[i:j].contiguous(), model, opts, train_occupancy, t_rand=tr, u=uu, seed=seed,
+                                                      ray_offset=int(ray_offset) + i, f16s=train_f16s))
+            train_stats = occ.add_stats(train_stats, train_occupancy.last_stats)
+        elif training:                                              # train.py:53-54: one autograd node per slab
             parts.append(train_path.render_train(rays[i:j].contiguous(), model, opts, t_rand=tr, u=uu, seed=seed,
                                                  ray_offset=int(ray_offset) + i, f16s=train_f16s))
         else:
             parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False, occupancy))
+    if train_occupancy is not None:
+        train_occupancy.last_stats = train_stats
     def cat(key):
         return parts[0][key] if len(parts) == 1 else torch.cat([p[key] for p in parts], dim=0)
     if Nf > 0:

@@ -5,8 +5,11 @@
     out = nerf_process.render_rays(rays, model, posenc, opts, occupancy=grid)
 
 A skipped sample's raw output is (0, 0, 0, 0), which ``post_process`` turns into weight 0 exactly: the render is the staged reference path
-with raw zeroed where ``grid.mark(rays, z)`` is 0.  Inference only (``torch.no_grad()``); fp32, ``f16s`` and ``bf16``.  The render call
-synchronises its stream once per network pass (the tile count goes to the host) and cannot be captured into a graph.
+with raw zeroed where ``grid.mark(rays, z)`` is 0.  ``occupancy=`` is inference only (``torch.no_grad()``); fp32, ``f16s`` and ``bf16``.  The
+render call synchronises its stream once per network pass (the tile count goes to the host) and cannot be captured into a graph.
+
+Training with a grid (``train_occupancy=``, occupancy_train.py) is composed in Python from the deterministic compaction
+(``OccupancyGrid.compact``, mi_occ_compact) and the two data movements around the networks (``scatter_raw``, ``gather_raw``).
 """
 from __future__ import annotations
 
@@ -84,6 +87,7 @@ class OccupancyGrid:
         self.lo, self.hi, self.res = _triple(lo, float), _triple(hi, float), _triple(res, int)
         self.outside_occupied = bool(outside_occupied)
         self.bits: Optional[torch.Tensor] = None          # int32 [words] on the device: the uint32 words of the header
+        self.bits_fine: Optional[torch.Tensor] = None     # a bitfield of its own for the fine network in compact() (None: the grid's bits)
         self.last_stats: Optional[Dict[str, int]] = None  # mi_occ_stats of the last render_rays / batchify call that used this grid (summed over slabs)
         self.words = int(_occ.lib().mi_occ_grid_words(C.byref(self.c_grid())))
         if self.words == 0:
@@ -113,6 +117,8 @@ class OccupancyGrid:
     def to(self, device) -> "OccupancyGrid":
         if self.bits is not None:
             self.bits = self.bits.to(device)
+        if self.bits_fine is not None:
+            self.bits_fine = self.bits_fine.to(device)
         return self
 
     # ---- baking ------------------------------------------------------------------------------------
@@ -180,6 +186,42 @@ class OccupancyGrid:
                                               dev_ptr(mask, "mask", torch.uint8, 1), stream_ptr(bits.device)), "mi_occ_mark")
         return mask
 
+    # ---- deterministic compaction (the training path) ----------------------------------------------
+    def compact(self, rays: torch.Tensor, z: torch.Tensor, network: str = "coarse") -> Dict[str, object]:
+        """mi_occ_compact: the surviving samples of rays [n,6] / z [n,S] as 32-sample tiles in a reproducible order (THE COMPACTION RULE of
+        the header).  ``network``: "coarse" or "fine" -- the fine network reads ``bits_fine`` when the grid has one, else the grid's bits.
+        Returns {"tile_rays" [T,6], "tile_z" [T,32], "tile_src" int32 [T,32], "slot" int32 [n,S], "tiles": T, "survivors": sum k_r}; the tile
+        tensors are views of the first T tiles.  ONE 8-byte device -> host read (the two counts): the only synchronisation of the pass."""
+        if network not in ("coarse", "fine"):
+            raise MiNerfError(f"network must be 'coarse' or 'fine', got {network!r}")
+        bits = self._need_bits()
+        if network == "fine" and self.bits_fine is not None:
+            bits = self.bits_fine
+        dev = bits.device
+        rays, z = as_f32_dev(rays, dev), as_f32_dev(z, dev)
+        if z.dim() != 2 or tuple(rays.shape) != (z.shape[0], 6):
+            raise MiNerfError(f"rays [n,6] / z [n,S] expected, got {tuple(rays.shape)} / {tuple(z.shape)}")
+        n, S = z.shape
+        L = _occ.lib()
+        nbytes = int(L.mi_occ_compact_scratch_bytes(n))
+        if nbytes == 0:
+            raise MiNerfError(f"mi_occ_compact refused: {_occ.last_error()}")
+        T = n * ((S + _occ.TILE - 1) // _occ.TILE)
+        tile_rays = torch.empty(T, 6, dtype=torch.float32, device=dev)
+        tile_z = torch.empty(T, _occ.TILE, dtype=torch.float32, device=dev)
+        tile_src = torch.empty(T, _occ.TILE, dtype=torch.int32, device=dev)
+        slot = torch.empty(n, S, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with ops._guard(dev):
+            _occ.check(L.mi_occ_compact(C.byref(self.c_grid()), dev_ptr(bits, "bits", torch.int32), dev_ptr(rays, "rays"), dev_ptr(z, "z"), n, S,
+                                        dev_ptr(tile_rays, "tile_rays"), dev_ptr(tile_z, "tile_z"), dev_ptr(tile_src, "tile_src", torch.int32),
+                                        dev_ptr(slot, "slot", torch.int32), dev_ptr(counts, "counts", torch.int32),
+                                        dev_ptr(scratch, "scratch", torch.uint8, 256), nbytes, stream_ptr(dev)), "mi_occ_compact")
+        tiles, survivors = (int(v) for v in counts.cpu().tolist())
+        return {"tile_rays": tile_rays[:tiles], "tile_z": tile_z[:tiles], "tile_src": tile_src[:tiles], "slot": slot, "tiles": tiles,
+                "survivors": survivors}
+
     # ---- persistence -------------------------------------------------------------------------------
     def save(self, path: str) -> None:
         """npz: lo, hi, res, outside_occupied and the uint32 words."""
@@ -225,6 +267,46 @@ def render_rays(net: Net, packed_c: torch.Tensor, packed_f: Optional[torch.Tenso
             dev_ptr(workspace, "workspace", torch.uint8, 256), workspace.numel(), dev_ptr(rgb_c), dev_ptr(disp_c), dev_ptr(rgb_f), dev_ptr(disp_f),
             C.byref(st), stream_ptr(dev)), "mi_occ_render_rays")
     return rgb_c, disp_c, rgb_f, disp_f, workspace, {k: int(getattr(st, k)) for k, _ in Stats._fields_}
+
+
+def _out_buffer(out: Optional[torch.Tensor], shape, dev) -> torch.Tensor:
+    if out is None:
+        return torch.empty(*shape, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise MiNerfError(f"out must be a contiguous float32 {tuple(shape)} tensor on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    return out
+
+
+def scatter_raw(tile_vals: torch.Tensor, slot: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mi_occ_scatter_raw: tile_vals [T,32,4], slot int32 [n,S] -> [n,S,4]; every element written, zeros where ``slot`` is -1.  ``out``: a
+    buffer to write into (every element of it is overwritten)."""
+    dev = slot.device
+    if slot.dim() != 2 or slot.dtype != torch.int32 or tile_vals.dim() != 3 or tuple(tile_vals.shape[1:]) != (_occ.TILE, 4):
+        raise MiNerfError(f"tile_vals [T,32,4] / slot int32 [n,S] expected, got {tuple(tile_vals.shape)} / {tuple(slot.shape)} {slot.dtype}")
+    n, S = slot.shape
+    if tile_vals.shape[0] == 0:
+        tile_vals = torch.zeros(1, _occ.TILE, 4, dtype=torch.float32, device=dev)       # nothing survived: no lane is read, every output is zero
+    tile_vals = as_f32_dev(tile_vals, dev)
+    out = _out_buffer(out, (n, S, 4), dev)
+    with ops._guard(dev):
+        _occ.check(_occ.lib().mi_occ_scatter_raw(dev_ptr(tile_vals, "tile_vals", align=16), dev_ptr(slot.contiguous(), "slot", torch.int32), n, S,
+                                                 dev_ptr(out, "out", align=16), stream_ptr(dev)), "mi_occ_scatter_raw")
+    return out
+
+
+def gather_raw(src: torch.Tensor, tile_src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mi_occ_gather_raw: src [n,S,4], tile_src int32 [T,32] -> [T,32,4] = src[tile_src] per lane, exact zeros on padding lanes (-1).
+    ``out``: a buffer to write into (every element of it is overwritten)."""
+    dev = tile_src.device
+    if tile_src.dim() != 2 or tile_src.shape[1] != _occ.TILE or tile_src.dtype != torch.int32 or src.dim() != 3 or src.shape[2] != 4:
+        raise MiNerfError(f"src [n,S,4] / tile_src int32 [T,32] expected, got {tuple(src.shape)} / {tuple(tile_src.shape)} {tile_src.dtype}")
+    src = as_f32_dev(src, dev)
+    T = tile_src.shape[0]
+    out = _out_buffer(out, (T, _occ.TILE, 4), dev)
+    with ops._guard(dev):
+        _occ.check(_occ.lib().mi_occ_gather_raw(dev_ptr(src, "src", align=16), dev_ptr(tile_src.contiguous(), "tile_src", torch.int32), T,
+                                                dev_ptr(out, "out", align=16), stream_ptr(dev)), "mi_occ_gather_raw")
+    return out
 
 
 def add_stats(a: Optional[Dict[str, int]], b: Dict[str, int]) -> Dict[str, int]:

@@ -1,0 +1,460 @@
+"""Training with an occupancy grid on the GPU (occupancy_train.py; mi_occ_compact / mi_occ_scatter_raw / mi_occ_gather_raw of
+include/mi_nerf_occ.h).  The compaction equals the numpy restatement of tests/test_occ_train_cpu.py bit for bit, in order; the forward is the
+MASKED IDENTITY of the inference path (the staged chain over all samples with raw zeroed where mi_occ_mark answers 0); the gradients are held
+against the float64 restatements with the EXISTING masked GPU path as the yardstick (e_new <= max(3 e_existing, 2e-5), the form
+tests/test_gpu_train.py uses against fixture F11); and a scene trains with the grid to the held-out PSNR of the full path, within the spread
+that the jitter seed alone produces.
+
+Measured on the first GPU run (docs/design/17_occupancy_training.md, section 17.5): see BIT_EXACT and ALL_ONES_BIT_EXACT below."""
+import copy
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from nerf_pytorch_paeng_amd import harness, ops, scenes, synthetic, train_path, weights
+from nerf_pytorch_paeng_amd import nerf_process as NP
+from nerf_pytorch_paeng_amd import occupancy as OC
+from nerf_pytorch_paeng_amd import occupancy_train as OT
+from nerf_pytorch_paeng_amd.model import NeRF, get_positional_encoder
+from oracle import restate as R
+from tests.test_occ_cpu import cell_rule
+from tests.test_occ_train_cpu import HAND_BITS, HAND_GRID, compaction_rule, hand_made, hand_mask
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+PARITY_BAR = 2e-5
+# Families whose forward masked identity holds bit for bit (each lane of the stash-forward kernels evaluates its own point, whatever tile it
+# sits in).  A family found otherwise is held to the parity bar 2e-5 instead and recorded in docs/design/17_occupancy_training.md.
+BIT_EXACT = {"fp32": True, "f16s": True}
+# An all-ones grid at S a multiple of 32 compacts every ray into its own samples in order: the pseudo-ray batch IS the full batch, point for
+# point.  Observed difference from train_path.render_train: zero, results and gradients.
+ALL_ONES_BIT_EXACT = True
+NETS = {"fp32": (4, 128), "f16s": (8, 256)}
+
+
+def lego_rays(n, seed=0):
+    K, H, W = synthetic.lego_camera()
+    pose = synthetic.pose_spherical(0.0, -30.0, 4.0)
+    pix = torch.from_numpy(synthetic.pixel_batch(H, W, n, seed)).to(DEV)
+    o, d = ops.make_o_d_pixels(W, H, K, pose, pix)
+    return torch.cat([o, d], -1).contiguous()
+
+
+def random_grid(res=(32, 32, 32), lo=-2.5, hi=2.5, outside=True, seed=0, p=0.5):
+    g = OC.OccupancyGrid(lo, hi, res, outside_occupied=outside)
+    cells = np.random.RandomState(seed).rand(g.words * 32) < p
+    cells[g.cells:] = False
+    return g.set_bits(np.packbits(cells, bitorder="little").view(np.uint32)).to(DEV)
+
+
+def constant_grid(value: bool, outside: bool):
+    g = OC.OccupancyGrid(-1.5, 1.5, 16, outside_occupied=outside)
+    return g.set_bits(np.full(g.words, 0xFFFFFFFF if value else 0, np.uint32)).to(DEV)
+
+
+def make_model(D, W, seed=0):
+    sd = synthetic.make_state_dict(seed, D, W)
+    model = NeRF(D, W, 63, 27).to(DEV)
+    model.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+    return sd, model
+
+
+def make_opts(Sc, Nf):
+    return SimpleNamespace(near=2.0, far=6.0, N_samples_c=Sc, N_samples_f=Nf, perturb=1.0, chunk_rays=4096, chunk_pts=524288, data_type="blender",
+                           gpu_ids=[0], rank=0)
+
+
+def grads_of(model):
+    """name -> gradient of every parameter that has one (without a fine pass the fine network has none, on either path)."""
+    return {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
+
+
+def mse2(out, tgt):
+    loss = torch.mean((out["rgb_c"] - tgt) ** 2)
+    return loss + torch.mean((out["rgb_f"] - tgt) ** 2) if "rgb_f" in out else loss
+
+
+# ---------------------------------------------------------------------------------------------------
+# 1. the compaction equals the restatement bit for bit
+# ---------------------------------------------------------------------------------------------------
+def _check_compaction(grid, rays, z, mask_np):
+    got = grid.compact(rays, z)
+    again = grid.compact(rays, z)
+    want = compaction_rule(mask_np, rays.cpu().numpy(), z.cpu().numpy())
+    assert (got["tiles"], got["survivors"]) == want["counts"]
+    for k in ("tile_rays", "tile_z", "tile_src", "slot"):
+        g = got[k].cpu().numpy()
+        assert g.shape == want[k].shape and g.dtype == want[k].dtype, (k, g.shape, want[k].shape)
+        assert np.array_equal(g.view(np.uint32), want[k].view(np.uint32)), k        # bits, not values: in order, not up to a permutation
+        assert np.array_equal(again[k].cpu().numpy().view(np.uint32), g.view(np.uint32)), k          # two calls give identical bytes
+    # slot, tile_src and mi_occ_mark agree with each other
+    mark = grid.mark(rays, z).cpu().numpy().astype(bool)
+    assert np.array_equal(mark, mask_np)
+    slot, src = got["slot"].cpu().numpy(), got["tile_src"].cpu().numpy().reshape(-1)
+    assert np.array_equal(slot >= 0, mark)
+    assert np.array_equal(np.sort(src[src >= 0]), np.nonzero(mark.reshape(-1))[0])
+    assert np.array_equal(slot.reshape(-1)[src[src >= 0]], np.nonzero(src >= 0)[0])
+    return got
+
+
+@pytest.mark.parametrize("n,S,seed", [(1, 64, 4), (7, 64, 0), (257, 64, 1), (1, 40, 3), (5, 40, 0), (257, 40, 2), (2051, 40, 5)])
+def test_compaction_equals_the_restatement_on_hand_made_rays(n, S, seed):
+    """Survivor counts {0, 1, 31, 32, 33, 63, 64} at S = 64 and {0, 1, 32, 33, 40} at S = 40; 2051 rays are more than two blocks of the scan."""
+    rays, z, counts = hand_made(n, S, seed)
+    grid = OC.OccupancyGrid(HAND_GRID["lo"], HAND_GRID["hi"], HAND_GRID["res"], outside_occupied=False).set_bits(HAND_BITS).to(DEV)
+    mask = hand_mask(rays, z)
+    assert mask.sum(1).tolist() == counts
+    got = _check_compaction(grid, torch.from_numpy(rays).to(DEV), torch.from_numpy(z).to(DEV), mask)
+    assert got["survivors"] == sum(counts) and got["tiles"] == sum((k + 31) // 32 for k in counts)
+
+
+@pytest.mark.parametrize("outside", [True, False])
+def test_compaction_equals_the_restatement_on_lego_rays(outside):
+    rays = lego_rays(256)
+    z = ops.stratified_z(2.0, 6.0, torch.rand(256, 64, generator=torch.Generator().manual_seed(3)).to(DEV))
+    grid = random_grid(outside=outside, seed=1)
+    mask = cell_rule(grid.lo, grid.hi, grid.res, outside, grid.bits.cpu().numpy().view(np.uint32), rays.cpu().numpy(), z.cpu().numpy())
+    got = _check_compaction(grid, rays, z, mask)
+    share = got["survivors"] / mask.size
+    print(f"\n[compact lego outside_occupied={outside}] evaluated share {share:.3f}, tiles {got['tiles']}")
+    assert 0.05 < share < 0.95
+
+
+def test_compaction_of_no_rays():
+    grid = random_grid()
+    got = grid.compact(torch.empty(0, 6, device=DEV), torch.empty(0, 64, device=DEV))
+    assert (got["tiles"], got["survivors"]) == (0, 0) and got["slot"].shape == (0, 64) and got["tile_src"].shape == (0, 32)
+
+
+# ---------------------------------------------------------------------------------------------------
+# 2. scatter_raw and gather_raw equal numpy indexing exactly
+# ---------------------------------------------------------------------------------------------------
+def test_scatter_and_gather_equal_numpy_indexing():
+    n, S = 257, 40
+    rays, z, _ = hand_made(n, S, 2)
+    grid = OC.OccupancyGrid(HAND_GRID["lo"], HAND_GRID["hi"], HAND_GRID["res"], outside_occupied=False).set_bits(HAND_BITS).to(DEV)
+    c = grid.compact(torch.from_numpy(rays).to(DEV), torch.from_numpy(z).to(DEV))
+    T = c["tiles"]
+    slot, src = c["slot"].cpu().numpy(), c["tile_src"].cpu().numpy()
+    vals = torch.randn(T, 32, 4, generator=torch.Generator().manual_seed(0))
+    poisoned = torch.full((n, S, 4), float("nan"), device=DEV)       # every element is written: no NaN is left
+    out = OC.scatter_raw(vals.to(DEV), c["slot"], out=poisoned).cpu().numpy()
+    want = np.where((slot >= 0)[..., None], vals.numpy().reshape(-1, 4)[np.maximum(slot, 0)], np.float32(0.0))
+    assert np.array_equal(out.view(np.uint32), want.view(np.uint32))                 # exact zeros (+0.0) at the skipped samples
+    # gather after scatter returns the tile values on real lanes, exact zeros on padding lanes
+    back = OC.gather_raw(torch.from_numpy(out).to(DEV), c["tile_src"], out=torch.full((T, 32, 4), float("nan"), device=DEV)).cpu().numpy()
+    real = src >= 0
+    assert np.array_equal(back[real], vals.numpy()[real]) and np.array_equal(back[~real].view(np.uint32), np.zeros_like(back[~real]).view(np.uint32))
+    assert real.sum() < real.size                                                    # the case has padding lanes
+    # gather from a NaN-filled source: padding lanes still read exact zeros, real lanes read src[tile_src]
+    nan_src = torch.full((n, S, 4), float("nan"), device=DEV)
+    g = OC.gather_raw(nan_src, c["tile_src"]).cpu().numpy()
+    assert np.isnan(g[real]).all() and np.array_equal(g[~real].view(np.uint32), np.zeros_like(g[~real]).view(np.uint32))
+    d = torch.randn(n, S, 4, generator=torch.Generator().manual_seed(1))
+    g = OC.gather_raw(d.to(DEV), c["tile_src"]).cpu().numpy()
+    want = np.where(real[..., None], d.numpy().reshape(-1, 4)[np.maximum(src, 0)], np.float32(0.0))
+    assert np.array_equal(g.view(np.uint32), want.view(np.uint32))
+    # nothing survived: every output is zero, no tile is read
+    none = OC.scatter_raw(torch.empty(0, 32, 4, device=DEV), torch.full((5, 40), -1, dtype=torch.int32, device=DEV))
+    assert none.shape == (5, 40, 4) and float(none.abs().max()) == 0.0
+    assert OC.gather_raw(d.to(DEV), torch.empty(0, 32, dtype=torch.int32, device=DEV)).shape == (0, 32, 4)
+
+
+# ---------------------------------------------------------------------------------------------------
+# 3. / 4. forward masked identity, gradients against a measured comparator -- one batch, computed once per family
+# ---------------------------------------------------------------------------------------------------
+def _existing_masked_path(model, f16s, rays, z, mask, prefix_module):
+    """The code from before this change with the mask applied by hand: full mlp_rays_train -> raw zeroed -> composite; composite_backward ->
+    d_raw zeroed at skipped samples -> mlp_backward.  Returns a closure for the backward and the forward results."""
+    st = train_path._state_for(model, f16s)
+    net = st.net
+    flat = st.flat(st.params(prefix_module))
+    blob = ops.pack_apply(st.map_fwd, flat)
+    if f16s:
+        raw, stash = ops.mlp_rays_train(net, ops.pack_apply_f16s(net, st.map_f16s(), flat, st.f16s_out_of_range), rays, z, f16s=True)
+    else:
+        raw, stash = ops.mlp_rays_train(net, blob, rays, z)
+    m = mask.bool()[..., None]
+    raw = torch.where(m, raw, torch.zeros_like(raw))
+    rgb, disp, _, wts, _ = ops.composite(raw, z, rays, want_all=True)
+
+    def backward(g_rgb):
+        split = f16s and net.W == 256
+        dgrad = split and net.D <= 15
+        blob_b = ops.pack_apply_f16s(net, st.map_bwd_f16s(), flat, st.f16s_out_of_range, backward=True) if dgrad else ops.pack_apply(st.map_bwd, flat)
+        d_raw = ops.composite_backward(raw, z, rays, g_rgb.contiguous())
+        d_raw = torch.where(m, d_raw, torch.zeros_like(d_raw))
+        grads, _ = ops.mlp_backward(net, blob, blob_b, rays, z, d_raw, stash, f16s_wgrad=split, f16s_dgrad=dgrad)
+        return dict(zip(st.names, st.split_grads(grads)))
+    return SimpleNamespace(rgb=rgb, disp=disp, weights=wts, backward=backward)
+
+
+@pytest.fixture(scope="module", params=sorted(NETS))
+def batch(request):
+    family = request.param
+    f16s = family == "f16s"
+    D, W = NETS[family]
+    n, Sc, Nf = 128, 64, 64
+    sd, model = make_model(D, W)
+    opts = make_opts(Sc, Nf)
+    rays = lego_rays(n)
+    g = torch.Generator().manual_seed(11)
+    t_rand, u, tgt = torch.rand(n, Sc, generator=g).to(DEV), torch.rand(n, Nf, generator=g).to(DEV), torch.rand(n, 3, generator=g).to(DEV)
+    grid = random_grid(seed=5)
+    # (b) the existing path with the mask applied
+    z_c = ops.stratified_z(2.0, 6.0, t_rand)
+    mask_c = grid.mark(rays, z_c)
+    bc = _existing_masked_path(model, f16s, rays, z_c, mask_c, model.model_coarse)
+    z_f = ops.fine_z(z_c, bc.weights, Nf, False, u)
+    mask_f = grid.mark(rays, z_f)
+    bf = _existing_masked_path(model, f16s, rays, z_f, mask_f, model.model_fine)
+    leaf_c, leaf_f = bc.rgb.clone().requires_grad_(True), bf.rgb.clone().requires_grad_(True)
+    g_c, g_f = torch.autograd.grad(mse2({"rgb_c": leaf_c, "rgb_f": leaf_f}, tgt), [leaf_c, leaf_f])
+    grads_b = {"model_coarse." + k: v for k, v in bc.backward(g_c).items()}
+    grads_b.update({"model_fine." + k: v for k, v in bf.backward(g_f).items()})
+    # (c) the new path: once as a user calls it (the forward identity), once with the depths pinned (the gradients)
+    free = OT.render_train(rays, model, opts, grid, t_rand=t_rand, u=u, f16s=f16s)
+    free = {k: v.detach().clone() for k, v in free.items()}
+    stats = dict(grid.last_stats)
+    model.zero_grad(set_to_none=True)
+    out = OT.render_train(rays, model, opts, grid, t_rand=t_rand, u=u, z_override=(z_c, z_f), f16s=f16s)
+    mse2(out, tgt).backward()
+    grads_c = grads_of(model)
+    model.zero_grad(set_to_none=True)
+    return SimpleNamespace(family=family, f16s=f16s, D=D, W=W, n=n, Sc=Sc, Nf=Nf, sd=sd, model=model, opts=opts, rays=rays, t_rand=t_rand, u=u, tgt=tgt,
+                           grid=grid, z_c=z_c, z_f=z_f, mask_c=mask_c, mask_f=mask_f, bc=bc, bf=bf, grads_b=grads_b, free=free, stats=stats,
+                           grads_c=grads_c)
+
+
+def test_forward_masked_identity(batch):
+    b = batch
+    print()
+    bad = []
+    for what, got, want in (("rgb_c", b.free["rgb_c"], b.bc.rgb), ("disp_c", b.free["disp_c"], b.bc.disp), ("rgb_f", b.free["rgb_f"], b.bf.rgb),
+                            ("disp_f", b.free["disp_f"], b.bf.disp)):
+        diff, err = int((got != want).sum()), float((got - want).abs().max())
+        print(f"[{b.family}] {what}: {diff} of {got.numel()} values differ, max |diff| {err:.3e}")
+        if not (diff == 0 if BIT_EXACT[b.family] else err <= PARITY_BAR):
+            bad.append((what, diff, err))
+    assert bad == []                                                 # every figure is printed above before this
+    s = b.stats
+    assert (s["total_c"], s["total_f"]) == (b.n * b.Sc, b.n * (b.Sc + b.Nf))
+    assert (s["evaluated_c"], s["evaluated_f"]) == (int(b.mask_c.sum()), int(b.mask_f.sum()))
+    assert (s["evaluated_c"] + s["padded_c"]) % 32 == 0 and (s["evaluated_f"] + s["padded_f"]) % 32 == 0 and 0 <= s["padded_c"] < 32 * b.n
+    assert 0 < s["evaluated_c"] < s["total_c"] and 0 < s["evaluated_f"] < s["total_f"]
+
+
+def test_gradients_against_the_existing_masked_path_as_comparator(batch):
+    """(a) oracle/restate.py in float64 (network, raw * mask, post_process, MSE(rgb_c) + MSE(rgb_f), autograd) with the depths pinned to the GPU's;
+    (b) the existing GPU path with the mask applied; (c) the new path.  Per parameter tensor, relative to the tensor's largest entry:
+    e_c <= max(3 e_b, 2e-5).  No ray and no tensor is left out."""
+    b = batch
+    rays = b.rays.cpu()
+    psd = {k: torch.as_tensor(v).clone().float().requires_grad_(True) for k, v in b.sd.items()}
+    tgt = b.tgt.cpu().double()
+
+    def oracle(prefix, z, mask):
+        z = z.cpu()
+        raw = R.mlp_forward(psd, prefix, R.embed(rays, z, 10, 4), b.D, 63, 27, dtype=torch.float64).reshape(b.n, z.shape[1], 4)
+        raw = raw * mask.cpu().double()[..., None]
+        return R.post_process(raw, z.double(), rays[:, 3:].double())[0]
+
+    loss = torch.mean((oracle("model_coarse.", b.z_c, b.mask_c) - tgt) ** 2) + torch.mean((oracle("model_fine.", b.z_f, b.mask_f) - tgt) ** 2)
+    loss.backward()
+    print()
+    worst_b = worst_c = 0.0
+    bad, count = [], 0
+    for k, _ in b.model.named_parameters():
+        want = psd[k].grad.double()
+        scale = float(want.abs().max())
+        assert scale > 0.0, k
+        e_b = float((b.grads_b[k].cpu().double() - want).abs().max()) / scale
+        e_c = float((b.grads_c[k].cpu().double() - want).abs().max()) / scale
+        worst_b, worst_c = max(worst_b, e_b), max(worst_c, e_c)
+        print(f"[{b.family}] {k}: existing masked path {e_b:.2e}, new path {e_c:.2e}")
+        if not e_c <= max(3.0 * e_b, PARITY_BAR):
+            bad.append((k, e_c, e_b))
+        count += 1
+    print(f"[{b.family}] worst per-tensor gradient error vs float64: existing masked path {worst_b:.2e}, new path {worst_c:.2e}")
+    assert count == 2 * (2 * b.D + 8)
+    assert bad == []
+
+
+# ---------------------------------------------------------------------------------------------------
+# 5. edge grids
+# ---------------------------------------------------------------------------------------------------
+def _both_ways(family, n, Sc, Nf, grid, seed=21):
+    f16s = family == "f16s"
+    _, model = make_model(*NETS[family])
+    opts = make_opts(Sc, Nf)
+    rays = lego_rays(n, 2)
+    g = torch.Generator().manual_seed(seed)
+    t_rand, u, tgt = torch.rand(n, Sc, generator=g).to(DEV), torch.rand(n, max(Nf, 1), generator=g).to(DEV), torch.rand(n, 3, generator=g).to(DEV)
+    u = u if Nf > 0 else None
+    full = train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, f16s=f16s)
+    mse2(full, tgt).backward()
+    g_full = grads_of(model)
+    model.zero_grad(set_to_none=True)
+    occ = OT.render_train(rays, model, opts, grid, t_rand=t_rand, u=u, f16s=f16s)
+    mse2(occ, tgt).backward()
+    return full, g_full, occ, grads_of(model), model
+
+
+def _compare_with_the_full_path(tag, full, g_full, occ, g_occ):
+    worst_out = max(float((occ[k].detach() - full[k].detach()).abs().max()) for k in full)
+    assert sorted(g_occ) == sorted(g_full) and len(g_full) > 0
+    rel = {k: float((g_occ[k] - g_full[k]).abs().max()) / float(g_full[k].abs().max()) for k in g_full}
+    worst_grad = max(rel.values())
+    print(f"\n[{tag}] all-ones grid vs train_path.render_train: outputs max |diff| {worst_out:.3e}, gradients worst relative difference {worst_grad:.3e}")
+    if ALL_ONES_BIT_EXACT:
+        assert worst_out == 0.0 and worst_grad == 0.0
+        assert all(torch.equal(occ[k], full[k]) for k in full) and all(torch.equal(g_occ[k], g_full[k]) for k in g_full)
+    else:
+        assert worst_out <= PARITY_BAR and worst_grad <= PARITY_BAR, (worst_out, rel)
+
+
+@pytest.mark.parametrize("family", sorted(NETS))
+def test_all_ones_grid_is_the_full_training_path(family):
+    grid = constant_grid(True, True)
+    full, g_full, occ, g_occ, _ = _both_ways(family, 96, 64, 64, grid)
+    s = grid.last_stats
+    assert (s["evaluated_c"], s["evaluated_f"], s["padded_c"], s["padded_f"]) == (s["total_c"], s["total_f"], 0, 0)
+    _compare_with_the_full_path(family, full, g_full, occ, g_occ)
+
+
+def test_all_ones_grid_above_four_tiles_per_cu():
+    """520 rays x 64 coarse samples, no fine pass: 1040 tiles, above 4 x CU count -- a wave takes a second unit on the compacted shape and
+    consumes the wrap of the weight-stream ring."""
+    grid = constant_grid(True, True)
+    full, g_full, occ, g_occ, _ = _both_ways("fp32", 520, 64, 0, grid)
+    assert grid.last_stats["evaluated_c"] + grid.last_stats["padded_c"] == 1040 * 32 > 4 * torch.cuda.get_device_properties(0).multi_processor_count * 32
+    _compare_with_the_full_path("fp32, 1040 tiles", full, g_full, occ, g_occ)
+
+
+@pytest.mark.parametrize("family", sorted(NETS))
+def test_all_zero_grid_launches_no_network_and_gives_zero_gradients(family, monkeypatch):
+    grid = constant_grid(False, False)
+    _, model = make_model(*NETS[family])
+    opts = make_opts(64, 64)
+    rays = lego_rays(64, 3)
+
+    def no_launch(*a, **k):
+        raise AssertionError("a network was launched although no sample survived")
+    monkeypatch.setattr(ops, "mlp_rays_train", no_launch)
+    monkeypatch.setattr(ops, "mlp_backward", no_launch)
+    out = OT.render_train(rays, model, opts, grid, seed=4, f16s=family == "f16s")
+    tgt = torch.rand(64, 3, generator=torch.Generator().manual_seed(0)).to(DEV)
+    mse2(out, tgt).backward()
+    assert float((out["rgb_c"] - 1.0).abs().max()) == 0.0 and float((out["rgb_f"] - 1.0).abs().max()) == 0.0       # the white background
+    s = grid.last_stats
+    assert s["evaluated_c"] == s["evaluated_f"] == s["padded_c"] == s["padded_f"] == 0 and s["total_f"] == 64 * 128
+    for k, p in model.named_parameters():
+        assert p.grad is not None and p.grad.shape == p.shape and float(p.grad.abs().max()) == 0.0, k
+
+
+# ---------------------------------------------------------------------------------------------------
+# 6. determinism
+# ---------------------------------------------------------------------------------------------------
+def test_two_backward_passes_give_identical_gradients(batch):
+    b = batch
+    flats = []
+    for _ in range(2):
+        b.model.zero_grad(set_to_none=True)
+        out = OT.render_train(b.rays, b.model, b.opts, b.grid, t_rand=b.t_rand, u=b.u, f16s=b.f16s)
+        mse2(out, b.tgt).backward()
+        flats.append(torch.cat([p.grad.reshape(-1) for p in b.model.parameters()]).clone())
+    b.model.zero_grad(set_to_none=True)
+    assert torch.equal(flats[0].view(torch.int32), flats[1].view(torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------------
+# public surface
+# ---------------------------------------------------------------------------------------------------
+def test_public_surface_runs_the_grid_path(batch, monkeypatch):
+    """nerf_process.render_rays / batchify(train_occupancy=grid) are occupancy_train.render_train; slabs sum their counts and accumulate
+    gradients like one node."""
+    b = batch
+    flags = {"f16s": True} if b.f16s else {}
+    b.model.zero_grad(set_to_none=True)
+    with torch.enable_grad():
+        out = NP.render_rays(b.rays, b.model, None, b.opts, t_rand=b.t_rand, u=b.u, train_occupancy=b.grid, **flags)
+    assert all(torch.equal(out[k], b.free[k]) for k in b.free) and b.grid.last_stats == b.stats and out["rgb_f"].requires_grad
+    monkeypatch.setattr(train_path, "MAX_TRAIN_RAYS", 50)              # three slabs of the 128 rays
+    rgb_c, _, rgb_f, _ = NP.batchify_rays_and_render_by_chunk(b.rays[:, :3], b.rays[:, 3:], b.model, None, 800, 800, None, b.opts, t_rand=b.t_rand, u=b.u,
+                                                              train_occupancy=b.grid, **flags)
+    assert torch.equal(rgb_f, b.free["rgb_f"]) and torch.equal(rgb_c, b.free["rgb_c"]) and b.grid.last_stats == b.stats
+    mse2({"rgb_c": rgb_c, "rgb_f": rgb_f}, b.tgt).backward()
+    for k, p in b.model.named_parameters():
+        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), k
+        if b.family == "fp32":                                       # the 4 x 128 network and the bar of test_training_slabs_accumulate_like_one_node:
+            e = float((p.grad - b.grads_c[k]).abs().max()) / float(b.grads_c[k].abs().max())      # same kernels, fp32 sums regrouped into three
+            assert e < 5e-5, (k, e)
+    b.model.zero_grad(set_to_none=True)
+
+
+# ---------------------------------------------------------------------------------------------------
+# 7. it trains
+# ---------------------------------------------------------------------------------------------------
+def test_a_scene_trains_with_the_grid():
+    """scenes.SolidScene.default() at 48 x 48, a 4 x 128 network, 300 full steps, bake (the defaults of
+    test_trained_scene_heldout_psnr_with_a_baked_grid), then 300 more steps three ways from the same checkpoint: the full path with jitter
+    seed A, the full path with seed B, the grid with seed A.  Held-out PSNR of the grid run >= min(full A, full B) - |full A - full B|: jitter
+    alone moves the result by that much.  The grid run's loss falls, and it evaluates less than every sample."""
+    warm, more, views, H = 300, 300, 12, 48
+    W = H
+    torch.manual_seed(0)
+    opts = SimpleNamespace(near=2.0, far=6.0, N_samples_c=64, N_samples_f=128, perturb=1.0, chunk_rays=4096, chunk_pts=524288, data_type="blender",
+                           gpu_ids=[0], rank=0, exp_name="occ_train", N_rays=1024, global_batch=True, idx_save=1 << 30, idx_print=1 << 30, precision="fp32")
+    K800, _, _ = synthetic.lego_camera()
+    K = np.array([[K800[0][0] * W / 800.0, 0, W / 2], [0, K800[1][1] * H / 800.0, H / 2], [0, 0, 1]])
+    posenc = get_positional_encoder(10), get_positional_encoder(4)
+    poses = harness.get_render_pose(n_angle=views + 2, phi=-30.0, nf=4.0)
+    images = scenes.SolidScene.default().render_views(poses, K, (H, W), opts.near, opts.far, 1024, DEV)
+    i_train, i_test = list(range(views)), [views]
+    model = NeRF(4, 128, 63, 27, skips=[4]).to(DEV)
+    optimizer = torch.optim.Adam(model.parameters(), lr=5e-4, betas=(0.9, 0.999))
+    criterion = torch.nn.MSELoss()
+    getter = harness.global_batch(images, K, poses, i_train, (H, W), DEV)
+    cam = (K, poses.numpy())
+    NP.manual_seed(7)
+    for i in range(1, warm + 1):
+        harness.train(i, i_train, images, cam, (H, W), model, criterion, posenc, optimizer, getter, None, opts)
+    with torch.no_grad():
+        grid = OC.OccupancyGrid(-4.5, 4.5, 160).bake(model, sub=2, sigma_min=0.0, dilate=1)
+    ckpt = (copy.deepcopy(model.state_dict()), copy.deepcopy(optimizer.state_dict()))
+    rng = torch.get_rng_state(), torch.cuda.get_rng_state(DEV)      # the getter reshuffles on the device at every epoch (27 steps)
+
+    def continue_training(jitter_seed, train_grid):
+        m = NeRF(4, 128, 63, 27, skips=[4]).to(DEV)
+        m.load_state_dict(ckpt[0])
+        opt = torch.optim.Adam(m.parameters(), lr=5e-4, betas=(0.9, 0.999))
+        opt.load_state_dict(copy.deepcopy(ckpt[1]))
+        get = copy.deepcopy(getter)                                  # the same ray batches three times
+        torch.set_rng_state(rng[0])
+        torch.cuda.set_rng_state(rng[1], DEV)
+        NP.manual_seed(jitter_seed)
+        o = SimpleNamespace(**vars(opts), train_occupancy=train_grid, occupancy_rebake_every=150 if train_grid is not None else 0)
+        losses, stats = [], None
+        for i in range(warm + 1, warm + more + 1):
+            losses.append(harness.train(i, i_train, images, cam, (H, W), m, criterion, posenc, opt, get, None, o)["loss"])
+            if train_grid is not None:
+                stats = OC.add_stats(stats, train_grid.last_stats)
+        m.eval()
+        NP.manual_seed(123)                                          # the same jitter for every held-out render
+        psnr = harness.test(warm + more, i_test, posenc, weights.packed_for(m), images[i_test], K, poses[i_test].to(DEV), (H, W), opts)["psnr"][0]
+        return psnr, torch.stack(losses).cpu(), stats
+
+    full_a, losses_a, _ = continue_training(1001, None)
+    full_b, losses_b, _ = continue_training(2002, None)
+    with_grid, losses, stats = continue_training(1001, grid)
+    share, padded = OC.evaluated_share(stats), OC.padded_share(stats)
+    first, last = float(losses[:30].mean()), float(losses[-30:].mean())
+    print(f"\n[trains] held-out PSNR after {warm} + {more} steps: full path seed A {full_a:.4f} dB, seed B {full_b:.4f} dB, grid (seed A) {with_grid:.4f} dB "
+          f"(largest per-step loss difference between the two full runs {float((losses_a - losses_b).abs().max()):.2e}); "
+          f"grid run: evaluated share {share:.3f}, padded share {padded:.3f}, occupied cells {grid.fraction():.4f}, "
+          f"loss first 30 steps {first:.5f} -> last 30 steps {last:.5f}; last step's stats {grid.last_stats}")
+    assert with_grid >= min(full_a, full_b) - abs(full_a - full_b), (full_a, full_b, with_grid)
+    assert last < first, (first, last)
+    assert share < 1.0, stats
