@@ -4,7 +4,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
 
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10]]
-                                             [--train-occupancy WARMUP:EVERY]
+                                             [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -12,6 +12,8 @@ mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after
 network and written as a binary PLY.  No counterpart in the reference.  ``--train-occupancy WARMUP:EVERY``: WARMUP full steps, then an
 occupancy grid is baked from the model (128^3 cells; ``--scene solid``: the box +-1.5 with everything outside it skipped, otherwise a box that
 holds every sample) and the remaining steps skip the samples it marks empty (occupancy_train.py), re-baking every EVERY steps (0: never).
+``--geometry ACC:DEPTH:DIST``: the weights of the opacity, depth and distortion losses (geometry.py; e.g. 0.1:0:0.01); ACC and DEPTH are
+supervised by the analytic scene's own opacity and depth, so they need ``--scene solid``.
 """
 import argparse
 import os
@@ -42,7 +44,19 @@ def main(argv=None):
     ap.add_argument("--mesh-iso", type=float, default=10.0, help="raw density of the surface")
     ap.add_argument("--mesh-box", type=float, default=1.5, help="the lattice spans +-this on every axis")
     ap.add_argument("--train-occupancy", default=None, metavar="WARMUP:EVERY", help="train with an occupancy grid baked after WARMUP full steps, re-baked every EVERY steps")
+    ap.add_argument("--geometry", default=None, metavar="ACC:DEPTH:DIST", help="weights of the opacity, depth and distortion losses (ACC, DEPTH: --scene solid only)")
     a = ap.parse_args(argv)
+    geometry = None
+    if a.geometry is not None:
+        try:
+            w_acc, w_depth, w_dist = (float(v) for v in a.geometry.split(":"))
+        except ValueError:
+            ap.error("--geometry takes ACC:DEPTH:DIST, three numbers")
+        if min(w_acc, w_depth, w_dist) < 0:
+            ap.error("--geometry takes three non-negative numbers")
+        if (w_acc or w_depth) and a.scene != "solid":
+            ap.error("--geometry with ACC or DEPTH above zero needs --scene solid (the targets come from the analytic scene)")
+        geometry = {"acc_weight": w_acc, "depth_weight": w_depth, "distortion_weight": w_dist}
     occ_warmup = occ_every = None
     if a.train_occupancy is not None:
         try:
@@ -65,11 +79,15 @@ def main(argv=None):
     # the "dataset": views of a fixed random NeRF rendered by the inference kernels (the teacher); the last two views are the test set
     if a.scene == "solid":                                                                       # the same cameras, the analytic scene
         images = scenes.SolidScene.default().render_views(poses, K, (H, W), opts.near, opts.far, 1024, dev)
+        if geometry is not None:
+            geometry["targets"] = scenes.SolidScene.default()                                    # its acc and depth along each training ray
     else:
         teacher = NeRF(8, 256, 63, 27).to(dev)
         teacher.load_state_dict({k: torch.as_tensor(v) for k, v in synthetic.make_state_dict(77, 8, 256).items()})
         with torch.no_grad():
             images = torch.stack([harness._render_pose(teacher, posenc, K, poses[i].to(dev), (H, W), opts)[0].reshape(H, W, 3) for i in range(a.views + 2)], 0)
+    if geometry is not None:
+        opts.geometry = geometry
     i_train, i_test = list(range(a.views)), [a.views, a.views + 1]
 
     model = NeRF(8, a.net_width, 63, 27, skips=[4]).to(dev)                                      # main.py:67-73
@@ -90,6 +108,8 @@ def main(argv=None):
         if i % opts.idx_print == 0:
             torch.cuda.synchronize()
             print(f"step {i:6d}  loss {float(out['loss']):.5f}  psnr_f {float(out['psnr_f']):.2f} dB  {(time.perf_counter() - t0) / i * 1e3:.1f} ms/step", flush=True)
+            if geometry is not None:
+                print("             " + "  ".join(f"{k} {float(out[k]):.3e}" for k in ("loss_acc", "loss_depth", "loss_distortion") if k in out), flush=True)
             grid = getattr(opts, "train_occupancy", None)
             if grid is not None and grid.last_stats:
                 from nerf_pytorch_paeng_amd import occupancy

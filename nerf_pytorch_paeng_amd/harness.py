@@ -473,7 +473,13 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
     the scaled backward used and the packer's out-of-range count; the training path itself raises when either says a step was clipped.
     ``opts.train_occupancy`` (absent = None): an occupancy.OccupancyGrid the step skips empty space with (occupancy_train.py);
     ``opts.occupancy_rebake_every`` (absent = 0: never): the grid is re-baked from the model, under no_grad and with its bake defaults,
-    before every step whose ``idx`` is a multiple of it."""
+    before every step whose ``idx`` is a multiple of it.
+    ``opts.geometry`` (absent = None): a mapping {"acc_weight", "depth_weight", "distortion_weight", "targets"} (geometry.parse_options; weights
+    default to 0, ``targets`` is a callable rays [B,6] -> (acc* [B], depth* [B]), required by the first two).  Per network the loss gains
+    acc_weight mse(acc, acc*) + depth_weight mean(acc* (depth - depth*)^2) + distortion_weight mean(distortion), and the dict the three
+    terms, summed over the networks and detached, as ``loss_acc`` / ``loss_depth`` / ``loss_distortion``."""
+    from . import geometry as geo
+    geom = geo.parse_options(getattr(opts, "geometry", None), float(opts.near), float(opts.far))
     model.train()
     img_h, img_w = hw
     gt_intrinsic, gt_extrinsic = gt_cam_param
@@ -492,8 +498,9 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
     if train_grid is not None and rebake > 0 and idx % rebake == 0:
         with torch.no_grad():
             train_grid.bake(model, **getattr(opts, "occupancy_bake_args", {}))
-    rgb_c, _, rgb_f, _ = NP.batchify_rays_and_render_by_chunk(rays_o.contiguous(), rays_d.contiguous(), model, posenc, img_h, img_w,
-                                                              gt_intrinsic, opts, **_precision(opts), train_occupancy=train_grid)      # train.py:53
+    rgb_c, _, rgb_f, _, *extras = NP.batchify_rays_and_render_by_chunk(rays_o.contiguous(), rays_d.contiguous(), model, posenc, img_h, img_w,
+                                                                       gt_intrinsic, opts, **_precision(opts), train_occupancy=train_grid,
+                                                                       **({} if geom is None else {"geometry": True}))      # train.py:53
     optimizer.zero_grad()
     target_img = target_img.contiguous()
     loss = criterion(rgb_c, target_img)                                                       # train.py:60
@@ -502,6 +509,15 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
         loss_f = criterion(rgb_f, target_img)
         out.update(loss_f=loss_f.detach(), psnr_f=-10.0 * torch.log10(loss_f.detach()))
         loss = loss + loss_f                                                                  # train.py:66
+    if geom is not None:
+        acc_t = depth_t = None
+        if geom["targets"] is not None:
+            with torch.no_grad():
+                acc_t, depth_t = geom["targets"](torch.cat([rays_o, rays_d], -1).contiguous())
+        for key in ("c", "f") if int(opts.N_samples_f) > 0 else ("c",):
+            for name, term in geo.loss_terms(geom, extras[0], key, acc_t, depth_t).items():
+                loss = loss + geom[name + "_weight"] * term
+                out["loss_" + name] = out.get("loss_" + name, 0.0) + term.detach()
     out["loss"] = loss.detach()
     loss.backward()                                                                           # train.py:69
     optimizer.step()                                                                          # train.py:70

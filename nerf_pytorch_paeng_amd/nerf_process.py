@@ -30,6 +30,7 @@ from .weights import PackedNeRF, packed_for
 from . import train_path
 from . import occupancy as occ
 from . import occupancy_train
+from . import geometry as geo
 
 # rays handed to one mi_nerf_render_rays call (workspace: 5.4 KB/ray at 64+128 samples -> ~5.6 GB)
 MAX_RAYS_PER_LAUNCH = 1 << 20
@@ -105,33 +106,39 @@ def pre_process(rays, posenc, opts, z_vals=None, weights=None, isFine=False, *, 
 
 
 class _Composite(torch.autograd.Function):
-    """post_process with the gradient the reference's loss uses: d rgb_map -> d raw (mi_nerf_composite_backward).
-    disp / acc / weights / depth are returned without a graph (train.py:60-66 reads the colours only)."""
+    """post_process, differentiable in rgb_map, acc_map and depth_map, and in weights when ``weights_grad``.  A loss that reads the colours
+    alone (train.py:60-66) gets d rgb_map -> d raw from mi_nerf_composite_backward; one that reads the others too, from
+    mi_geo_composite_backward (geometry.py).  disp is returned without a graph (it passes through a max, a NaN filter and a clamp)."""
 
     @staticmethod
-    def forward(ctx, raw, z, d):
+    def forward(ctx, raw, z, d, weights_grad=False):
         rgb, disp, acc, wts, depth = ops.composite(raw, z, d, want_all=True)
         ctx.save_for_backward(raw, z, d)
-        ctx.mark_non_differentiable(disp, acc, wts, depth)
+        ctx.mark_non_differentiable(*((disp,) if weights_grad else (disp, wts)))
         ctx.set_materialize_grads(False)
         return rgb, disp, acc, wts, depth
 
     @staticmethod
-    def backward(ctx, g_rgb, *_):
-        if g_rgb is None:
-            return None, None, None
+    def backward(ctx, g_rgb, g_disp, g_acc, g_wts, g_depth):
+        if g_rgb is None and g_acc is None and g_wts is None and g_depth is None:
+            return None, None, None, None
         raw, z, d = ctx.saved_tensors
-        return ops.composite_backward(raw, z, d, g_rgb.contiguous().float()), None, None
+        if g_acc is None and g_wts is None and g_depth is None:
+            return ops.composite_backward(raw, z, d, g_rgb.contiguous().float()), None, None, None
+        g_rgb, g_acc, g_wts, g_depth = (None if g is None else g.contiguous().float() for g in (g_rgb, g_acc, g_wts, g_depth))
+        # no distortion term here: the normalising bounds are not read
+        return geo.composite_geo_backward(raw, z, d, 0.0, 1.0, g_rgb, g_acc, g_depth, None, g_wts), None, None, None
 
 
-def post_process(outputs, z_vals, rays_d):
+def post_process(outputs, z_vals, rays_d, *, weights_grad: bool = False):
     """Alpha compositing (nerf_process.py:89-140) -> (rgb_map, disp_map, acc_map, weights, depth_map).
-    Differentiable in ``rgb_map`` w.r.t. ``outputs`` when they carry a graph."""
+    Differentiable in ``rgb_map``, ``acc_map`` and ``depth_map`` w.r.t. ``outputs`` when they carry a graph; ``weights_grad=True`` makes the
+    per-sample ``weights`` differentiable too (without the keyword they are returned without a graph, as they always were)."""
     z = as_f32_dev(z_vals)
     raw = as_f32_dev(outputs, z.device)
     d = as_f32_dev(rays_d, z.device)
     if torch.is_grad_enabled() and raw.requires_grad:
-        return _Composite.apply(raw, z.detach(), d.detach())
+        return _Composite.apply(raw, z.detach(), d.detach(), bool(weights_grad))
     return ops.composite(raw, z, d, want_all=True)
 
 
@@ -148,7 +155,7 @@ def run_network(model, embedded, is_fine: bool = False):
 
 # --------------------------------------------------------------------------------------------------
 def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, ray_offset: int, prec: ops.Precision,
-            intermediates: bool, occupancy=None) -> Dict[str, torch.Tensor]:
+            intermediates: bool, occupancy=None, geometry: bool = False) -> Dict[str, torch.Tensor]:
     n = rays.shape[0]
     dev = rays.device
     Sc, Nf = int(opts.N_samples_c), int(opts.N_samples_f)
@@ -180,6 +187,11 @@ def _render(rays: torch.Tensor, packed: PackedNeRF, opts, t_rand, u, seed: int, 
     out = {"rgb_c": rgb_c, "disp_c": disp_c}                        # nerf_process.py:215-216
     if Nf > 0:
         out["rgb_f"], out["disp_f"] = rgb_f, disp_f
+    if geometry:                                                    # the six geometry outputs from the raw / z the pass left in its workspace
+        v = views(cfg, n, ws)
+        for key in ("c", "f") if Nf > 0 else ("c",):
+            extra = geo.composite_geo(v["raw_" + key], v["z_" + key], rays, float(opts.near), float(opts.far))
+            out.update({name + "_" + key: t for name, t in zip(geo.EXTRA_KEYS, (extra[2], extra[4], extra[5]))})
     if intermediates:
         for k, v in views(cfg, n, ws).items():
             out["_" + k] = v
@@ -225,11 +237,17 @@ def _train_f16s(prec: ops.Precision, intermediates: bool = False) -> bool:
     return prec.fine == "f16s"
 
 
+def _geometry_kw(geometry) -> Dict[str, bool]:
+    """No keyword means today's call, argument for argument."""
+    return {"geometry": True} if geometry else {}
+
+
 def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ray_offset: int = 0, bf16: bool = False,
                 return_intermediates: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False,
-                occupancy=None, train_occupancy=None):
+                occupancy=None, train_occupancy=None, geometry: bool = False):
     """Coarse pass -> composite -> resample -> fine pass (nerf_process.py:185-216) as one fused launch
-    sequence.  Returns ``{'rgb_c','disp_c'[,'rgb_f','disp_f']}``.  ``bf16`` / ``f16s`` / ``coarse_f16s`` / ``f16`` / ``coarse_f16`` select
+    sequence.  Returns ``{'rgb_c','disp_c'[,'rgb_f','disp_f']}``; ``geometry=True`` adds ``acc_*``, ``depth_*`` and ``distortion_*`` [n] per
+    network (geometry.py), differentiable outputs of the training node when gradients are enabled.  ``bf16`` / ``f16s`` / ``coarse_f16s`` / ``f16`` / ``coarse_f16`` select
     the networks' precision mode (ops.precision(); fp32 MFMA by default).  With gradients: fp32 or f16s.  ``occupancy``: an OccupancyGrid
     (occupancy.py) -- the networks skip the samples it marks empty; ``return_intermediates`` then also returns ``_occ_stats``.
     ``train_occupancy``: the same for the training path (gradients enabled; fp32 or f16s); the counts are in the grid's ``last_stats``."""
@@ -242,22 +260,24 @@ def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ra
             raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
         if train_occupancy is not None:
             return occupancy_train.render_train(rays, model, opts, train_occupancy, t_rand=t_rand, u=u, seed=_next_seed(seed),
-                                                ray_offset=int(ray_offset), f16s=train_f16s)
-        return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=_next_seed(seed), ray_offset=int(ray_offset), f16s=train_f16s)
+                                                ray_offset=int(ray_offset), f16s=train_f16s, **_geometry_kw(geometry))
+        return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=_next_seed(seed), ray_offset=int(ray_offset), f16s=train_f16s,
+                                       **_geometry_kw(geometry))
     packed = packed_for(model)
     rays = as_f32_dev(rays, packed.device)
     if rays.dim() != 2 or rays.shape[1] != 6:
         raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
     if occupancy is not None and rays.shape[0] > occ.MAX_RAYS_PER_LAUNCH:
         raise MiNerfError(f"render_rays with a grid takes at most {occ.MAX_RAYS_PER_LAUNCH} rays per call (batchify_rays_and_render_by_chunk slabs them)")
-    return _render(rays, packed, opts, t_rand, u, _next_seed(seed), int(ray_offset), prec, return_intermediates, occupancy)
+    return _render(rays, packed, opts, t_rand, u, _next_seed(seed), int(ray_offset), prec, return_intermediates, occupancy, **_geometry_kw(geometry))
 
 
 def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts, *, t_rand=None, u=None, seed=None,
                                       ray_offset: int = 0, bf16: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False,
-                                      coarse_f16: bool = False, occupancy=None, train_occupancy=None):
+                                      coarse_f16: bool = False, occupancy=None, train_occupancy=None, geometry: bool = False):
     """Drop-in entry point (nerf_process.py:220-252): flatten, optional NDC warp for llff, render.
-    Returns ``(rgb_c [N,3], disp_c [N], rgb_f [N,3] | None, disp_f [N] | None)``.
+    Returns ``(rgb_c [N,3], disp_c [N], rgb_f [N,3] | None, disp_f [N] | None)``; with ``geometry=True`` a fifth element, the dict of
+    ``acc_*`` / ``depth_*`` / ``distortion_*`` [N] that ``render_rays(..., geometry=True)`` adds, concatenated over the slabs.
 
     ``opts.chunk_rays`` bounded the reference's activation memory; the fused kernels keep activations in
     registers, so rays are launched in slabs of up to MAX_RAYS_PER_LAUNCH.  The result does not depend on
@@ -291,17 +311,18 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
         tr, uu = (None if t_rand is None else t_rand[i:j]), (None if u is None else u[i:j])
         if train_occupancy is not None:
             parts.append(occupancy_train.render_train(rays[i:j].contiguous(), model, opts, train_occupancy, t_rand=tr, u=uu, seed=seed,
-                                                      ray_offset=int(ray_offset) + i, f16s=train_f16s))
+                                                      ray_offset=int(ray_offset) + i, f16s=train_f16s, **_geometry_kw(geometry)))
             train_stats = occ.add_stats(train_stats, train_occupancy.last_stats)
         elif training:                                              # train.py:53-54: one autograd node per slab
             parts.append(train_path.render_train(rays[i:j].contiguous(), model, opts, t_rand=tr, u=uu, seed=seed,
-                                                 ray_offset=int(ray_offset) + i, f16s=train_f16s))
+                                                 ray_offset=int(ray_offset) + i, f16s=train_f16s, **_geometry_kw(geometry)))
         else:
-            parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False, occupancy))
+            parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False, occupancy, **_geometry_kw(geometry)))
     if train_occupancy is not None:
         train_occupancy.last_stats = train_stats
     def cat(key):
         return parts[0][key] if len(parts) == 1 else torch.cat([p[key] for p in parts], dim=0)
-    if Nf > 0:
-        return cat("rgb_c"), cat("disp_c"), cat("rgb_f"), cat("disp_f")
-    return cat("rgb_c"), cat("disp_c"), None, None
+    res = (cat("rgb_c"), cat("disp_c"), cat("rgb_f"), cat("disp_f")) if Nf > 0 else (cat("rgb_c"), cat("disp_c"), None, None)
+    if geometry:
+        return (*res, {name + "_" + key: cat(name + "_" + key) for key in (("c", "f") if Nf > 0 else ("c",)) for name in geo.EXTRA_KEYS})
+    return res

@@ -19,6 +19,7 @@ from typing import Dict, List, Optional
 
 import torch
 
+from . import geometry as geo
 from . import ops
 from ._lib import MiNerfError, Net, as_f32_dev
 from .weights import _param_shape, infer_net, pad_index_map, padded_train_net
@@ -177,7 +178,8 @@ def _flat(params) -> torch.Tensor:
 
 
 class _RenderTrain(torch.autograd.Function):
-    """rays (+ explicit randomness) and the two networks' parameters -> rgb_c, disp_c, rgb_f, disp_f."""
+    """rays (+ explicit randomness) and the two networks' parameters -> rgb_c, disp_c, rgb_f, disp_f; with ``cfg["geometry"]`` also
+    acc_c, depth_c, distortion_c, acc_f, depth_f, distortion_f, differentiable like the colours (geometry.node_forward / node_backward)."""
 
     @staticmethod
     def forward(ctx, st: _TrainState, rays, cfg: Dict, t_rand, u, z_override, *params):
@@ -197,46 +199,48 @@ class _RenderTrain(torch.autograd.Function):
         blob_c = ops.pack_apply(st.map_fwd, flat_c)
         z_c = ops.stratified_z(cfg["near"], cfg["far"], t_rand) if z_override is None else z_override[0]
         raw_c, stash_c = forward_net(flat_c, blob_c, z_c)
-        rgb_c, disp_c, _, w_c, _ = ops.composite(raw_c, z_c, rays, want_all=True)
-        ctx.st, ctx.Nf, ctx.f16s = st, Nf, f16s
+        rgb_c, disp_c, w_c, extra_c = geo.node_forward(cfg, raw_c, z_c, rays, True)
+        ctx.st, ctx.Nf, ctx.f16s, ctx.cfg = st, Nf, f16s, cfg
         saved = [rays, flat_c, blob_c, z_c, raw_c, stash_c]
         if Nf > 0:
             flat_f = st.flat(params[n_each:])
             blob_f = ops.pack_apply(st.map_fwd, flat_f)
             z_f = ops.fine_z(z_c, w_c, Nf, det, None if det else u) if (z_override is None or z_override[1] is None) else z_override[1]
             raw_f, stash_f = forward_net(flat_f, blob_f, z_f)
-            rgb_f, disp_f, *_ = ops.composite(raw_f, z_f, rays, want_all=False)
+            rgb_f, disp_f, _, extra_f = geo.node_forward(cfg, raw_f, z_f, rays, False)
             saved += [flat_f, blob_f, z_f, raw_f, stash_f]
         else:
             rgb_f = torch.empty(0, 3, device=rays.device)
             disp_f = torch.empty(0, device=rays.device)
+            extra_f = tuple(torch.empty(0, device=rays.device) for _ in extra_c)
         ctx.save_for_backward(*saved)
         ctx.mark_non_differentiable(disp_c, disp_f)
         ctx.set_materialize_grads(False)
-        return rgb_c, disp_c, rgb_f, disp_f
+        return (rgb_c, disp_c, rgb_f, disp_f, *extra_c, *extra_f)
 
     @staticmethod
-    def backward(ctx, g_rgb_c, g_disp_c, g_rgb_f, g_disp_f):
+    def backward(ctx, g_rgb_c, g_disp_c, g_rgb_f, g_disp_f, *g_extra):
         st: _TrainState = ctx.st
         net = st.net
         saved = ctx.saved_tensors
         rays = saved[0]
+        g_extra_c, g_extra_f = g_extra[:len(g_extra) // 2], g_extra[len(g_extra) // 2:]
 
-        def one(flat, blob, z, raw, stash, g_rgb) -> List[Optional[torch.Tensor]]:
-            if g_rgb is None:
+        def one(flat, blob, z, raw, stash, g_rgb, g_ext) -> List[Optional[torch.Tensor]]:
+            if g_rgb is None and all(g is None for g in g_ext):
                 return [None] * len(st.names)
             f16s = ctx.f16s and net.W == 256
             f16s_dgrad = f16s and net.D <= 15              # the split-precision chain keeps a tile's ReLU' words of all layers in LDS
             blob_b = ops.pack_apply_f16s(net, st.map_bwd_f16s(), flat, st.f16s_out_of_range, backward=True) if f16s_dgrad else ops.pack_apply(st.map_bwd, flat)
-            d_raw = ops.composite_backward(raw, z, rays, g_rgb.contiguous().float())
+            d_raw = geo.node_backward(ctx.cfg, raw, z, rays, g_rgb, g_ext)
             grads, work = ops.mlp_backward(net, blob, blob_b, rays, z, d_raw, stash, f16s_wgrad=f16s, f16s_dgrad=f16s_dgrad)
             if f16s:
                 st.note_f16s_backward(work, z.shape[0], z.shape[1])
             return st.split_grads(grads)
 
-        gc = one(*saved[1:6], g_rgb_c)
-        gf = one(*saved[6:11], g_rgb_f) if ctx.Nf > 0 else [None] * len(st.names)
-        if ctx.f16s and net.W == 256 and (g_rgb_c is not None or g_rgb_f is not None):
+        gc = one(*saved[1:6], g_rgb_c, g_extra_c)
+        gf = one(*saved[6:11], g_rgb_f, g_extra_f) if ctx.Nf > 0 else [None] * len(st.names)
+        if ctx.f16s and net.W == 256 and any(g is not None for g in (g_rgb_c, g_rgb_f, *g_extra)):
             st.end_f16s_step()                                 # both nets' range words are folded: read them at the cadence
         return (None, None, None, None, None, None, *gc, *gf)
 
@@ -263,9 +267,10 @@ class _EmbeddedTrain(torch.autograd.Function):
 
 
 def render_train(rays: torch.Tensor, model: torch.nn.Module, opts, *, t_rand=None, u=None, seed: int = 0, ray_offset: int = 0,
-                 z_override=None, det: Optional[bool] = None, f16s: bool = False) -> Dict[str, torch.Tensor]:
+                 z_override=None, det: Optional[bool] = None, f16s: bool = False, geometry: bool = False) -> Dict[str, torch.Tensor]:
     """Differentiable ``render_rays`` (nerf_process.py:185-216) for one slab of rays [n, 6].  ``f16s``: the two forward launches run in
-    split precision (fp32-grade results, ~3x faster); the backward kernels are the fp32 ones."""
+    split precision (fp32-grade results, ~3x faster); the backward kernels are the fp32 ones.  ``geometry``: the dict also carries
+    ``acc_*``, ``depth_*`` and ``distortion_*`` per network, differentiable like the colours (geometry.py)."""
     st = _state_for(model, f16s)                 # f16s: the 256-wide state (any netWidth <= 256 is scattered into it)
     dev = st.device
     if isinstance(rays, torch.Tensor) and rays.requires_grad:
@@ -282,12 +287,22 @@ def render_train(rays: torch.Tensor, model: torch.nn.Module, opts, *, t_rand=Non
         u = ops.fill_uniform(seed, 1, ray_offset, n, Nf, dev) if u is None else as_f32_dev(u, dev)
     else:
         u = None
-    cfg = {"near": float(opts.near), "far": float(opts.far), "Sc": Sc, "Nf": Nf, "det": bool(det), "f16s": bool(f16s)}
+    cfg = {"near": float(opts.near), "far": float(opts.far), "Sc": Sc, "Nf": Nf, "det": bool(det), "f16s": bool(f16s), "geometry": bool(geometry)}
     params = st.params(model.model_coarse) + st.params(model.model_fine)
-    rgb_c, disp_c, rgb_f, disp_f = _RenderTrain.apply(st, rays, cfg, t_rand, u, z_override, *params)
+    rgb_c, disp_c, rgb_f, disp_f, *extra = _RenderTrain.apply(st, rays, cfg, t_rand, u, z_override, *params)
+    return node_outputs(rgb_c, disp_c, rgb_f, disp_f, extra, Nf)
+
+
+def node_outputs(rgb_c, disp_c, rgb_f, disp_f, extra, Nf: int) -> Dict[str, torch.Tensor]:
+    """The dict of ``render_rays`` from a training node's outputs (``extra``: empty, or the six geometry outputs)."""
     out = {"rgb_c": rgb_c, "disp_c": disp_c}
     if Nf > 0:
         out["rgb_f"], out["disp_f"] = rgb_f, disp_f
+    if extra:
+        k = len(geo.EXTRA_KEYS)
+        out.update({name + "_c": v for name, v in zip(geo.EXTRA_KEYS, extra[:k])})
+        if Nf > 0:
+            out.update({name + "_f": v for name, v in zip(geo.EXTRA_KEYS, extra[k:])})
     return out
 
 
