@@ -1,4 +1,4 @@
-"""Build libmi_nerf.so, libmi_nerf_iqa.so, libmi_nerf_occ.so, libmi_nerf_scene.so, libmi_nerf_mesh.so and libmi_nerf_geo.so with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libmi_nerf.so, libmi_nerf_iqa.so, libmi_nerf_occ.so, libmi_nerf_scene.so, libmi_nerf_mesh.so, libmi_nerf_geo.so and libmi_nerf_pose.so with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m nerf_pytorch_paeng_amd.build [--force]          the shipped libraries (clean build: ~1 min 20 s on 8 cores)
     python -m nerf_pytorch_paeng_amd.build --variant TAG -DFOO -DBAR=1     an A/B variant (tools/ab_probe.py)
@@ -20,6 +20,8 @@ What lands where:
                                                     linked against libmi_nerf.so (rpath $ORIGIN) like libmi_nerf_occ.so.
   nerf_pytorch_paeng_amd/libmi_nerf_geo.so (+ .stamp)   geometry losses (include/mi_nerf_geo.h, csrc/geo.hip): a sixth library with a stamp of its own; it
                                                     includes csrc/common.h and csrc/stage_dev.h and links against no other library of the project.
+  nerf_pytorch_paeng_amd/libmi_nerf_pose.so (+ .stamp)  ray and pose gradients (include/mi_nerf_pose.h, csrc/pose.hip): a seventh library with a stamp of its
+                                                    own; it includes csrc/common.h and links against no other library of the project.
   build_scratch/obj/                                objects of the shipped library (cache; tests/test_packing_cpu.py disassembles them)
   build_scratch/obj_TAG/, build_scratch/libmi_nerf_TAG.so    variants.  build_scratch/ is git-ignored AND gpurun-ignored: a variant is
                                                     built where it is used (tools/ab_probe.py builds the ones it is asked for on the box).
@@ -61,6 +63,10 @@ MESH_SOURCES = ["mesh.hip"]
 GEO_LIB = os.path.join(HERE, "libmi_nerf_geo.so")
 GEO_STAMP = GEO_LIB + ".stamp"
 GEO_SOURCES = ["geo.hip"]
+# libmi_nerf_pose.so: its own source and header; it shares common.h with libmi_nerf.so at compile time and nothing at link time
+POSE_LIB = os.path.join(HERE, "libmi_nerf_pose.so")
+POSE_STAMP = POSE_LIB + ".stamp"
+POSE_SOURCES = ["pose.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          # the MLP kernel's register-resident design needs its k-loops FULLY unrolled (static register indices)
@@ -274,6 +280,30 @@ def build_geo_library(force: bool = False, verbose: bool = False) -> str:
     return GEO_LIB
 
 
+def _pose_headers():
+    return [os.path.join(INCLUDE, "mi_nerf_pose.h"), os.path.join(CSRC, "common.h"), os.path.join(INCLUDE, "mi_nerf.h")]
+
+
+def pose_source_stamp() -> str:
+    return _digest([os.path.join(CSRC, s) for s in POSE_SOURCES] + _pose_headers(), [FLAGS])
+
+
+def build_pose_library(force: bool = False, verbose: bool = False) -> str:
+    """libmi_nerf_pose.so, a no-op when its stamp matches (like build_library).  It links against no other library of the project."""
+    want = pose_source_stamp()
+    if not force and os.path.exists(POSE_LIB) and os.path.exists(POSE_STAMP) and open(POSE_STAMP).read() == want:
+        if verbose:
+            print(f"up to date: {POSE_LIB} ({os.path.getsize(POSE_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+        return POSE_LIB
+    objs = [_compile(s, force, headers=_pose_headers()) for s in POSE_SOURCES]
+    _link(objs, POSE_LIB)
+    with open(POSE_STAMP, "w") as fh:
+        fh.write(want)
+    if verbose:
+        print(f"built {POSE_LIB} ({os.path.getsize(POSE_LIB) / 1024:.0f} KiB, stamp {want[:16]})")
+    return POSE_LIB
+
+
 def variant_path(tag: str) -> str:
     return os.path.join(SCRATCH, f"libmi_nerf_{tag}.so")
 
@@ -323,3 +353,4 @@ if __name__ == "__main__":
         print(build_scene_library(force="--force" in sys.argv, verbose=True))
         print(build_mesh_library(force="--force" in sys.argv, verbose=True))
         print(build_geo_library(force="--force" in sys.argv, verbose=True))
+        print(build_pose_library(force="--force" in sys.argv, verbose=True))

@@ -435,10 +435,10 @@ def global_batch(images, gt_intrinsic, gt_extrinsic, i_train: Sequence[int], hw,
     return GetterRayBatchIdx(rr, generator, shuffle=shuffle)                                            # main.py:102: a permutation, not a copy
 
 
-def sample_rays_and_pixel(i, img_w, img_h, K, pose, target_img, opts, generator: Optional[torch.Generator] = None):
+def sample_rays_and_pixel(i, img_w, img_h, K, pose, target_img, opts, generator: Optional[torch.Generator] = None, *, pose_grad: bool = False):
     """rays.py:36-64 fused with the ``make_o_d`` that precedes it in train.py:43-45: N_rays pixels without replacement
     (inside the centre crop while ``i < opts.precrop_iters``), rays generated for those pixels only.
-    Returns ``(rays_o [N,3], rays_d [N,3], target [N,3])``."""
+    Returns ``(rays_o [N,3], rays_d [N,3], target [N,3])``.  ``pose_grad``: the same rays from ``pose.make_o_d``, differentiable in ``pose``."""
     target_img = as_f32_dev(target_img)
     dev = target_img.device
     if i < int(getattr(opts, "precrop_iters", 0)):
@@ -456,7 +456,11 @@ def sample_rays_and_pixel(i, img_w, img_h, K, pose, target_img, opts, generator:
     sel = torch.randperm(n_coords, device=dev, generator=generator)[:n]                         # rays.py:53-54
     py, px = ys[sel // xs.numel()], xs[sel % xs.numel()]
     pix = (py * img_w + px).contiguous()
-    rays_o, rays_d = ops.make_o_d_pixels(int(img_w), int(img_h), K, pose, pix)
+    if pose_grad:
+        from . import pose as pose_mod
+        rays_o, rays_d = pose_mod.make_o_d(int(img_w), int(img_h), K, pose, pixels=pix)
+    else:
+        rays_o, rays_d = ops.make_o_d_pixels(int(img_w), int(img_h), K, pose, pix)
     target = target_img.reshape(-1, 3)[pix]
     return rays_o, rays_d, target
 
@@ -477,9 +481,20 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
     ``opts.geometry`` (absent = None): a mapping {"acc_weight", "depth_weight", "distortion_weight", "targets"} (geometry.parse_options; weights
     default to 0, ``targets`` is a callable rays [B,6] -> (acc* [B], depth* [B]), required by the first two).  Per network the loss gains
     acc_weight mse(acc, acc*) + depth_weight mean(acc* (depth - depth*)^2) + distortion_weight mean(distortion), and the dict the three
-    terms, summed over the networks and detached, as ``loss_acc`` / ``loss_depth`` / ``loss_distortion``."""
+    terms, summed over the networks and detached, as ``loss_acc`` / ``loss_depth`` / ``loss_distortion``.
+    ``opts.pose_refine`` (absent = None): a pose.CameraRefiner whose parameters the caller has put into ``optimizer``.  The per-image branch
+    then makes its rays from the refined pose with ``pose.make_o_d`` and renders with ``ray_grad=True``, so the step also moves the
+    refiner; the global batch, whose rays are precomputed from fixed poses, is refused."""
     from . import geometry as geo
     geom = geo.parse_options(getattr(opts, "geometry", None), float(opts.near), float(opts.far))
+    refiner = getattr(opts, "pose_refine", None)
+    if refiner is not None:
+        from .pose import CameraRefiner
+        if not isinstance(refiner, CameraRefiner):
+            raise MiNerfError(f"opts.pose_refine must be a pose.CameraRefiner, got {type(refiner).__name__}")
+        if global_batch_idx is not None and getattr(opts, "global_batch", True):
+            raise MiNerfError("opts.pose_refine needs the per-image branch: the global batch holds rays precomputed from fixed poses "
+                              "(pass global_batch_idx=None or opts.global_batch=False)")
     model.train()
     img_h, img_w = hw
     gt_intrinsic, gt_extrinsic = gt_cam_param
@@ -492,7 +507,11 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
         i_img = int(np.random.choice(i_train))                                                # train.py:37
         target_full = as_f32_dev(torch.as_tensor(images[i_img]), dev)
         pose = torch.as_tensor(np.asarray(gt_extrinsic[i_img]) if not isinstance(gt_extrinsic, torch.Tensor) else gt_extrinsic[i_img])
-        rays_o, rays_d, target_img = sample_rays_and_pixel(idx, img_w, img_h, gt_intrinsic, pose[:3, :4], target_full, opts, generator)
+        if refiner is not None:
+            rays_o, rays_d, target_img = sample_rays_and_pixel(idx, img_w, img_h, gt_intrinsic, refiner(i_img, pose[:3, :4]), target_full, opts,
+                                                               generator, pose_grad=True)
+        else:
+            rays_o, rays_d, target_img = sample_rays_and_pixel(idx, img_w, img_h, gt_intrinsic, pose[:3, :4], target_full, opts, generator)
     train_grid = getattr(opts, "train_occupancy", None)
     rebake = int(getattr(opts, "occupancy_rebake_every", 0) or 0)
     if train_grid is not None and rebake > 0 and idx % rebake == 0:
@@ -500,7 +519,8 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
             train_grid.bake(model, **getattr(opts, "occupancy_bake_args", {}))
     rgb_c, _, rgb_f, _, *extras = NP.batchify_rays_and_render_by_chunk(rays_o.contiguous(), rays_d.contiguous(), model, posenc, img_h, img_w,
                                                                        gt_intrinsic, opts, **_precision(opts), train_occupancy=train_grid,
-                                                                       **({} if geom is None else {"geometry": True}))      # train.py:53
+                                                                       **({} if geom is None else {"geometry": True}),
+                                                                       **({} if refiner is None else {"ray_grad": True}))   # train.py:53
     optimizer.zero_grad()
     target_img = target_img.contiguous()
     loss = criterion(rgb_c, target_img)                                                       # train.py:60
@@ -513,7 +533,7 @@ def train(idx, i_train, images, gt_cam_param, hw, model, criterion, posenc, opti
         acc_t = depth_t = None
         if geom["targets"] is not None:
             with torch.no_grad():
-                acc_t, depth_t = geom["targets"](torch.cat([rays_o, rays_d], -1).contiguous())
+                acc_t, depth_t = geom["targets"](torch.cat([rays_o, rays_d], -1).detach().contiguous())
         for key in ("c", "f") if int(opts.N_samples_f) > 0 else ("c",):
             for name, term in geo.loss_terms(geom, extras[0], key, acc_t, depth_t).items():
                 loss = loss + geom[name + "_weight"] * term

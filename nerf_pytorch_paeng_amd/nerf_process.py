@@ -237,24 +237,33 @@ def _train_f16s(prec: ops.Precision, intermediates: bool = False) -> bool:
     return prec.fine == "f16s"
 
 
-def _geometry_kw(geometry) -> Dict[str, bool]:
+def _geometry_kw(geometry, ray_grad=False) -> Dict[str, bool]:
     """No keyword means today's call, argument for argument."""
-    return {"geometry": True} if geometry else {}
+    return {**({"geometry": True} if geometry else {}), **({"ray_grad": True} if ray_grad else {})}
+
+
+def _ray_grad_arg(ray_grad, train_occupancy) -> bool:
+    if ray_grad and train_occupancy is not None:
+        raise MiNerfError("ray_grad=True with train_occupancy= is not built: the occupancy-training node differentiates the parameters only")
+    return bool(ray_grad)
 
 
 def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ray_offset: int = 0, bf16: bool = False,
                 return_intermediates: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False, coarse_f16: bool = False,
-                occupancy=None, train_occupancy=None, geometry: bool = False):
+                occupancy=None, train_occupancy=None, geometry: bool = False, ray_grad: bool = False):
     """Coarse pass -> composite -> resample -> fine pass (nerf_process.py:185-216) as one fused launch
     sequence.  Returns ``{'rgb_c','disp_c'[,'rgb_f','disp_f']}``; ``geometry=True`` adds ``acc_*``, ``depth_*`` and ``distortion_*`` [n] per
     network (geometry.py), differentiable outputs of the training node when gradients are enabled.  ``bf16`` / ``f16s`` / ``coarse_f16s`` / ``f16`` / ``coarse_f16`` select
     the networks' precision mode (ops.precision(); fp32 MFMA by default).  With gradients: fp32 or f16s.  ``occupancy``: an OccupancyGrid
     (occupancy.py) -- the networks skip the samples it marks empty; ``return_intermediates`` then also returns ``_occ_stats``.
-    ``train_occupancy``: the same for the training path (gradients enabled; fp32 or f16s); the counts are in the grid's ``last_stats``."""
+    ``train_occupancy``: the same for the training path (gradients enabled; fp32 or f16s); the counts are in the grid's ``last_stats``.
+    ``ray_grad``: rays that require grad receive their gradient from the training node (pose.py), also when the model is frozen."""
     prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
-    occupancy = _occupancy_arg(occupancy, train_path.wants_grad(model), prec)
-    train_occupancy = _train_occupancy_arg(train_occupancy, train_path.wants_grad(model), prec)
-    if train_path.wants_grad(model):
+    ray_grad = _ray_grad_arg(ray_grad, train_occupancy)
+    training = train_path.wants_grad(model) or train_path.wants_ray_grad(model, ray_grad, rays)
+    occupancy = _occupancy_arg(occupancy, training, prec)
+    train_occupancy = _train_occupancy_arg(train_occupancy, training, prec)
+    if training:
         train_f16s = _train_f16s(prec, return_intermediates)
         if rays.dim() != 2 or rays.shape[1] != 6:
             raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
@@ -262,7 +271,7 @@ def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ra
             return occupancy_train.render_train(rays, model, opts, train_occupancy, t_rand=t_rand, u=u, seed=_next_seed(seed),
                                                 ray_offset=int(ray_offset), f16s=train_f16s, **_geometry_kw(geometry))
         return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=_next_seed(seed), ray_offset=int(ray_offset), f16s=train_f16s,
-                                       **_geometry_kw(geometry))
+                                       **_geometry_kw(geometry, ray_grad))
     packed = packed_for(model)
     rays = as_f32_dev(rays, packed.device)
     if rays.dim() != 2 or rays.shape[1] != 6:
@@ -274,7 +283,8 @@ def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ra
 
 def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts, *, t_rand=None, u=None, seed=None,
                                       ray_offset: int = 0, bf16: bool = False, f16s: bool = False, coarse_f16s: bool = False, f16: bool = False,
-                                      coarse_f16: bool = False, occupancy=None, train_occupancy=None, geometry: bool = False):
+                                      coarse_f16: bool = False, occupancy=None, train_occupancy=None, geometry: bool = False,
+                                      ray_grad: bool = False):
     """Drop-in entry point (nerf_process.py:220-252): flatten, optional NDC warp for llff, render.
     Returns ``(rgb_c [N,3], disp_c [N], rgb_f [N,3] | None, disp_f [N] | None)``; with ``geometry=True`` a fifth element, the dict of
     ``acc_*`` / ``depth_*`` / ``distortion_*`` [N] that ``render_rays(..., geometry=True)`` adds, concatenated over the slabs.
@@ -283,9 +293,11 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
     registers, so rays are launched in slabs of up to MAX_RAYS_PER_LAUNCH.  The result does not depend on
     the slab size because the jitter is keyed on the global ray index (``ray_offset`` + position).
     ``occupancy``: an OccupancyGrid (occupancy.py); its ``last_stats`` then holds the sample counts of this call.  ``train_occupancy``: the
-    same for the training path (occupancy_train.py)."""
+    same for the training path (occupancy_train.py).  ``ray_grad``: ``ray_o`` / ``ray_d`` that require grad receive their gradient (through
+    the NDC warp too, for llff), also when the model is frozen."""
     prec = ops.precision(bf16, f16s, coarse_f16s, f16, coarse_f16)
-    training = train_path.wants_grad(model)
+    ray_grad = _ray_grad_arg(ray_grad, train_occupancy)
+    training = train_path.wants_grad(model) or train_path.wants_ray_grad(model, ray_grad, ray_o, ray_d)
     occupancy = _occupancy_arg(occupancy, training, prec)
     train_occupancy = _train_occupancy_arg(train_occupancy, training, prec)
     train_f16s = _train_f16s(prec) if training else False
@@ -298,7 +310,11 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
     if getattr(opts, "data_type", None) == "llff":                  # nerf_process.py:224-226
         k00 = K[0][0]
         focal = float(k00.item()) if isinstance(k00, torch.Tensor) else float(k00)
-        flat_o, flat_d = ndc_rays(H, W, focal, 1.0, flat_o, flat_d)
+        if ray_grad:
+            from . import pose
+            flat_o, flat_d = pose.ndc_rays(H, W, focal, 1.0, flat_o, flat_d)
+        else:
+            flat_o, flat_d = ndc_rays(H, W, focal, 1.0, flat_o, flat_d)
     rays = torch.cat((flat_o, flat_d), dim=-1)                      # nerf_process.py:229
     N = rays.shape[0]
     seed = _next_seed(seed)
@@ -315,7 +331,7 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
             train_stats = occ.add_stats(train_stats, train_occupancy.last_stats)
         elif training:                                              # train.py:53-54: one autograd node per slab
             parts.append(train_path.render_train(rays[i:j].contiguous(), model, opts, t_rand=tr, u=uu, seed=seed,
-                                                 ray_offset=int(ray_offset) + i, f16s=train_f16s, **_geometry_kw(geometry)))
+                                                 ray_offset=int(ray_offset) + i, f16s=train_f16s, **_geometry_kw(geometry, ray_grad)))
         else:
             parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False, occupancy, **_geometry_kw(geometry)))
     if train_occupancy is not None:

@@ -173,13 +173,22 @@ def wants_grad(model) -> bool:
             and any(p.requires_grad for p in model.parameters()))
 
 
+def wants_ray_grad(model, ray_grad: bool, *rays) -> bool:
+    """``ray_grad=True`` and one of the ray tensors carries a graph: the call goes to the training node even when no parameter requires
+    grad (a frozen model: pose estimation), and the node then runs the backward-data chain alone."""
+    return (bool(ray_grad) and torch.is_grad_enabled() and isinstance(model, torch.nn.Module)
+            and any(isinstance(r, torch.Tensor) and r.requires_grad for r in rays))
+
+
 def _flat(params) -> torch.Tensor:
     return torch.cat([p.detach().reshape(-1) for p in params]).float()
 
 
 class _RenderTrain(torch.autograd.Function):
     """rays (+ explicit randomness) and the two networks' parameters -> rgb_c, disp_c, rgb_f, disp_f; with ``cfg["geometry"]`` also
-    acc_c, depth_c, distortion_c, acc_f, depth_f, distortion_f, differentiable like the colours (geometry.node_forward / node_backward)."""
+    acc_c, depth_c, distortion_c, acc_f, depth_f, distortion_f, differentiable like the colours (geometry.node_forward / node_backward).
+    With ``cfg["ray_grad"]`` the backward also returns the gradient of ``rays`` (pose.input_grad on the deltas the backward-data chain left
+    in its workspace: no second backward pass), and a network none of whose parameters requires grad runs that chain alone (stage 1)."""
 
     @staticmethod
     def forward(ctx, st: _TrainState, rays, cfg: Dict, t_rand, u, z_override, *params):
@@ -226,23 +235,34 @@ class _RenderTrain(torch.autograd.Function):
         rays = saved[0]
         g_extra_c, g_extra_f = g_extra[:len(g_extra) // 2], g_extra[len(g_extra) // 2:]
 
-        def one(flat, blob, z, raw, stash, g_rgb, g_ext) -> List[Optional[torch.Tensor]]:
+        n_each = len(st.names)
+        need_rays = bool(ctx.cfg.get("ray_grad", False)) and ctx.needs_input_grad[1]
+        g_rays: List[torch.Tensor] = []
+
+        def one(flat, blob, z, raw, stash, g_rgb, g_ext, need_params: bool = True) -> List[Optional[torch.Tensor]]:
             if g_rgb is None and all(g is None for g in g_ext):
                 return [None] * len(st.names)
             f16s = ctx.f16s and net.W == 256
             f16s_dgrad = f16s and net.D <= 15              # the split-precision chain keeps a tile's ReLU' words of all layers in LDS
             blob_b = ops.pack_apply_f16s(net, st.map_bwd_f16s(), flat, st.f16s_out_of_range, backward=True) if f16s_dgrad else ops.pack_apply(st.map_bwd, flat)
             d_raw = geo.node_backward(ctx.cfg, raw, z, rays, g_rgb, g_ext)
-            grads, work = ops.mlp_backward(net, blob, blob_b, rays, z, d_raw, stash, f16s_wgrad=f16s, f16s_dgrad=f16s_dgrad)
+            grads, work = ops.mlp_backward(net, blob, blob_b, rays, z, d_raw, stash, stage=0 if need_params else 1, f16s_wgrad=f16s,
+                                           f16s_dgrad=f16s_dgrad)
             if f16s:
                 st.note_f16s_backward(work, z.shape[0], z.shape[1])
-            return st.split_grads(grads)
+            if need_rays:
+                from . import pose
+                g_rays.append(pose.input_grad(net, flat, rays, z, raw, d_raw, work))
+            return st.split_grads(grads) if need_params else [None] * len(st.names)
 
-        gc = one(*saved[1:6], g_rgb_c, g_extra_c)
-        gf = one(*saved[6:11], g_rgb_f, g_extra_f) if ctx.Nf > 0 else [None] * len(st.names)
+        # without ray_grad every call is what it was (stage 0); with it a network whose parameters are all frozen skips the weight gradients
+        frozen = [bool(ctx.cfg.get("ray_grad", False)) and not any(ctx.needs_input_grad[6 + k * n_each:6 + (k + 1) * n_each]) for k in (0, 1)]
+        gc = one(*saved[1:6], g_rgb_c, g_extra_c, not frozen[0])
+        gf = one(*saved[6:11], g_rgb_f, g_extra_f, not frozen[1]) if ctx.Nf > 0 else [None] * len(st.names)
         if ctx.f16s and net.W == 256 and any(g is not None for g in (g_rgb_c, g_rgb_f, *g_extra)):
             st.end_f16s_step()                                 # both nets' range words are folded: read them at the cadence
-        return (None, None, None, None, None, None, *gc, *gf)
+        g_r = None if not g_rays else (g_rays[0] if len(g_rays) == 1 else g_rays[0] + g_rays[1])
+        return (None, g_r, None, None, None, None, *gc, *gf)
 
 
 class _EmbeddedTrain(torch.autograd.Function):
@@ -267,13 +287,16 @@ class _EmbeddedTrain(torch.autograd.Function):
 
 
 def render_train(rays: torch.Tensor, model: torch.nn.Module, opts, *, t_rand=None, u=None, seed: int = 0, ray_offset: int = 0,
-                 z_override=None, det: Optional[bool] = None, f16s: bool = False, geometry: bool = False) -> Dict[str, torch.Tensor]:
+                 z_override=None, det: Optional[bool] = None, f16s: bool = False, geometry: bool = False,
+                 ray_grad: bool = False) -> Dict[str, torch.Tensor]:
     """Differentiable ``render_rays`` (nerf_process.py:185-216) for one slab of rays [n, 6].  ``f16s``: the two forward launches run in
     split precision (fp32-grade results, ~3x faster); the backward kernels are the fp32 ones.  ``geometry``: the dict also carries
-    ``acc_*``, ``depth_*`` and ``distortion_*`` per network, differentiable like the colours (geometry.py)."""
+    ``acc_*``, ``depth_*`` and ``distortion_*`` per network, differentiable like the colours (geometry.py).  ``ray_grad``: rays that require
+    grad are accepted and receive their gradient (pose.py: d rays, from there d pose); the depths stay constants, as in the reference.
+    Without it such rays are refused, so that a gradient is never dropped silently."""
     st = _state_for(model, f16s)                 # f16s: the 256-wide state (any netWidth <= 256 is scattered into it)
     dev = st.device
-    if isinstance(rays, torch.Tensor) and rays.requires_grad:
+    if isinstance(rays, torch.Tensor) and rays.requires_grad and not ray_grad:
         raise MiNerfError("rays require grad: the training path differentiates w.r.t. the MLP parameters only (the reference trains "
                           "nothing else, main.py:79-80); detach the rays, or a gradient would be dropped silently")
     rays = as_f32_dev(rays, dev)
@@ -288,6 +311,8 @@ def render_train(rays: torch.Tensor, model: torch.nn.Module, opts, *, t_rand=Non
     else:
         u = None
     cfg = {"near": float(opts.near), "far": float(opts.far), "Sc": Sc, "Nf": Nf, "det": bool(det), "f16s": bool(f16s), "geometry": bool(geometry)}
+    if ray_grad:
+        cfg["ray_grad"] = True
     params = st.params(model.model_coarse) + st.params(model.model_fine)
     rgb_c, disp_c, rgb_f, disp_f, *extra = _RenderTrain.apply(st, rays, cfg, t_rand, u, z_override, *params)
     return node_outputs(rgb_c, disp_c, rgb_f, disp_f, extra, Nf)
