@@ -33,9 +33,11 @@ def posenc_backward(b, g, L):
     return out
 
 
-def input_grad_rule(rays, z, raw, d_raw, delta_x0, delta_skip, delta_d, w_x0, w_skip, w_d, L_x, L_d, norm_term=True):
+def input_grad_rule(rays, z, raw, d_raw, delta_x0, delta_skip, delta_d, w_x0, w_skip, w_d, L_x, L_d, norm_term=True, points=None, view=None):
     """THE INPUT-GRADIENT RULE -> (d_rays [n,6], d_pts [P,3], d_view [n,3], d_emb [P, in_x + in_d]) in the dtype of the inputs.
-    ``norm_term=False`` leaves out the |d| of the sample distances (to show that it is needed)."""
+    ``norm_term=False`` leaves out the |d| of the sample distances (to show that it is needed).  ``points`` [P,3] / ``view`` [n,3]: where
+    sin / cos are evaluated, instead of the o + z d and d / |d| this dtype would form itself -- the fp32 values of the forward, so that
+    float64 differentiates the numbers the kernels saw (at |x| = 2048 half an ulp of x is 0.06 rad in the top band)."""
     n, S = z.shape
     in_x, in_d = 3 + 6 * L_x, 3 + 6 * L_d
     W = delta_x0.shape[1]
@@ -46,9 +48,10 @@ def input_grad_rule(rays, z, raw, d_raw, delta_x0, delta_skip, delta_d, w_x0, w_
     if delta_skip is not None:
         g_gx = g_gx + delta_skip @ w_skip[:, :in_x]
     g_gd = delta_d @ w_d[:, W:W + in_d]
-    x = (o[:, None, :] + d[:, None, :] * z[..., None]).reshape(-1, 3)
+    x = (o[:, None, :] + d[:, None, :] * z[..., None]).reshape(-1, 3) if points is None else points.reshape(-1, 3).to(rays.dtype)
+    v_enc = v if view is None else view.to(rays.dtype)
     g_x = posenc_backward(x, g_gx, L_x).reshape(n, S, 3)
-    g_v = posenc_backward(v[:, None, :].expand(n, S, 3).reshape(-1, 3), g_gd, L_d).reshape(n, S, 3)
+    g_v = posenc_backward(v_enc[:, None, :].expand(n, S, 3).reshape(-1, 3), g_gd, L_d).reshape(n, S, 3)
     G_o, G_v = g_x.sum(1), g_v.sum(1)
     G_d = (z[..., None] * g_x).sum(1) + (G_v - v * (v * G_v).sum(-1, keepdim=True)) / nrm
     if norm_term:
@@ -221,6 +224,250 @@ def test_e32_stays_below_one_percent_on_every_gpu_case():
             worst[(name, n, S)] = max(c.e32(k) for k in ("d_rays", "d_pts", "d_view", "d_emb"))
     print({k: f"{v:.1e}" for k, v in worst.items()})
     assert max(worst.values()) < 1e-2, worst
+
+
+# ---------------------------------------------------------------------------------------------------
+# input_grad_kernel on its own (tests/test_gpu_pose_edges.py): synthetic deltas, so that no backward-data error, no ReLU knife and no
+# network forward stand between the kernel and the rule.  Everything a case is made of comes from its seed, on the CPU.
+# ---------------------------------------------------------------------------------------------------
+CUS_MI355X = 256                                      # the CPU test builds the ray-loop cases for this many compute units
+OUTPUTS = ("d_rays", "d_pts", "d_view", "d_emb")
+
+#             name              D   W  skip L_x L_d      (skip -1: no layer concatenates gamma(x))
+EDGE_NETS = {"D8W256": (8, 256, 4, 10, 4), "D2W128": (2, 128, -1, 10, 4),
+             "D8W256-noskip": (8, 256, -1, 10, 4),    # 256 * 64 + 128 * 32 floats of LDS = 80 KiB exactly: the <= of the launch
+             "D3W128-s0": (3, 128, 0, 10, 4), "D8W256-s0": (8, 256, 0, 10, 4), "D8W256-s6": (8, 256, 6, 10, 4)}
+EDGE_L = ((1, 1), (5, 3), (9, 2), (10, 0), (0, 4))
+EDGE_NETS.update({f"D3W128-s0-L{lx}.{ld}": (3, 128, 0, lx, ld) for lx, ld in EDGE_L})
+BRANCH_ARRANGEMENTS = ("fast", "straddle", "slow", "one_slow0", "one_slow15", "one_slow16", "one_slow31", "one_fast0", "one_fast31")
+BRANCH_SIZES = ((5, 33), (5, 96), (1, 48))
+
+
+def far():
+    """tests/test_gpu_far_points.py: far_rays, check_arrangement, points, is_slow (its GPU tests are marked; the builders need no device)."""
+    from tests import test_gpu_far_points as F
+    return F
+
+
+def edge_specs(group=None):
+    """(group, net, kind, n, S) of every synthetic-delta case.  kind: a far_rays arrangement, or "pixel" (lego pixel rays, depths in [2, 6]).
+    n: a number, or (a, b) for a * CUs + b (the ray loop: more rays than four times the resident workgroups)."""
+    specs = []
+    for net in ("D8W256", "D2W128"):
+        specs += [("branch", net, arr, n, S) for arr in BRANCH_ARRANGEMENTS for n, S in BRANCH_SIZES] + [("branch", net, "edge", 6, 2)]
+    specs += [("loop", "D8W256", "pixel", (8, 3), 3), ("loop", "D3W128-s0", "pixel", (16, 3), 3), ("loop", "D8W256-noskip", "pixel", (16, 3), 3),
+              ("lds", "D8W256-noskip", "pixel", 5, 33)]
+    specs += [("maps", net, "pixel", n, S) for net in [f"D3W128-s0-L{lx}.{ld}" for lx, ld in EDGE_L] + ["D8W256-s0", "D8W256-s6"] for n, S in ((5, 33), (3, 7))]
+    specs += [("samples", "D2W128", "pixel", 1, 257), ("samples", "D2W128", "pixel", 2, 1024)]
+    specs += [("isolation", "D8W256", "pixel", 9, 40)]
+    return [s for s in specs if group is None or s[0] == group]
+
+
+def spec_id(spec):
+    group, net, kind, n, S = spec
+    return f"{group}-{net}-{kind}-{n if isinstance(n, int) else f'{n[0]}cus+{n[1]}'}x{S}"
+
+
+_EDGE_SD = {}
+
+
+def edge_sd(name):
+    """One synthetic state dict per network of EDGE_NETS (weights seed: the position in the table)."""
+    if name not in _EDGE_SD:
+        D, W, skip, L_x, L_d = EDGE_NETS[name]
+        skips = (skip,) if 0 <= skip and skip + 1 < D else ()
+        _EDGE_SD[name] = synthetic.make_state_dict(40 + sorted(EDGE_NETS).index(name), D, W, 3 + 6 * L_x, 3 + 6 * L_d, skips=skips)
+    return _EDGE_SD[name]
+
+
+def pinned(rays, z):
+    """(points [P,3], view [n,3]) in fp32 as the forward forms them: o + d * z with the product rounded, then the sum; d / |d|."""
+    d = rays[:, 3:]
+    return far().points(rays, z).reshape(-1, 3), d / torch.norm(d, dim=-1, keepdim=True)
+
+
+class SyntheticCase:
+    """What input_grad_kernel reads, drawn from one seed: rays and depths of ``kind``, randn deltas of the layers that read gamma(x) and
+    gamma(d), randn raw / d_raw, the weights of ``edge_sd``.  ``rule(dtype)`` is input_grad_rule at the pinned fp32 points."""
+
+    def __init__(self, spec, cus=CUS_MI355X):
+        import zlib
+        self.spec = spec
+        group, self.name, self.kind, n, S = spec
+        self.D, self.W, self.skip, self.L_x, self.L_d = EDGE_NETS[self.name]
+        self.has_skip = 0 <= self.skip and self.skip + 1 < self.D
+        self.in_x, self.in_d = 3 + 6 * self.L_x, 3 + 6 * self.L_d
+        self.n = n = n if isinstance(n, int) else n[0] * cus + n[1]
+        self.S = S
+        self.seed = seed = zlib.crc32(spec_id(spec).encode()) % 100000
+        if self.kind == "pixel":
+            self.rays, self.z = pixel_rays(n, seed % 12), depths(n, S, seed)
+        else:
+            self.rays, self.z = far().far_rays(self.kind, n, S)
+            far().check_arrangement(self.kind, self.rays, self.z)                  # both sides of the branch where the case claims them
+        g = torch.Generator().manual_seed(seed)
+        P, W = n * S, self.W
+        self.delta_x0 = torch.randn(P, W, generator=g)
+        self.delta_skip = torch.randn(P, W, generator=g) if self.has_skip else None
+        self.delta_d = torch.randn(P, W // 2, generator=g)
+        self.raw, self.d_raw = torch.randn(n, S, 4, generator=g), torch.randn(n, S, 4, generator=g)
+        self.sd = edge_sd(self.name)
+        self._memo = {}
+
+    def weights(self, dtype, prefix="model_fine."):
+        w = lambda k: torch.as_tensor(self.sd[prefix + k + ".weight"]).to(dtype)       # noqa: E731
+        return w("linear_x.0"), (w(f"linear_x.{self.skip + 1}") if self.has_skip else None), w("linear_d")
+
+    def rule(self, dtype, rays=None, z=None):
+        """{output: tensor} by the rule in ``dtype`` (other rays / depths: the same deltas on them)."""
+        key = dtype if rays is None and z is None else None
+        if key in self._memo:
+            return self._memo[key]
+        rays, z = self.rays if rays is None else rays, self.z if z is None else z
+        pts, view = pinned(rays, z)
+        t = lambda a: None if a is None else a.to(dtype)                                # noqa: E731
+        out = dict(zip(OUTPUTS, input_grad_rule(t(rays), t(z), t(self.raw), t(self.d_raw), t(self.delta_x0), t(self.delta_skip), t(self.delta_d),
+                                                *self.weights(dtype), self.L_x, self.L_d, points=pts, view=view)))
+        if key is not None:
+            self._memo[key] = out
+        return out
+
+    def e32(self):
+        """{output: the rule in fp32 against the rule in float64, relative to the largest entry}."""
+        r32, r64 = self.rule(torch.float32), self.rule(torch.float64)
+        return {k: rel_err(r32[k], r64[k]) for k in OUTPUTS}
+
+
+def poisoned(c):
+    """The isolation batch: ray 1 with a NaN origin component, ray 4 with an infinite depth at one sample, ray 6 with a zero direction.
+    Rays 0-3, 4-7 and 8 share a workgroup each, so every poisoned ray has clean neighbours."""
+    rays, z = c.rays.clone(), c.z.clone()
+    rays[1, 1] = float("nan")
+    z[4, 17] = float("inf")
+    rays[6, 3:] = 0.0
+    return rays, z, (1, 4, 6)
+
+
+def blind_sd(tag):
+    """The state dict of test_gpu_far_points.blind_net(tag), without its device blob."""
+    D, W, skip = far().NETS[tag]
+    skips = (skip,) if skip >= 0 else ()
+    sd = synthetic.make_state_dict(70 + D + W, D, W, skips=skips)
+    for net in ("model_coarse.", "model_fine."):
+        for layer in [0] + [s + 1 for s in skips if s + 1 < D]:
+            w = sd[f"{net}linear_x.{layer}.weight"].copy()
+            w[:, :3] = 0.0
+            sd[f"{net}linear_x.{layer}.weight"] = w
+    return sd
+
+
+CHAIN = {"tag": "d8w256", "arr": "straddle", "n": 5, "S": 33, "rays_seed": 4, "prefix": "model_fine."}
+
+
+def chain_inputs():
+    c = CHAIN
+    rays, z = far().far_rays(c["arr"], c["n"], c["S"], seed=c["rays_seed"])
+    far().check_arrangement(c["arr"], rays, z)
+    return rays, z, torch.randn(c["n"], c["S"], 3, generator=torch.Generator().manual_seed(11))
+
+
+def chain_autograd(sd, rays, z, g_rgb, dtype, keep=None):
+    """The chain case's comparator: autograd in ``dtype`` through gamma of the PINNED fp32 points and view directions (test_gpu_far_points.
+    gamma64) -> network -> rgb, differentiated down to the rays: the points enter as pinned + (x - x.detach()), whose value is the pinned
+    point and whose derivative is that of x = o + z d.  rgb is the network's colour output at every sample, ``g_rgb`` [n,S,3] its gradient:
+    composited, samples 25 units apart saturate alpha at once and 3 of the 165 points would carry any gradient, one of them beyond the
+    branch.  ``keep``: as PoseCase.autograd.  -> the dict of PoseCase.autograd."""
+    D, W, skip = far().NETS[CHAIN["tag"]]
+    n, S = z.shape
+    L_x, L_d, in_x, in_d = 10, 4, 63, 27
+    r = rays.to(dtype).clone().requires_grad_(True)
+    zt = z.to(dtype)
+    o, d = r[:, :3], r[:, 3:]
+    p32, v32 = pinned(rays, z)
+    x = (o[:, None, :] + d[:, None, :] * zt[..., None]).reshape(-1, 3)
+    v = d / torch.norm(d, dim=-1, keepdim=True)
+    pts = p32.to(dtype) + (x - x.detach())
+    view = v32.to(dtype) + (v - v.detach())
+    pts.retain_grad()
+    view.retain_grad()
+    emb = torch.cat([R.posenc(pts, L_x), R.posenc(view[:, None, :].expand(n, S, 3).reshape(-1, 3), L_d)], -1)
+    emb.retain_grad()
+    taps = {}
+    raw = R.mlp_forward(sd, CHAIN["prefix"], emb, D, in_x, in_d, skips=(skip,), dtype=dtype, taps=taps).reshape(n, S, 4)
+    if keep is not None:
+        raw = torch.where(keep.view(n, S, 1), raw, raw.detach())
+    raw.retain_grad()
+    (raw[..., :3] * g_rgb.to(dtype)).sum().backward()
+    return {"raw": raw.detach(), "pre": {k: t.detach() for k, t in taps.items() if k != "feat"}, "d_rays": r.grad, "d_raw": raw.grad, "d_emb": emb.grad,
+            "d_pts": pts.grad, "d_view": view.grad, "delta_x0": taps["a0"].grad, "delta_skip": taps[f"a{skip + 1}"].grad, "delta_d": taps["ad"].grad}
+
+
+def test_every_synthetic_edge_case_is_well_posed():
+    """Every case of tests/test_gpu_pose_edges.py built from its seed: the rule in fp32 is within 1e-2 of the rule in float64 on every output
+    (the GPU bar is max(3 e32, 2e-4)), the far arrangements hold what they claim (SyntheticCase asserts it), the ray-loop cases have more rays
+    than four times the resident workgroups of a 256-CU device, and the poisoned rays of the isolation case are non-finite in the float64
+    rule exactly where the kernel is expected to be."""
+    worst = {}
+    for spec in edge_specs():
+        c = SyntheticCase(spec)
+        e = c.e32()
+        print(f"{spec_id(spec)}: " + "  ".join(f"{k} {v:.1e}" for k, v in e.items()))
+        assert all(np.isfinite(v) for v in e.values()), (spec, e)
+        worst[spec_id(spec)] = max(e.values())
+        if spec[0] == "loop":
+            lds = ((2 if c.has_skip else 1) * c.W * 64 + (c.W // 2) * 32) * 4
+            assert c.n > 4 * CUS_MI355X * (2 if lds <= 80 * 1024 else 1), (spec, lds)
+    assert max(worst.values()) < 1e-2, {k: v for k, v in worst.items() if v >= 1e-2}
+    c = SyntheticCase(edge_specs("lds")[0])
+    assert ((2 if c.has_skip else 1) * c.W * 64 + (c.W // 2) * 32) * 4 == 80 * 1024
+    # isolation: what the rule leaves non-finite
+    c = SyntheticCase(edge_specs("isolation")[0])
+    rays, z, bad = poisoned(c)
+    ref = c.rule(torch.float64, rays, z)
+    S = c.S
+    fin = {k: torch.isfinite(v) for k, v in ref.items()}
+    clean = [i for i in range(c.n) if i not in bad]
+    assert all(bool(fin["d_rays"][i].all() and fin["d_view"][i].all() and fin["d_pts"][i * S:(i + 1) * S].all()) for i in clean) and bool(fin["d_emb"].all())
+    assert fin["d_rays"][1].tolist() == [True, False, True, True, False, True] and not bool(fin["d_pts"][S:2 * S, 1].any())     # the NaN origin component
+    assert not bool(fin["d_rays"][4].any()) and not bool(fin["d_pts"][4 * S + 17].any()) and bool(fin["d_pts"][4 * S:4 * S + 17].all())   # the infinite depth
+    assert fin["d_rays"][6].tolist() == [True] * 3 + [False] * 3 and not bool(fin["d_view"][6].any()) and bool(fin["d_pts"][6 * S:7 * S].all())   # d = 0
+
+
+def test_the_chain_case_is_well_posed_and_the_pinned_rule_is_its_autograd():
+    """blind d8w256 at the branch: fp32 autograd at the pinned points is within 1e-2 of float64 on every output, gradient reaches points on
+    both sides of the branch, and input_grad_rule with points= / view= on float64's own deltas reproduces float64 autograd."""
+    rays, z, g_rgb = chain_inputs()
+    sd = blind_sd(CHAIN["tag"])
+    a64, a32 = chain_autograd(sd, rays, z, g_rgb, torch.float64), chain_autograd(sd, rays, z, g_rgb, torch.float32)
+    e32 = {k: rel_err(a32[k], a64[k]) for k in OUTPUTS}
+    slow = far().is_slow(rays, z).reshape(-1)
+    live = a64["d_pts"].abs().max(-1)[0] > 1e-6 * float(a64["d_pts"].abs().max())
+    print("chain e32:", {k: f"{v:.1e}" for k, v in e32.items()}, "points with gradient: fast", int((live & ~slow).sum()), "slow", int((live & slow).sum()))
+    assert max(e32.values()) < 1e-2, e32
+    assert int((live & slow).sum()) >= 5 and int((live & ~slow).sum()) >= 5
+    w = lambda k: torch.as_tensor(sd[CHAIN["prefix"] + k + ".weight"]).double()            # noqa: E731
+    pts, view = pinned(rays, z)
+    got = input_grad_rule(rays.double(), z.double(), a64["raw"], a64["d_raw"], a64["delta_x0"], a64["delta_skip"], a64["delta_d"], w("linear_x.0"),
+                          w("linear_x.5"), w("linear_d"), 10, 4, points=pts, view=view)
+    errs = {k: rel_err(g, a64[k]) for k, g in zip(OUTPUTS, got)}
+    assert max(errs.values()) < 1e-10, errs
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_NETS))
+def test_weight_blocks_for_every_skip_layer_and_encoding_of_the_edge_cases(name):
+    from nerf_pytorch_paeng_amd import ops, pose
+    D, W, skip, L_x, L_d = EDGE_NETS[name]
+    c = SyntheticCase(("maps", name, "pixel", 1, 2))
+    net = ops.make_net(D, W, skip if c.has_skip else -1, L_x, L_d)
+    flat = ops.flatten_params(c.sd, "model_fine.", net)
+    blocks = pose.weight_blocks(net)
+    for key, w in zip(("x0", "skip", "d"), c.weights(torch.float32)):
+        if w is None:
+            assert blocks[key] is None
+            continue
+        off, ld = blocks[key]
+        assert ld == w.shape[1] and torch.equal(flat[off:off + w.numel()].view_as(w), w), (name, key)
+    assert (blocks["skip"] is not None) == c.has_skip
 
 
 def _ndc_inputs(n, seed=0, broadcast=False):
