@@ -7,9 +7,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
 
-from ._lib import MiNerfError
+from ._lib import loader
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmi_nerf_iqa.so")
@@ -29,40 +28,7 @@ SIGNATURES = {
     "mi_iqa_ssim": (_I, [_P, _P, _I64, _I, _I, _I, _U32, _P, _P, _P, _SZ, _P]),
 }
 
-_lib: Optional[C.CDLL] = None
-
-
-def lib() -> C.CDLL:
-    """Load (once) and return the shared library; raise loudly if it is not there."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise MiNerfError(
-                f"{LIB_PATH} not found: build it with `python -m nerf_pytorch_paeng_amd.build` "
-                "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback for this path.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise MiNerfError(f"{LIB_PATH} does not export {name}: stale build?") from e
-            fn.restype, fn.argtypes = res, args
-        v = handle.mi_iqa_abi_version()
-        if v != ABI_VERSION:
-            raise MiNerfError(f"ABI mismatch: library {v}, binding {ABI_VERSION}")
-        _lib = handle
-    return _lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = lib().mi_iqa_last_error()
-        raise MiNerfError(f"{what} failed (status {rc}): {msg.decode() if msg else '?'}")
-
-
-def last_error() -> str:
-    msg = lib().mi_iqa_last_error()
-    return msg.decode() if msg else ""
+lib, check, last_error = loader(globals(), "mi_iqa")
 
 
 def ssim_window():

@@ -21,6 +21,47 @@ class MiNerfError(RuntimeError):
     pass
 
 
+def loader(module: dict, prefix: str, first=None):
+    """(lib, check, last_error) of one shared library, for the binding module whose globals() are passed: its LIB_PATH, SIGNATURES and
+    ABI_VERSION are read when lib() first runs, so a tool may still assign LIB_PATH after the import.  `prefix` names the library's
+    PREFIX_abi_version / PREFIX_last_error; `first` is the lib() of the library this one links against, loaded before it."""
+    handle: Optional[C.CDLL] = None
+
+    def lib() -> C.CDLL:
+        """Load (once) and return the shared library; raise loudly if it is not there."""
+        nonlocal handle
+        if handle is None:
+            path = module["LIB_PATH"]
+            if not os.path.exists(path):
+                raise MiNerfError(
+                    f"{path} not found: build it with `python -m nerf_pytorch_paeng_amd.build` "
+                    "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback for this path.")
+            if first is not None:
+                first()                                 # the copy this library's rpath resolves to
+            h = C.CDLL(path)
+            for name, (res, args) in module["SIGNATURES"].items():
+                try:
+                    fn = getattr(h, name)
+                except AttributeError as e:
+                    raise MiNerfError(f"{path} does not export {name}: stale build?") from e
+                fn.restype, fn.argtypes = res, args
+            v = getattr(h, prefix + "_abi_version")()
+            if v != module["ABI_VERSION"]:
+                raise MiNerfError(f"ABI mismatch: library {v}, binding {module['ABI_VERSION']}")
+            handle = h
+        return handle
+
+    def last_error() -> str:
+        msg = getattr(lib(), prefix + "_last_error")()
+        return msg.decode() if msg else ""
+
+    def check(rc: int, what: str) -> None:
+        if rc != 0:
+            raise MiNerfError(f"{what} failed (status {rc}): {last_error() or '?'}")
+
+    return lib, check, last_error
+
+
 class Net(C.Structure):          # mi_nerf_net
     _fields_ = [("D", C.c_int32), ("W", C.c_int32), ("skip", C.c_int32), ("L_x", C.c_int32), ("L_d", C.c_int32)]
 
@@ -124,35 +165,7 @@ SIGNATURES = {
     "mi_nerf_selftest_mfma": (_I, [_P]),
 }
 
-_lib: Optional[C.CDLL] = None
-
-
-def lib() -> C.CDLL:
-    """Load (once) and return the shared library; raise loudly if it is not there."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise MiNerfError(
-                f"{LIB_PATH} not found: build it with `python -m nerf_pytorch_paeng_amd.build` "
-                "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback for this path.")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise MiNerfError(f"{LIB_PATH} does not export {name}: stale build?") from e
-            fn.restype, fn.argtypes = res, args
-        v = handle.mi_nerf_abi_version()
-        if v != ABI_VERSION:
-            raise MiNerfError(f"ABI mismatch: library {v}, binding {ABI_VERSION}")
-        _lib = handle
-    return _lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = lib().mi_nerf_last_error()
-        raise MiNerfError(f"{what} failed (status {rc}): {msg.decode() if msg else '?'}")
+lib, check, last_error = loader(globals(), "mi_nerf")
 
 
 def dev_ptr(t: Optional[torch.Tensor], name: str = "tensor", dtype=torch.float32, align: int = 4) -> Optional[int]:

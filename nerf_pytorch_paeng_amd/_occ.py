@@ -8,10 +8,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
 
 from . import _lib
-from ._lib import MiNerfError, Net, RenderCfg
+from ._lib import Net, RenderCfg, loader
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmi_nerf_occ.so")
@@ -54,38 +53,4 @@ SIGNATURES = {
     "mi_occ_render_rays": (_I, [_NETP, _P, _P, _CFGP, _GRIDP, _P, _P, _P, _I64, _P, _P, _P, _SZ, _P, _P, _P, _P, C.POINTER(Stats), _P]),
 }
 
-_handle: Optional[C.CDLL] = None
-
-
-def lib() -> C.CDLL:
-    """Load (once) and return the shared library; raise loudly if it is not there."""
-    global _handle
-    if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise MiNerfError(
-                f"{LIB_PATH} not found: build it with `python -m nerf_pytorch_paeng_amd.build` "
-                "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback for this path.")
-        _lib.lib()                                  # libmi_nerf.so first: the copy this library's rpath resolves to
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise MiNerfError(f"{LIB_PATH} does not export {name}: stale build?") from e
-            fn.restype, fn.argtypes = res, args
-        v = handle.mi_occ_abi_version()
-        if v != ABI_VERSION:
-            raise MiNerfError(f"ABI mismatch: library {v}, binding {ABI_VERSION}")
-        _handle = handle
-    return _handle
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = lib().mi_occ_last_error()
-        raise MiNerfError(f"{what} failed (status {rc}): {msg.decode() if msg else '?'}")
-
-
-def last_error() -> str:
-    msg = lib().mi_occ_last_error()
-    return msg.decode() if msg else ""
+lib, check, last_error = loader(globals(), "mi_occ", first=_lib.lib)

@@ -6,17 +6,7 @@
 namespace minerf {
 
 // ---- error plumbing --------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-int hip_fail(hipError_t e, const char* what) {
-    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
-    return MI_NERF_EHIP;
-}
+ABI_ERROR_STATE(, MI_NERF_EHIP)          // external linkage: declared in common.h for the other translation units
 
 // ---- per-device launch state -----------------------------------------------------------------------
 int device_cus() {

@@ -1,35 +1,22 @@
-// common.h -- error plumbing and small device helpers shared by all translation units.
+// common.h -- libmi_nerf.so's names for the error plumbing of abi_error.h, and small device helpers shared by all translation units.
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/mi_nerf.h"
+#include "abi_error.h"
 
 namespace minerf {
 
+// libmi_nerf.so's one message buffer lives in api.hip (ABI_ERROR_STATE of abi_error.h); every translation unit writes it through these
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 
-#define MN_CHECK_ARG(cond, ...)                  \
-    do {                                         \
-        if (!(cond)) {                           \
-            ::minerf::set_error(__VA_ARGS__);    \
-            return MI_NERF_EINVAL;               \
-        }                                        \
-    } while (0)
+#define MN_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::minerf, MI_NERF_EINVAL, cond, __VA_ARGS__)
+#define MN_HIP(call) ABI_HIP(::minerf, call, #call)
+#define MN_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::minerf, name)
 
-#define MN_HIP(call)                                                   \
-    do {                                                               \
-        hipError_t e__ = (call);                                       \
-        if (e__ != hipSuccess) return ::minerf::hip_fail(e__, #call);  \
-    } while (0)
-
-#define MN_LAUNCH_CHECK(name)                                                \
-    do {                                                                     \
-        hipError_t e__ = hipGetLastError();                                  \
-        if (e__ != hipSuccess) return ::minerf::hip_fail(e__, "launch " name); \
-    } while (0)
+// blocks of `per_block` items that cover n
+static inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // Per-DEVICE launch state (a process may drive several GPUs: the 160 KB dynamic-LDS opt-in is an attribute of the function ON a
 // device, and the CU count is a property of the device): small arrays indexed by the current device ordinal.

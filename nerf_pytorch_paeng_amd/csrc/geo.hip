@@ -11,55 +11,24 @@
 // Forward quantities are recomputed in the backward; no LDS, no scratch, no atomic.  Compiled with -ffp-contract=off like stages.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/mi_nerf_geo.h"
+#include "abi_error.h"
 #include "common.h"
 #include "stage_dev.h"
 
 namespace migeo {
 
+using minerf::blocks_for;
 using minerf::f32x4;
 using minerf::wave_excl_prod;
+using minerf::wave_excl_suffix_sum;
 using minerf::wave_excl_sum;
 using minerf::wave_sum;
 
-// ---- error plumbing (the conventions of api.hip) -----------------------------------------------------
-static thread_local char g_err[512] = "";
-static void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-static int hip_fail(hipError_t e, const char* what) {
-    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
-    return MI_GEO_EHIP;
-}
-#define GEO_CHECK_ARG(cond, ...)             \
-    do {                                     \
-        if (!(cond)) {                       \
-            ::migeo::set_error(__VA_ARGS__); \
-            return MI_GEO_EINVAL;            \
-        }                                    \
-    } while (0)
-#define GEO_LAUNCH_CHECK(name)                                                \
-    do {                                                                      \
-        hipError_t e__ = hipGetLastError();                                   \
-        if (e__ != hipSuccess) return ::migeo::hip_fail(e__, "launch " name); \
-    } while (0)
-
-// exclusive SUFFIX sum across the 64 lanes (sum of the lanes above this one), Kogge-Stone on __shfl_down: the twin of wave_excl_sum
-__device__ __forceinline__ float wave_excl_suffix_sum(float v, int lane) {
-    float inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float o = __shfl_down(inc, d, 64);
-        if (lane + d < 64) inc += o;
-    }
-    const float e = __shfl_down(inc, 1, 64);
-    return lane == 63 ? 0.0f : e;
-}
+// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
+ABI_ERROR_STATE(static, MI_GEO_EHIP)
+#define GEO_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::migeo, MI_GEO_EINVAL, cond, __VA_ARGS__)
+#define GEO_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::migeo, name)
 
 // THE DISTORTION RULE, the interval half: t_i, delta_i, m_i of one sample from its depth and the next one's (zn == zv for the last sample)
 __device__ __forceinline__ void interval(float zv, float zn, float near_, float span, float& m, float& delta) {
@@ -276,8 +245,6 @@ __global__ __launch_bounds__(256) void geo_composite_bwd_kernel(const float* __r
         }
     }
 }
-
-static inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // what both entries check before any HIP call
 static int check_common(const char* who, const float* raw, const float* z, const float* rays, int ray_stride, int64_t n, int S, float near_,

@@ -11,36 +11,15 @@
 // Arithmetic: fp64 moments of the fp32 pixels (mi_nerf_iqa.h says why); the kernel is bound by its fp64 FMAs, not by HBM.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/mi_nerf_iqa.h"
+#include "abi_error.h"
 
 namespace miiqa {
 
-// ---- error plumbing (the conventions of api.hip) -----------------------------------------------------
-static thread_local char g_err[512] = "";
-static void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-static int hip_fail(hipError_t e, const char* what) {
-    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
-    return MI_IQA_EHIP;
-}
-#define IQA_CHECK_ARG(cond, ...)               \
-    do {                                       \
-        if (!(cond)) {                         \
-            ::miiqa::set_error(__VA_ARGS__);   \
-            return MI_IQA_EINVAL;              \
-        }                                      \
-    } while (0)
-#define IQA_LAUNCH_CHECK(name)                                              \
-    do {                                                                    \
-        hipError_t e__ = hipGetLastError();                                 \
-        if (e__ != hipSuccess) return ::miiqa::hip_fail(e__, "launch " name); \
-    } while (0)
+// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
+ABI_ERROR_STATE(static, MI_IQA_EHIP)
+#define IQA_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::miiqa, MI_IQA_EINVAL, cond, __VA_ARGS__)
+#define IQA_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::miiqa, name)
 
 // ---- geometry ----------------------------------------------------------------------------------
 constexpr int TAPS = MI_IQA_SSIM_TAPS;      // 11

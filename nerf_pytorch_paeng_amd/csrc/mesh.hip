@@ -13,46 +13,17 @@
 // numpy restatement in tests/test_mesh_cpu.py computes the rule a second time, from the header, without a table.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/mi_nerf_mesh.h"
+#include "abi_error.h"
 
 namespace mimesh {
 
-// ---- error plumbing (the conventions of api.hip) -----------------------------------------------------
-static thread_local char g_err[768] = "";
-static void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-static int hip_fail(hipError_t e, const char* what) {
-    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
-    return MI_MESH_EHIP;
-}
-// a failed call into libmi_nerf.so: its status becomes ours (EINVAL stays EINVAL), its text is carried over
-static int nerf_fail(int rc, const char* what) {
-    set_error("%s failed (status %d): %s", what, rc, mi_nerf_last_error());
-    return rc == MI_NERF_EINVAL ? MI_MESH_EINVAL : MI_MESH_EHIP;
-}
-#define MESH_CHECK_ARG(cond, ...)              \
-    do {                                       \
-        if (!(cond)) {                         \
-            ::mimesh::set_error(__VA_ARGS__);  \
-            return MI_MESH_EINVAL;             \
-        }                                      \
-    } while (0)
-#define MESH_LAUNCH_CHECK(name)                                               \
-    do {                                                                      \
-        hipError_t e__ = hipGetLastError();                                   \
-        if (e__ != hipSuccess) return ::mimesh::hip_fail(e__, "launch " name); \
-    } while (0)
-#define MESH_NERF(call)                                                  \
-    do {                                                                 \
-        int rc__ = (call);                                               \
-        if (rc__ != MI_NERF_OK) return ::mimesh::nerf_fail(rc__, #call); \
-    } while (0)
+// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
+ABI_ERROR_STATE(static, MI_MESH_EHIP)
+ABI_NERF_FAIL(MI_MESH_EINVAL, MI_MESH_EHIP)
+#define MESH_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::mimesh, MI_MESH_EINVAL, cond, __VA_ARGS__)
+#define MESH_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::mimesh, name)
+#define MESH_NERF(call) ABI_NERF(::mimesh, call, #call)
 
 constexpr int SCAN_TILE = MI_MESH_SCAN_TILE;          // 256 threads x 4 elements
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }

@@ -16,51 +16,18 @@
 // occ_count_kernel     popcount of the grid's cells
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/mi_nerf_occ.h"
+#include "abi_error.h"
 
 namespace miocc {
 
-// ---- error plumbing (the conventions of api.hip) -----------------------------------------------------
-static thread_local char g_err[768] = "";
-static void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-static int hip_fail(hipError_t e, const char* what) {
-    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
-    return MI_OCC_EHIP;
-}
-// a failed call into libmi_nerf.so: its status becomes ours (EINVAL stays EINVAL), its text is carried over
-static int nerf_fail(int rc, const char* what) {
-    set_error("%s failed (status %d): %s", what, rc, mi_nerf_last_error());
-    return rc == MI_NERF_EINVAL ? MI_OCC_EINVAL : MI_OCC_EHIP;
-}
-#define OCC_CHECK_ARG(cond, ...)               \
-    do {                                       \
-        if (!(cond)) {                         \
-            ::miocc::set_error(__VA_ARGS__);   \
-            return MI_OCC_EINVAL;              \
-        }                                      \
-    } while (0)
-#define OCC_HIP(call)                                                   \
-    do {                                                                \
-        hipError_t e__ = (call);                                        \
-        if (e__ != hipSuccess) return ::miocc::hip_fail(e__, #call);    \
-    } while (0)
-#define OCC_LAUNCH_CHECK(name)                                              \
-    do {                                                                    \
-        hipError_t e__ = hipGetLastError();                                 \
-        if (e__ != hipSuccess) return ::miocc::hip_fail(e__, "launch " name); \
-    } while (0)
-#define OCC_NERF(call)                                          \
-    do {                                                        \
-        int rc__ = (call);                                      \
-        if (rc__ != MI_NERF_OK) return ::miocc::nerf_fail(rc__, #call); \
-    } while (0)
+// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
+ABI_ERROR_STATE(static, MI_OCC_EHIP)
+ABI_NERF_FAIL(MI_OCC_EINVAL, MI_OCC_EHIP)
+#define OCC_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::miocc, MI_OCC_EINVAL, cond, __VA_ARGS__)
+#define OCC_HIP(call) ABI_HIP(::miocc, call, #call)
+#define OCC_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::miocc, name)
+#define OCC_NERF(call) ABI_NERF(::miocc, call, #call)
 
 constexpr int TILE = MI_OCC_TILE;
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }

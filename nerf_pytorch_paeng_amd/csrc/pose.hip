@@ -1,6 +1,6 @@
 // pose.hip -- libmi_nerf_pose.so (include/mi_nerf_pose.h): gradients of the training path with respect to rays and camera poses.  A library
-// of its own: it shares common.h with libmi_nerf.so at compile time (the sin / cos of the forward's positional encoding, so that the
-// backward differentiates the numbers the forward produced) and nothing at link time.
+// of its own: it shares common.h / stage_dev.h with libmi_nerf.so at compile time (the sin / cos of the forward's positional encoding, so
+// that the backward differentiates the numbers the forward produced; wave_sum) and nothing at link time.
 //
 //   input_grad_kernel<W>        one 64-lane wavefront per ray.  Per 32-sample tile: [32 points][64 + 32 columns] = delta rows x the three
 //                               narrow weight blocks on v_mfma_f32_32x32x2_f32 (weights staged once per workgroup in LDS, delta rows read
@@ -13,10 +13,10 @@
 // No atomic, no host synchronisation, no allocation.  Compiled with -ffp-contract=off like stages.hip: x = o + z d is the forward's x.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/mi_nerf_pose.h"
+#include "abi_error.h"
 #include "common.h"
+#include "stage_dev.h"
 
 namespace mipose {
 
@@ -25,42 +25,14 @@ using minerf::f32x4;
 using minerf::SINCOS_FAST_LIMIT;
 using minerf::sin_cos_fast;
 using minerf::sin_cos_slow;
+using minerf::wave_sum;
 
-// ---- error plumbing (the conventions of api.hip) -----------------------------------------------------
-static thread_local char g_err[512] = "";
-static void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-static int hip_fail(hipError_t e, const char* what) {
-    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
-    return MI_POSE_EHIP;
-}
-#define POSE_CHECK_ARG(cond, ...)             \
-    do {                                      \
-        if (!(cond)) {                        \
-            ::mipose::set_error(__VA_ARGS__); \
-            return MI_POSE_EINVAL;            \
-        }                                     \
-    } while (0)
-#define POSE_HIP(call)                                                \
-    do {                                                              \
-        hipError_t e__ = (call);                                      \
-        if (e__ != hipSuccess) return ::mipose::hip_fail(e__, #call); \
-    } while (0)
-#define POSE_LAUNCH_CHECK(name)                                                \
-    do {                                                                       \
-        hipError_t e__ = hipGetLastError();                                    \
-        if (e__ != hipSuccess) return ::mipose::hip_fail(e__, "launch " name); \
-    } while (0)
+// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
+ABI_ERROR_STATE(static, MI_POSE_EHIP)
+#define POSE_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::mipose, MI_POSE_EINVAL, cond, __VA_ARGS__)
+#define POSE_HIP(call) ABI_HIP(::mipose, call, #call)
+#define POSE_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::mipose, name)
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 // sum over the 32 lanes of this lane's half of the wave
 __device__ __forceinline__ float half_sum(float v) {
 #pragma unroll

@@ -11,36 +11,15 @@
 // compares -- and a lane owns nothing but its point.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/mi_nerf_scene.h"
+#include "abi_error.h"
 
 namespace miscene {
 
-// ---- error plumbing (the conventions of api.hip) -----------------------------------------------------
-static thread_local char g_err[512] = "";
-static void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-static int hip_fail(hipError_t e, const char* what) {
-    set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
-    return MI_SCENE_EHIP;
-}
-#define SCENE_CHECK_ARG(cond, ...)             \
-    do {                                       \
-        if (!(cond)) {                         \
-            ::miscene::set_error(__VA_ARGS__); \
-            return MI_SCENE_EINVAL;            \
-        }                                      \
-    } while (0)
-#define SCENE_LAUNCH_CHECK(name)                                                \
-    do {                                                                        \
-        hipError_t e__ = hipGetLastError();                                     \
-        if (e__ != hipSuccess) return ::miscene::hip_fail(e__, "launch " name); \
-    } while (0)
+// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
+ABI_ERROR_STATE(static, MI_SCENE_EHIP)
+#define SCENE_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::miscene, MI_SCENE_EINVAL, cond, __VA_ARGS__)
+#define SCENE_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::miscene, name)
 
 constexpr long long MAX_POINTS = 1LL << 39;      // 2^31 blocks of 256 threads
 

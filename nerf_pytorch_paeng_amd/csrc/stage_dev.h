@@ -36,6 +36,17 @@ __device__ __forceinline__ float wave_excl_sum(float v, int lane) {
     const float e = __shfl_up(inc, 1, 64);
     return lane == 0 ? 0.0f : e;
 }
+// exclusive SUFFIX sum across the 64 lanes (sum of the lanes above this one), Kogge-Stone on __shfl_down: the twin of wave_excl_sum
+__device__ __forceinline__ float wave_excl_suffix_sum(float v, int lane) {
+    float inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float o = __shfl_down(inc, d, 64);
+        if (lane + d < 64) inc += o;
+    }
+    const float e = __shfl_down(inc, 1, 64);
+    return lane == 63 ? 0.0f : e;
+}
 
 // ------------------------------------------------------------------------------------------------
 // alpha compositing: one wavefront per ray, lane l owns samples [l*C, (l+1)*C)

@@ -198,18 +198,6 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
     composite_ray<C>(raw, z, rays, ray_stride, ray, S, lane, rgb_o, disp_o, acc_o, w_o, depth_o, nullptr);
 }
 
-// exclusive SUFFIX sum across the 64 lanes (sum of the lanes above this one), Kogge-Stone on __shfl_down
-__device__ __forceinline__ float wave_excl_suffix_sum(float v, int lane) {
-    float inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float o = __shfl_down(inc, d, 64);
-        if (lane + d < 64) inc += o;
-    }
-    const float e = __shfl_down(inc, 1, 64);
-    return lane == 63 ? 0.0f : e;
-}
-
 // ------------------------------------------------------------------------------------------------
 // alpha compositing, backward: d rgb_map [n,3] -> d raw [n,S,4]   (what autograd does for
 // nerf_process.py:89-140 when the loss reads rgb_map only, train.py:59-66; depths are constants:
@@ -339,7 +327,6 @@ __global__ __launch_bounds__(256) void composite_fine_z_kernel(const float* __re
 // host entry points (called from api.cpp)
 // ------------------------------------------------------------------------------------------------
 constexpr int MAX_LDS_FLOATS_PER_RAY = 64 * 1024 / 4 / 4;      // 4 rays per block share 64 KB: 4096 floats per ray
-static inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 int stage_make_o_d(int W, int H, const float k4[4], const float pose12[12], int row0, int n_rows, float* o, float* d,
                    hipStream_t st) {
