@@ -5,6 +5,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
+                                             [--fused-adam] [--lr-min LR --warmup STEPS]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -13,7 +14,10 @@ network and written as a binary PLY.  No counterpart in the reference.  ``--trai
 occupancy grid is baked from the model (128^3 cells; ``--scene solid``: the box +-1.5 with everything outside it skipped, otherwise a box that
 holds every sample) and the remaining steps skip the samples it marks empty (occupancy_train.py), re-baking every EVERY steps (0: never).
 ``--geometry ACC:DEPTH:DIST``: the weights of the opacity, depth and distortion losses (geometry.py; e.g. 0.1:0:0.01); ACC and DEPTH are
-supervised by the analytic scene's own opacity and depth, so they need ``--scene solid``.
+supervised by the analytic scene's own opacity and depth, so they need ``--scene solid``.  ``--fused-adam``: optim.FusedAdam (one launch per
+step, skipping a step whose gradients are not finite) instead of torch.optim.Adam.  ``--lr-min LR`` / ``--warmup STEPS``: the reference's
+schedule (main.py:83-90, optim.CosineAnnealingWarmupRestarts) over one cycle of ``--steps``, from LR up to 5e-4 in STEPS steps and back; with
+none of the three the run is what it was.
 """
 import argparse
 import os
@@ -45,7 +49,12 @@ def main(argv=None):
     ap.add_argument("--mesh-box", type=float, default=1.5, help="the lattice spans +-this on every axis")
     ap.add_argument("--train-occupancy", default=None, metavar="WARMUP:EVERY", help="train with an occupancy grid baked after WARMUP full steps, re-baked every EVERY steps")
     ap.add_argument("--geometry", default=None, metavar="ACC:DEPTH:DIST", help="weights of the opacity, depth and distortion losses (ACC, DEPTH: --scene solid only)")
+    ap.add_argument("--fused-adam", action="store_true", help="optim.FusedAdam instead of torch.optim.Adam")
+    ap.add_argument("--lr-min", type=float, default=None, help="warm-up cosine schedule from this rate up to 5e-4 and back over --steps")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps of the schedule (default with --lr-min: a twentieth of --steps)")
     a = ap.parse_args(argv)
+    if a.warmup is not None and not 0 <= a.warmup < a.steps:
+        ap.error("--warmup takes a number of steps below --steps")
     geometry = None
     if a.geometry is not None:
         try:
@@ -91,7 +100,16 @@ def main(argv=None):
     i_train, i_test = list(range(a.views)), [a.views, a.views + 1]
 
     model = NeRF(8, a.net_width, 63, 27, skips=[4]).to(dev)                                      # main.py:67-73
-    optimizer = torch.optim.Adam(model.parameters(), lr=5e-4, betas=(0.9, 0.999))                # main.py:79-80
+    if a.fused_adam:
+        from nerf_pytorch_paeng_amd.optim import FusedAdam
+        optimizer = FusedAdam(model.parameters(), lr=5e-4, betas=(0.9, 0.999), skip_nonfinite=True)
+    else:
+        optimizer = torch.optim.Adam(model.parameters(), lr=5e-4, betas=(0.9, 0.999))            # main.py:79-80
+    scheduler = None
+    if a.lr_min is not None or a.warmup is not None:                                             # main.py:83-90
+        from nerf_pytorch_paeng_amd.optim import CosineAnnealingWarmupRestarts
+        scheduler = CosineAnnealingWarmupRestarts(optimizer, first_cycle_steps=a.steps + 1, max_lr=5e-4, min_lr=5e-5 if a.lr_min is None else a.lr_min,
+                                                  warmup_steps=a.steps // 20 if a.warmup is None else a.warmup)
     criterion = torch.nn.MSELoss()
     getter = harness.global_batch(images, K, poses, i_train, (H, W), dev)                        # main.py:92-106
     t0 = time.perf_counter()
@@ -105,6 +123,8 @@ def main(argv=None):
             opts.occupancy_bake_args = {"f16s": a.precision == "f16s"}
             print(f"step {i:6d}  occupancy grid baked: {opts.train_occupancy.fraction():.4f} of the cells occupied", flush=True)
         out = harness.train(i, i_train, images, (K, poses.numpy()), (H, W), model, criterion, posenc, optimizer, getter, None, opts, log_dir=a.out)
+        if scheduler is not None:
+            scheduler.step()                                                                     # main.py:161
         if i % opts.idx_print == 0:
             torch.cuda.synchronize()
             print(f"step {i:6d}  loss {float(out['loss']):.5f}  psnr_f {float(out['psnr_f']):.2f} dB  {(time.perf_counter() - t0) / i * 1e3:.1f} ms/step", flush=True)
