@@ -68,7 +68,8 @@ const char* mi_nerf_last_error(void);
  * W = 128, 256 (32 points per wave) and 384, 512 (16 points per wave), and mi_nerf_pack_weights / mi_nerf_pack_map lay a network of any other width out for the next of them, with zero
  * weights and biases for the hidden units it does not have (exactly 0 through the ReLU: the W-wide network's result at the padded width's
  * cost; linear_d is W // 2 wide, model/NeRF.py:28); the training path W in {128, 256}; the bf16 and split-precision variants W = 256;
- * 2 <= D <= 16, L_x <= 10, L_d <= 4 (the kernels evaluate gamma_10 / gamma_4; gamma_L is a prefix of them in the reference's
+ * 2 <= D <= 16 (the split-precision forward, inference and training: D <= 14; its backward-data kernel: D <= 15; the bf16 / f16 kernels run
+ * D > 12 at 32 points per wave only -- each refused with an error that names the limit), L_x <= 10, L_d <= 4 (the kernels evaluate gamma_10 / gamma_4; gamma_L is a prefix of them in the reference's
  * channel order, PositionalEncoding.py:18-24, so a network with fewer frequencies is packed with zero weights on the rest and
  * gives the same result), at most one skip (skip = -1: none; a skip index >= D-1 never fires, exactly like the reference's
  * `range(D-1)` construction at model/NeRF.py:25).  Pre-embedded rows (mi_nerf_mlp_embedded) have the network's own width.

@@ -428,6 +428,8 @@ int mi_nerf_render_rays(const mi_nerf_net* net, const void* packed_c, const void
     if (int rc = mode_plan(cfg->mode, &p)) return rc;
     if (p.coarse == Family::F16 || p.fine == Family::F16)
         if (int rc = check_net_half(net, "f16")) return rc;                // before any launch: both networks of these modes are 256 wide
+    if (p.coarse == Family::F16S || p.fine == Family::F16S)
+        if (int rc = check_net_f16s_forward(net)) return rc;               // likewise: its depth limit is below the blob's (half_layout.h)
     FineDraw fd{};
     if (p.coarse == Family::BF16 || p.coarse == Family::F16) {
         // the half kernel draws the stratified depths in its own prologue and writes z_c (one launch fewer: at a 512-ray shard a
@@ -465,6 +467,8 @@ int mi_nerf_time_mlp_rays(const mi_nerf_net* net, const void* packed, const floa
     MN_CHECK_ARG(p.coarse == p.fine, "MI_NERF_MODE_* %d is two kernel families (mi_nerf_render_rays only): one network, one kernel family", mode);
     if (p.fine == Family::F16)
         if (int rc = check_net_half(net, "f16")) return rc;                // before the events: no GPU call for a network the kernel cannot run
+    if (p.fine == Family::F16S)
+        if (int rc = check_net_f16s_forward(net)) return rc;
     hipEvent_t e0, e1;
     MN_HIP(hipEventCreate(&e0));
     MN_HIP(hipEventCreate(&e1));

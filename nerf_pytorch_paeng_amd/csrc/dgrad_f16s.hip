@@ -296,6 +296,10 @@ int dgrad_f16s(const mi_nerf_net* net, const void* packed_bwd_f16s_dev, const fl
                long long n_valid, const unsigned* absmax_dev, hipStream_t st) {
     using namespace f16s;
     if (int rc = check_net_half(net, "f16-split")) return rc;
+    constexpr auto lds_bytes = [](int D) { return (size_t)HRING_BYTES + (size_t)(3 * 128 + 256) * 4 + (size_t)4 * D * 1024; };      // ring | heads | per wave: D layers of mask words
+    static_assert(lds_bytes(F16S_DGRAD_MAX_D) <= LDS_BYTES && lds_bytes(F16S_DGRAD_MAX_D + 1) > LDS_BYTES, "F16S_DGRAD_MAX_D is what this launch's LDS holds");
+    MN_CHECK_ARG(net->D <= F16S_DGRAD_MAX_D, "the split-precision backward-data kernel keeps a tile's ReLU' words of all layers in LDS: D = %d does not fit (D <= %d)",
+                 net->D, F16S_DGRAD_MAX_D);
     MN_CHECK_ARG(n_rays >= 1 && S >= 1, "bad sizes n_rays=%lld S=%d", (long long)n_rays, S);
     MN_CHECK_ARG(packed_bwd_f16s_dev && color_w_dev && dens_w_dev && d_raw_dev && mask_h && mask_g && delta_h && delta_f && delta_d && absmax_dev, "NULL device pointer");
     DArgs a{};
@@ -311,8 +315,7 @@ int dgrad_f16s(const mi_nerf_net* net, const void* packed_bwd_f16s_dev, const fl
     a.n_wtiles = (unsigned)n_wtiles;
     a.absmax_bits = absmax_dev;
     a.delta_absmax_bits = const_cast<unsigned*>(absmax_dev) + 1;    // second word of the same slot (zeroed with the first)
-    const size_t lds = HRING_BYTES + (size_t)(3 * 128 + 256) * 4 + (size_t)4 * net->D * 1024;      // ring | heads | per wave: D layers of mask words
-    MN_CHECK_ARG(lds <= 160 * 1024, "the split-precision backward-data kernel keeps a tile's ReLU' words of all layers in LDS: D = %d does not fit (D <= 15)", net->D);
+    const size_t lds = lds_bytes(net->D);
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)dgrad_f16s_kernel)) return rc;
     const int n_cus = device_cus();

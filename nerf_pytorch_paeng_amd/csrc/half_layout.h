@@ -55,12 +55,29 @@ inline HalfLayout make_half_layout(int D, int W, int skip, HalfStream kind) {
 // the split-precision backward stream (W = 256): linear_d^T's feature block, linear_feat^T, linear_x[D-1 .. 1]^T, as pairs
 inline uint32_t bwd_stream_bytes_s(int D) { return (uint32_t)(16 * 4 + 16 * 8 * D) * 2u * QUAD_BYTES; }
 
+// DEPTH LIMITS BELOW 16.  The blobs and the packers take D = 2..16; three launches keep D-proportional tables beside the 96 KiB weight ring
+// in the CU's 160 KiB of LDS and run out of it sooner (each launcher static_asserts its own formula against these):
+//   split-precision forward (mlp_f16s_kernel, inference and stash): side tables with D x 256 biases + 34 KiB of per-wave buffers   D <= 14
+//   bf16 / f16 forward, 64 points per wave: the same side tables + 36 KiB of per-wave buffers (32 points per wave: 18 KiB)         D <= 12
+//   split-precision backward data (dgrad_f16s_kernel): 4 KiB of ReLU' words per layer                                               D <= 15
+constexpr int LDS_BYTES = 160 * 1024;
+constexpr int F16S_FWD_MAX_D = 14, HALF_64PT_MAX_D = 12, F16S_DGRAD_MAX_D = 15;
+__host__ __device__ constexpr size_t half_side_bytes(int D) { return ((size_t)D * 256 + 256 + 128 + 4 + (3 + 6 * KERNEL_LD) * 128) * 4; }
+
 // shapes the 16-bit variants are built for; `variant`: "bf16", "f16-split", "f16"
 inline int check_net_half(const mi_nerf_net* net, const char* variant) {
     MN_CHECK_ARG(net != nullptr, "net is NULL");
     MN_CHECK_ARG(net->W == 256, "the %s variant is built for W=256 only (got %d; weights.PackedNeRF pads narrower networks)", variant, net->W);
     MN_CHECK_ARG(net->D >= 2 && net->D <= 16 && net->L_x >= 0 && net->L_x <= KERNEL_LX && net->L_d >= 0 && net->L_d <= KERNEL_LD && net->skip >= -1,
                  "unsupported network for the %s variant (D=%d L_x=%d L_d=%d skip=%d)", variant, net->D, net->L_x, net->L_d, net->skip);
+    return MI_NERF_OK;
+}
+// ... and the split-precision FORWARD on top of it (inference, training forward, every render mode whose plan has an F16S family): checked
+// before the first launch of a render, not when the launch is reached
+inline int check_net_f16s_forward(const mi_nerf_net* net) {
+    if (int rc = check_net_half(net, "f16-split")) return rc;
+    MN_CHECK_ARG(net->D <= F16S_FWD_MAX_D, "the split-precision forward kernel keeps every layer's biases and its waves' encoding buffers beside the weight ring in LDS: "
+                 "D = %d does not fit (D <= %d); a deeper network runs in fp32, bf16 or f16", net->D, F16S_FWD_MAX_D);
     return MI_NERF_OK;
 }
 

@@ -15,6 +15,8 @@ constexpr int NP = 2;                                      // point tiles (16 po
 constexpr int NBUF = 4, LA = NBUF - 1;                     // A-operand pipeline: quad PAIRS in flight (a body's pair count and the tail's padding jump are multiples of 4)
 constexpr int KPE = enc_ksteps32(KERNEL_LX), KH = 8, NT = 16;      // k-steps over gamma(x) (63 -> 64 channels), over a 256-wide activation; output tiles of a 256-wide layer
 constexpr float SC_DN = 1.0f / SPLIT_SCALE, SC_UP = SPLIT_SCALE;   // 2^-11, 2^11
+// LDS of a forward launch: ring | side tables | per wave: the hoisted direction bias [W/2], the parked gamma(x) fragments [hi, lo][NP][KPE] quads
+__host__ __device__ constexpr size_t fwd_lds_bytes(int D) { return (size_t)HRING_BYTES + half_side_bytes(D) + 4 * (256 / 2) * 4 + (size_t)4 * 2 * NP * KPE * QUAD_BYTES; }
 // (MT = 16, KF = 32 and the tail -- TAIL_USED of TAIL_PAIRS quad PAIRS carry weights -- are the bf16 stream's: half_layout.h)
 
 // ---------------------------------------------------------------------------------------------
@@ -575,7 +577,8 @@ template <bool STASH>
 static int launch_f16s(const mi_nerf_net* net, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays, int S,
                        float* raw_dev, const StashF16s* stash, hipStream_t st) {
     using namespace f16s;
-    if (int rc = check_net_half(net, "f16-split")) return rc;
+    static_assert(fwd_lds_bytes(F16S_FWD_MAX_D) <= LDS_BYTES && fwd_lds_bytes(F16S_FWD_MAX_D + 1) > LDS_BYTES, "F16S_FWD_MAX_D is what this launch's LDS holds");
+    if (int rc = check_net_f16s_forward(net)) return rc;
     MN_CHECK_ARG(n_rays >= 0 && S >= 1, "bad sizes n_rays=%lld S=%d", (long long)n_rays, S);
     if (n_rays == 0) return MI_NERF_OK;
     MN_CHECK_ARG(packed_dev && rays_dev && z_dev && raw_dev, "NULL device pointer");
@@ -592,8 +595,8 @@ static int launch_f16s(const mi_nerf_net* net, const void* packed_dev, const flo
     a.skip_layer = (net->skip >= 0 && net->skip + 1 < net->D) ? net->skip + 1 : -1;
     a.stream_bytes = L.stream_bytes; a.side_floats = L.side_floats;
     a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d; a.o_head_b = L.head_b; a.o_wdir_t = L.wdir_t;
-    const size_t lds = HRING_BYTES + (size_t)a.side_floats * 4 + 4 * (256 / 2) * 4 + (size_t)4 * 2 * NP * KPE * QUAD_BYTES;
-    MN_CHECK_ARG(lds <= 160 * 1024, "LDS budget exceeded: %zu bytes", lds);
+    const size_t lds = fwd_lds_bytes(net->D);
+    MN_CHECK_ARG((size_t)a.side_floats * 4 == half_side_bytes(net->D) && lds <= LDS_BYTES, "internal: the forward launch of a %d-deep network needs %zu bytes of LDS", net->D, lds);
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)mlp_f16s_kernel<STASH>)) return rc;
     const int n_cus = device_cus();

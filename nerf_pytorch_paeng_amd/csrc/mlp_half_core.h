@@ -689,8 +689,14 @@ static PhaseB make_phase(const MlpArgsB& a, long long tile0, long long tile_end,
 template <int NPA, int NPB, int NWV, bool F16>
 static int launch_half(MlpArgsB a, long long split, long long n_wtiles, hipStream_t st) {
     constexpr int NPM = NPA > NPB ? NPA : NPB;
-    const size_t lds = HRING_BYTES + (size_t)a.side_floats * 4 + (size_t)NWV * (NPM / 2) * (256 / 2) * 4 + (size_t)NWV * NPM * enc_ksteps32(10) * QUAD_BYTES;
-    MN_CHECK_ARG(lds <= 160 * 1024, "LDS budget exceeded: %zu bytes", lds);
+    // ring | side tables | per wave: a hoisted direction bias [W/2] per 32-point tile, the parked gamma(x) fragments [NPM][KPE] quads
+    constexpr auto lds_bytes = [](int D) { return (size_t)HRING_BYTES + half_side_bytes(D) + (size_t)NWV * (NPM / 2) * (256 / 2) * 4 + (size_t)NWV * NPM * enc_ksteps32(10) * QUAD_BYTES; };
+    static_assert(NPM == 4 ? (lds_bytes(HALF_64PT_MAX_D) <= LDS_BYTES && lds_bytes(HALF_64PT_MAX_D + 1) > LDS_BYTES) : lds_bytes(16) <= LDS_BYTES,
+                  "the 64-point shape holds HALF_64PT_MAX_D layers' tables, the 32-point shape every depth check_net_half accepts");
+    MN_CHECK_ARG(NPM != 4 || a.D <= HALF_64PT_MAX_D, "the 64-points-per-wave shape of the %s kernel keeps every layer's biases and 36 KiB of per-wave buffers beside the weight ring "
+                 "in LDS: D = %d does not fit (D <= %d); points_per_wave 0 or 32 runs a deeper network at 32 points per wave", F16 ? "f16" : "bf16", a.D, HALF_64PT_MAX_D);
+    const size_t lds = lds_bytes(a.D);
+    MN_CHECK_ARG((size_t)a.side_floats * 4 == half_side_bytes(a.D) && lds <= LDS_BYTES, "internal: this launch of a %d-deep network needs %zu bytes of LDS", a.D, lds);
     auto kern = [] {                                         // only the element type of this translation unit is instantiated
         if constexpr (F16) return mlp_f16_kernel<256, 10, 4, NPA, NPB, NWV>;
         else return mlp_bf16_kernel<256, 10, 4, NPA, NPB, NWV>;
@@ -771,7 +777,8 @@ static int mlp_rays_half(const mi_nerf_net* net, const HalfLayout& L, const void
     a.stream_bytes = L.walk_bytes; a.side_floats = L.side_floats;
     a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d; a.o_head_b = L.head_b; a.o_wdir_t = L.wdir_t;
     if (points_per_wave == 64) return launch_half<4, 0, 4, F16>(a, n_wtiles, n_wtiles, st);
-    if (points_per_wave == 32) return launch_half<2, 0, 4, F16>(a, n_wtiles, n_wtiles, st);
+    // ... and a network deeper than the 64-point shape's LDS holds (HALF_64PT_MAX_D: half_layout.h) runs every launch at 32 points per wave
+    if (points_per_wave == 32 || net->D > HALF_64PT_MAX_D) return launch_half<2, 0, 4, F16>(a, n_wtiles, n_wtiles, st);
     // (An 8-wave shape -- 32 points per wave, two waves per SIMD -- was measured SLOWER than the 64-point shape at every size: 4096 rays, fine
     // launch 638 vs 603 us, profiles/r03_bf16_two_waves_per_simd.txt.  The kernel is not short of latency hiding, it is short of power: twice
     // the LDS reads per FLOP cost more clock than the interleaving wins back.  Its instantiation is gone: tools/ABLATIONS.md.)

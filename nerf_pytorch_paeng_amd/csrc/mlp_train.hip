@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <vector>
 #include "mlp_core.h"
+#include "half_layout.h"
 
 namespace minerf {
 
@@ -172,7 +173,11 @@ void mlp_dgrad_kernel(const DgradArgs a) {
 // ---------------------------------------------------------------------------------------------
 // backward weights
 // ---------------------------------------------------------------------------------------------
-constexpr int WG_MAXB = 12;               // products per launch (an 8-layer net has 9 wide ones)
+// Products per launch.  A D-layer net has D + 1 wide ones (D - 1 trunk layers, linear_feat, linear_d): up to D = 11 they are one batch (an
+// 8-layer net: 9; D = 11: exactly WG_MAXB).  Past 11 layers mlp_backward_fp32 flushes a full batch of WG_MAXB and runs the rest as a second
+// batch in stream order, which reuses the partial buffer behind the first batch's reduce: D = 12 flushes behind linear_feat and runs
+// linear_d as a batch of one (every CU a slice: the partial buffer exactly full at 3072 points and more), D = 13..16 flush inside the trunk loop.
+constexpr int WG_MAXB = 12;
 struct WgradArgs {                        // a BATCH of products of the same point set: blockIdx.y picks the product
     const float* dlt[WG_MAXB]; const float* x[WG_MAXB];     // delta [P, ldd] (columns [0, M)), layer input [P, ldx] (columns [0, N))
     int ldd[WG_MAXB], ldx[WG_MAXB], M[WG_MAXB], N[WG_MAXB]; // M, N <= 256
@@ -997,6 +1002,9 @@ int mlp_backward_fp32(const mi_nerf_net* net, const void* packed_fwd, const void
     // mi_nerf_pack_weights_bwd_f16s); both scale their gradient operands from max|d_raw| of this call, taken on the device
     unsigned* absmax = nullptr;
     if (mode & 3) {
+        // (dgrad_f16s checks this again next to its LDS formula; here it is refused before the first launch of the call)
+        MN_CHECK_ARG(!(mode & 2) || D <= F16S_DGRAD_MAX_D, "the split-precision backward-data kernel keeps a tile's ReLU' words of all layers in LDS: "
+                     "D = %d does not fit (D <= %d); the fp32 backward-data kernel reads the same stash", D, F16S_DGRAD_MAX_D);
         MN_CHECK_ARG(W == 256 && !x_dev, "the split-precision backward is built for W=256 and the ray entry point");
         absmax = (unsigned*)((char*)work + L.partial + al256(WGRAD_PARTIAL_FLOATS * 4));
         MN_HIP(hipMemsetAsync(absmax, 0, 8, st));              // [0] max|d_raw|, [1] max|delta * s| (written by the split-precision backward-data kernel)

@@ -97,7 +97,7 @@ class _RenderTrainOcc(torch.autograd.Function):
             n_t = tile_src.shape[0]
             if n_t == 0:                                             # no sample was evaluated: the parameters did not reach the colours
                 return st.split_grads(torch.zeros(st.n_flat, dtype=torch.float32, device=rays.device))
-            f16s_dgrad = f16s and net.D <= 15
+            f16s_dgrad = f16s and ops.f16s_dgrad_fits(net)
             blob_b = ops.pack_apply_f16s(net, st.map_bwd_f16s(), flat, st.f16s_out_of_range, backward=True) if f16s_dgrad else ops.pack_apply(st.map_bwd, flat)
             d_raw = geo.node_backward(ctx.cfg, raw, z, rays, g_rgb, g_ext)
             d_tiles = occ.gather_raw(d_raw, tile_src)

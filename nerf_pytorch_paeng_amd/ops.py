@@ -26,6 +26,25 @@ def make_net(D: int, W: int, skip: int = 4, L_x: int = 10, L_d: int = 4) -> Net:
     return Net(D, W, skip, L_x, L_d)
 
 
+# Depth limits below the blobs' 16 (csrc/half_layout.h: what each launch keeps beside the weight ring in the 160 KiB of LDS).  The library
+# refuses each with an error naming it; callers that choose a route, or that want to refuse a model before any work, read them here.
+F16S_FWD_MAX_D = 14          # split-precision forward: inference and the training forward
+F16S_DGRAD_MAX_D = 15        # split-precision backward-data kernel
+HALF_64PT_MAX_D = 12         # bf16 / f16 at 64 points per wave (deeper: 32 points per wave, chosen by the library when points_per_wave is 0)
+
+
+def check_f16s_forward_depth(net: Net) -> None:
+    """Refuse, before anything is packed or launched, a network the split-precision forward has no room for (the library's own message)."""
+    if net.D > F16S_FWD_MAX_D:
+        raise MiNerfError(f"the split-precision forward kernel keeps every layer's biases and its waves' encoding buffers beside the weight ring in LDS: "
+                          f"D = {net.D} does not fit (D <= {F16S_FWD_MAX_D}); a deeper network runs in fp32, bf16 or f16")
+
+
+def f16s_dgrad_fits(net: Net) -> bool:
+    """Whether a split-precision backward runs its backward-data chain in split precision too (else the fp32 chain, over the same stash)."""
+    return net.D <= F16S_DGRAD_MAX_D
+
+
 # ------------------------------------------------------------------------------------------------
 # weights
 # ------------------------------------------------------------------------------------------------

@@ -159,12 +159,14 @@ def _state_for(model: torch.nn.Module, f16s: bool = False) -> _TrainState:
     if per_width is None:
         per_width = _states[model] = {}
     known = next(iter(per_width.values()), None)
+    st = None
     if known is not None:                                  # the module's own shape is on record: which kernel width does this precision train at?
         st = per_width.get(padded_train_net(known.net_model, f16s).W)
-        if st is not None and st.device == dev:
-            return st
-    st = _TrainState(model, dev, f16s)
-    per_width[st.net.W] = st
+    if st is None or st.device != dev:
+        st = _TrainState(model, dev, f16s)
+        per_width[st.net.W] = st
+    if f16s:                                               # a depth the split-precision forward has no LDS for: refused here, before the step starts
+        ops.check_f16s_forward_depth(st.net)
     return st
 
 
@@ -243,7 +245,7 @@ class _RenderTrain(torch.autograd.Function):
             if g_rgb is None and all(g is None for g in g_ext):
                 return [None] * len(st.names)
             f16s = ctx.f16s and net.W == 256
-            f16s_dgrad = f16s and net.D <= 15              # the split-precision chain keeps a tile's ReLU' words of all layers in LDS
+            f16s_dgrad = f16s and ops.f16s_dgrad_fits(net)   # the split-precision chain keeps a tile's ReLU' words of all layers in LDS
             blob_b = ops.pack_apply_f16s(net, st.map_bwd_f16s(), flat, st.f16s_out_of_range, backward=True) if f16s_dgrad else ops.pack_apply(st.map_bwd, flat)
             d_raw = geo.node_backward(ctx.cfg, raw, z, rays, g_rgb, g_ext)
             grads, work = ops.mlp_backward(net, blob, blob_b, rays, z, d_raw, stash, stage=0 if need_params else 1, f16s_wgrad=f16s,

@@ -162,9 +162,12 @@ class PackedNeRF:
     def kernel_blobs(self, prec: "ops.Precision") -> Tuple[Net, torch.Tensor, torch.Tensor]:
         """(network, coarse blob, fine blob) to hand the library for ``prec`` (ops.precision()): each blob from its kernel family's packer
         (the f16 kernel reads the split-precision blobs' hi halves), the 256-wide network whenever a family is not fp32."""
+        net = self.kernel_net(bf16=prec.fine == "bf16", f16s=prec.reads_f16s)      # (refuses a width the mode has no kernel for)
+        if "f16s" in (prec.coarse, prec.fine):            # a depth the split-precision forward has no LDS for: refused before anything is packed
+            ops.check_f16s_forward_depth(self.net)
         blobs = {"fp32": lambda: (self.coarse, self.fine), "bf16": self.bf16, "f16s": self.f16s, "f16": self.f16s}
         coarse, fine = blobs[prec.coarse]()[0], blobs[prec.fine]()[1]
-        return self.kernel_net(bf16=prec.fine == "bf16", f16s=prec.reads_f16s), coarse, fine
+        return net, coarse, fine
 
     def _wide_flats(self, wide: Net):
         """The device-resident flat parameter vectors scattered into the layout of ``wide`` (nn.Module source)."""

@@ -183,6 +183,47 @@ def test_argument_refusals_without_a_gpu():
     assert rc == EINVAL and "MI_NERF_MODE_" in lib.mi_nerf_last_error().decode()      # mode 9 is two networks: render_rays only
 
 
+def test_depth_refusals_without_a_gpu():
+    """The depth limits (csrc/half_layout.h; ops.F16S_FWD_MAX_D, HALF_64PT_MAX_D, F16S_DGRAD_MAX_D) and netDepth 2..16 itself are argument
+    checks: answered with an error that names the depth or the limit, before the first HIP call (on a machine without a GPU any HIP call
+    would put "HIP error" into the message) and before any of the host stubs handed over as device pointers is looked at."""
+    lib = _lib.lib()
+    stub = C.cast((C.c_char * 64)(), C.c_void_p)
+
+    def refused(rc, *needles):
+        msg = lib.mi_nerf_last_error().decode()
+        assert rc == EINVAL and all(s in msg for s in needles) and "HIP error" not in msg, (rc, msg)
+
+    for D in (15, 16):                                             # the split-precision forward: alone, as the training forward, in a render mode
+        net = ops.make_net(D, 256, D - 2)
+        refused(lib.mi_nerf_mlp_rays_f16s(C.byref(net), stub, stub, stub, 4, 8, stub, None), f"D = {D} does not fit (D <= {ops.F16S_FWD_MAX_D})")
+        refused(lib.mi_nerf_mlp_rays_train_f16s(C.byref(net), stub, stub, stub, 4, 8, stub, stub, 1 << 40, None), f"(D <= {ops.F16S_FWD_MAX_D})")
+        for mode in (5, 6):
+            rc, msg = _render_call(lib, net, mode)
+            assert rc == EINVAL and f"(D <= {ops.F16S_FWD_MAX_D})" in msg and "HIP error" not in msg, (mode, rc, msg)
+        refused(lib.mi_nerf_time_mlp_rays(C.byref(net), stub, stub, stub, 1, 1, stub, 1, 5, C.byref(C.c_float()), None), f"(D <= {ops.F16S_FWD_MAX_D})")
+    for D in (13, 16):                                             # bf16 at 64 points per wave (the plan itself picks 32 for such a network)
+        refused(lib.mi_nerf_mlp_rays_bf16_shape(C.byref(ops.make_net(D, 256, 4)), stub, stub, stub, 4, 8, stub, 64, None),
+                f"D = {D} does not fit (D <= {ops.HALF_64PT_MAX_D})")
+    net16 = ops.make_net(16, 256, 4)
+    for mode in (2, 3):                                            # the split-precision backward-data chain, with or without the split-precision products
+        refused(lib.mi_nerf_mlp_backward_mode(C.byref(net16), stub, stub, stub, stub, 4, 8, stub, stub, stub, 1 << 40, stub, 0, mode, None),
+                f"D = 16 does not fit (D <= {ops.F16S_DGRAD_MAX_D})")
+    for D in (17, 1):                                              # netDepth 2..16: every forward family, the training forward and backward
+        for W in (128, 256, 512):
+            refused(lib.mi_nerf_mlp_rays(C.byref(ops.make_net(D, W, -1)), stub, stub, stub, 4, 8, stub, None), f"D={D}")
+        net = ops.make_net(D, 256, -1)
+        refused(lib.mi_nerf_mlp_rays_bf16_shape(C.byref(net), stub, stub, stub, 4, 8, stub, 0, None), f"D={D}")
+        refused(lib.mi_nerf_mlp_rays_f16s(C.byref(net), stub, stub, stub, 4, 8, stub, None), f"D={D}")
+        refused(lib.mi_nerf_time_mlp_rays(C.byref(net), stub, stub, stub, 1, 1, stub, 1, 8, C.byref(C.c_float()), None), f"D={D}")
+        for fn in (lib.mi_nerf_mlp_rays_train, lib.mi_nerf_mlp_rays_train_f16s):
+            refused(fn(C.byref(net), stub, stub, stub, 4, 8, stub, stub, 1 << 40, None), f"D={D}")
+        for mode in (0, 1, 3):
+            refused(lib.mi_nerf_mlp_backward_mode(C.byref(net), stub, stub, stub, stub, 4, 8, stub, stub, stub, 1 << 40, stub, 0, mode, None), f"D={D}")
+        for size_fn in (lib.mi_nerf_packed_bytes, lib.mi_nerf_packed_bytes_bf16, lib.mi_nerf_packed_bytes_f16s, lib.mi_nerf_packed_bytes_bwd_f16s):
+            assert size_fn(C.byref(net)) == 0 and f"D={D}" in lib.mi_nerf_last_error().decode()
+
+
 # ---------------------------------------------------------------------------------------------------
 # the kernel's addressing assumption: the f16s blob's hi quads, read as the ring reads them, are the bf16 stream
 # ---------------------------------------------------------------------------------------------------

@@ -60,7 +60,7 @@ def launch_shape(n, S):
 
 
 ORACLE_CASES = [(8, 4, 10, 4, 300, 64), (8, 4, 10, 4, 64, 192), (3, 0, 10, 4, 77, 65), (2, -1, 6, 2, 40, 33),
-                (8, 4, 10, 4, 1024, 64), (8, 4, 10, 4, 1100, 64)]
+                (8, 4, 10, 4, 1024, 64), (8, 4, 10, 4, 1100, 64), (16, 14, 10, 4, 77, 65)]
 
 
 def test_oracle_cases_cover_every_launch_shape():
@@ -91,6 +91,11 @@ def test_f16_network_vs_oracle(D, skip, L_x, L_d, n, S, lego_rays):
           f"max |oracle32 - oracle64| {e_ref:.3e}")
     assert torch.isfinite(got).all()
     assert e_gpu <= max(4 * e_ref, 2e-5), (e_gpu, e_ref)
+    if D > ops.HALF_64PT_MAX_D:
+        # The 64-point shape's LDS holds 12 layers' side tables: the plan runs a deeper network at 32 points per wave whatever the launch size
+        # (launch_shape() above describes D <= 12).  2200 rays x 3 tiles is where it would open with whole 64-point rounds: same rays, same bits.
+        big, zb = lego_rays[:2200].contiguous(), z[torch.arange(2200) % n].to(DEV)
+        assert torch.equal(f16_net_alone(packed, big, zb)[:n].cpu().double().reshape(-1, 4), got)
 
 
 @pytest.mark.parametrize("n", [300, 1100])

@@ -45,18 +45,29 @@ def packed_big():
 
 @pytest.mark.parametrize("D,skip,L_x,L_d,n,S", [(8, 4, 10, 4, 64, 192), (8, 4, 10, 4, 33, 100), (8, 4, 10, 4, 5, 64), (8, 4, 10, 4, 700, 33),
                                                  (7, 5, 10, 4, 37, 96), (3, -1, 10, 4, 37, 96), (8, 3, 10, 4, 37, 96), (2, -1, 10, 4, 37, 96),
-                                                 (9, 0, 10, 4, 37, 96), (8, 4, 6, 2, 37, 96), (4, -1, 0, 4, 37, 96)])
+                                                 (9, 0, 10, 4, 37, 96), (8, 4, 6, 2, 37, 96), (4, -1, 0, 4, 37, 96),
+                                                 (16, 14, 10, 4, 37, 96), (15, 7, 10, 4, 37, 96), (12, -1, 10, 4, 37, 96), (14, 12, 10, 4, 37, 96)])
 def test_f16s_mlp_vs_oracles(D, skip, L_x, L_d, n, S, lego_rays):
     """Raw network outputs of the split-precision kernel: (1) against the restatement with its rounding points (fp64 accumulation):
     what is left is fp32 summation order; (2) against the fp64 evaluation of the network: no further than 4x the reference's own fp32
     arithmetic (and than the fp32 MFMA kernel).  Both trunk polarities, the skip layer at odd / even l, no skip, fewer frequencies,
-    ragged sample counts, flat and ray-major tile walks."""
+    ragged sample counts, flat and ray-major tile walks.
+    The kernel keeps D x 256 biases beside its weight ring and per-wave buffers in LDS, which holds 14 layers (ops.F16S_FWD_MAX_D; D = 15
+    misses the 160 KiB by 16 bytes): D = 14, skip at D - 2, is its largest footprint; D = 15 and 16 are refused by name before any launch --
+    the blob itself packs at any depth up to 16 (the f16 kernel reads it: tests/test_gpu_f16.py)."""
     skips = (skip,) if skip >= 0 else ()
     in_x, in_d = 3 + 6 * L_x, 3 + 6 * L_d
     sd = synthetic.make_state_dict(17 + D + L_x, D, 256, in_x=in_x, in_d=in_d, skips=skips)
     packed = weights.PackedNeRF.from_state_dict(sd, DEV)
     rays = lego_rays[:n].contiguous()
     z = torch.sort(T(R.counter_uniform(3, 0, 0, n, S)) * 4 + 2, -1)[0]
+    if D > ops.F16S_FWD_MAX_D:
+        with pytest.raises(MiNerfError, match=r"D = %d does not fit \(D <= 14\)" % D):
+            ops.mlp_rays(packed.net, packed.f16s()[1], rays, z.to(DEV), f16s=True)
+        with pytest.raises(MiNerfError, match=r"D = %d does not fit \(D <= 14\)" % D):        # ... and a render in that mode, before anything is packed
+            NP.render_rays(rays, packed, None, make_opts(N_samples_c=16, N_samples_f=16), f16s=True)
+        print(f"f16s D={D}: refused by name (LDS holds {ops.F16S_FWD_MAX_D} layers)")
+        return
     x = R.embed(rays.cpu(), z, L_x, L_d)
     ref64 = R.mlp_forward(sd, "model_fine.", x.double(), D, in_x, in_d, skips=skips, dtype=torch.float64)
     ref32 = R.mlp_forward(sd, "model_fine.", x, D, in_x, in_d, skips=skips)
@@ -278,7 +289,7 @@ def _flat_params(sd, prefix, net):
     return torch.cat([torch.as_tensor(sd[prefix + k]).reshape(-1) for k in ops.param_names(net)]).float().to(DEV)
 
 
-@pytest.mark.parametrize("D,skip", [(8, 4), (4, -1), (3, 0)])
+@pytest.mark.parametrize("D,skip", [(8, 4), (4, -1), (3, 0), (16, 14)])
 def test_f16s_device_pack_is_the_host_pack(D, skip):
     sd = synthetic.make_state_dict(5, D, 256, skips=() if skip < 0 else (skip,))
     net = weights.infer_net(sd)
@@ -389,7 +400,7 @@ def test_f16s_training_step_gradients_match_the_fp32_path(lego_rays):
         NP.render_rays(rays, model, None, opts, bf16=True)
 
 
-@pytest.mark.parametrize("D,skip", [(8, 4), (3, 0), (2, -1)])
+@pytest.mark.parametrize("D,skip", [(8, 4), (3, 0), (2, -1), (16, 14), (15, 0)])
 def test_f16s_backward_stream_device_pack_is_the_host_pack(D, skip):
     sd = synthetic.make_state_dict(6, D, 256, skips=() if skip < 0 else (skip,))
     net = weights.infer_net(sd)

@@ -182,7 +182,7 @@ def _existing_masked_path(model, f16s, rays, z, mask, prefix_module):
 
     def backward(g_rgb):
         split = f16s and net.W == 256
-        dgrad = split and net.D <= 15
+        dgrad = split and ops.f16s_dgrad_fits(net)
         blob_b = ops.pack_apply_f16s(net, st.map_bwd_f16s(), flat, st.f16s_out_of_range, backward=True) if dgrad else ops.pack_apply(st.map_bwd, flat)
         d_raw = ops.composite_backward(raw, z, rays, g_rgb.contiguous())
         d_raw = torch.where(m, d_raw, torch.zeros_like(d_raw))
@@ -285,9 +285,9 @@ def test_gradients_against_the_existing_masked_path_as_comparator(batch):
 # ---------------------------------------------------------------------------------------------------
 # 5. edge grids
 # ---------------------------------------------------------------------------------------------------
-def _both_ways(family, n, Sc, Nf, grid, seed=21):
+def _both_ways(family, n, Sc, Nf, grid, seed=21, shape=None):
     f16s = family == "f16s"
-    _, model = make_model(*NETS[family])
+    _, model = make_model(*(shape or NETS[family]))
     opts = make_opts(Sc, Nf)
     rays = lego_rays(n, 2)
     g = torch.Generator().manual_seed(seed)
@@ -322,6 +322,22 @@ def test_all_ones_grid_is_the_full_training_path(family):
     s = grid.last_stats
     assert (s["evaluated_c"], s["evaluated_f"], s["padded_c"], s["padded_f"]) == (s["total_c"], s["total_f"], 0, 0)
     _compare_with_the_full_path(family, full, g_full, occ, g_occ)
+
+
+@pytest.mark.parametrize("family,D,W", [("f16s", 16, 256), ("f16s", 14, 256), ("fp32", 16, 128)])
+def test_all_ones_grid_is_the_full_training_path_at_depth(family, D, W):
+    """The compacted entry at the depths where the backward splits its weight-gradient batch (past 11 layers) and where the split-precision
+    kernels run out of LDS: D = 14 is the deepest network the split-precision forward holds, D = 16 is refused by name before the step starts
+    (by the rule train_path applies: occupancy_train reads the same one), and trains in fp32."""
+    grid = constant_grid(True, True)
+    if family == "f16s" and D > ops.F16S_FWD_MAX_D:
+        _, model = make_model(D, W)
+        with pytest.raises(ops.MiNerfError, match=r"D = %d does not fit \(D <= 14\)" % D):
+            OT.render_train(lego_rays(96, 2), model, make_opts(64, 64), grid, seed=4, f16s=True)
+        return
+    full, g_full, occ, g_occ, _ = _both_ways(family, 96, 64, 64, grid, shape=(D, W, 5 if D == 14 else 0))      # (14 x 256, seed 0: densities dead on every sample)
+    assert len(g_full) == 2 * (2 * D + 8)
+    _compare_with_the_full_path(f"{family} D={D}", full, g_full, occ, g_occ)
 
 
 def test_all_ones_grid_above_four_tiles_per_cu():

@@ -566,25 +566,40 @@ def test_bf16_render_psnr(packed_big, lego_rays):
 # ---------------------------------------------------------------------------------------------------
 # other network shapes, the frame harness, error behaviour
 # ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,W", [(6, 128), (2, 128), (3, 256), (10, 256)])
+def measured_bar(e_ref, floor, deep):
+    """The bar of a forward result's distance from the fp64 oracle.  Cases from before the deep ones keep their literal; a deep case (added
+    with docs/design/10_training_path.md "Depths 11-16") is held to the measured comparator of test_mlp_rays_fused_vs_oracle,
+    max(4 e_ref, the same literal), e_ref being the fp32 CPU oracle's own distance from fp64 on the same inputs: a 16-layer network's
+    outputs reach |27| when the skip sits at D - 2, where a fixed literal would measure the inputs, not the kernel."""
+    return max(4.0 * e_ref, floor) if deep else floor
+
+
+@pytest.mark.parametrize("D,W", [(6, 128), (2, 128), (3, 256), (10, 256), (16, 256), (13, 128), (16, 128)])
 def test_other_network_shapes(D, W):
-    """skip=[4] only fires when D >= 6 (model/NeRF.py:25 builds range(D-1)); depth is a run-time loop in the kernel."""
+    """skip=[4] only fires when D >= 6 (model/NeRF.py:25 builds range(D-1)); depth is a run-time loop in the kernel.  D = 16 is the deepest
+    network check_net accepts (the side tables' D x W biases at their largest, the weight ring's slot parity over the most layers)."""
     sd = synthetic.make_state_dict(21, D, W)
     packed = weights.PackedNeRF.from_state_dict(sd, DEV)
     assert packed.net.skip == (4 if D >= 6 else -1)
     x = torch.rand(100, 90) * 2 - 1
     y = ops.mlp_embedded(packed.net, packed.coarse, x.to(DEV))
     ref = R.mlp_forward(sd, "model_coarse.", x, D, 63, 27, dtype=torch.float64)
-    assert err(y, ref) <= 5e-5
+    e_gpu, e_ref = err(y, ref), err(R.mlp_forward(sd, "model_coarse.", x, D, 63, 27), ref)
+    print(f"D={D} W={W} embedded rows: |gpu-fp64| {e_gpu:.2e}  |torch fp32-fp64| {e_ref:.2e}")
+    assert e_gpu <= measured_bar(e_ref, 5e-5, D > 10)
     rays = torch.cat([torch.rand(9, 3) * 2 - 1, torch.nn.functional.normalize(torch.randn(9, 3), dim=-1)], -1)
     z = torch.sort(torch.rand(9, 64) * 4 + 2, -1)[0]
     raw = ops.mlp_rays(packed.net, packed.fine, rays.to(DEV), z.to(DEV))
-    ref = R.mlp_forward(sd, "model_fine.", R.embed(rays, z, 10, 4).double(), D, 63, 27, dtype=torch.float64).reshape(9, 64, 4)
-    assert err(raw, ref) <= 1e-4
+    emb = R.embed(rays, z, 10, 4)
+    ref = R.mlp_forward(sd, "model_fine.", emb.double(), D, 63, 27, dtype=torch.float64).reshape(9, 64, 4)
+    e_gpu, e_ref = err(raw, ref), err(R.mlp_forward(sd, "model_fine.", emb, D, 63, 27).reshape(9, 64, 4), ref)
+    print(f"D={D} W={W} fused rays: |gpu-fp64| {e_gpu:.2e}  |torch fp32-fp64| {e_ref:.2e}")
+    assert e_gpu <= measured_bar(e_ref, 1e-4, D > 10)
 
 
 @pytest.mark.parametrize("D,W,skip", [(8, 64, 4), (4, 64, 4), (8, 192, 4), (6, 100, 2), (8, 200, 4), (3, 31, 0), (8, 129, 4),
-                                      (8, 512, 4), (4, 300, 1), (8, 257, 4), (2, 512, -1), (16, 384, 7), (8, 400, 4), (5, 384, 2)])
+                                      (8, 512, 4), (4, 300, 1), (8, 257, 4), (2, 512, -1), (16, 384, 7), (8, 400, 4), (5, 384, 2),
+                                      (16, 512, 14), (16, 200, 14)])
 def test_network_widths_without_a_kernel_of_their_own(D, W, skip, lego_rays):
     """--netWidth values the reference accepts (config.py:57; model/NeRF.py:24-30 builds any W) but no kernel is instantiated for: the
     packer lays such a network out for the next kernel width (64 -> 128, 192 -> 256, 300 -> 384, 400 -> 512) with zero weights for the hidden units it
@@ -597,17 +612,26 @@ def test_network_widths_without_a_kernel_of_their_own(D, W, skip, lego_rays):
     sd = synthetic.make_state_dict(40 + W, D, W, skips=skips)
     packed = weights.PackedNeRF.from_state_dict(sd, DEV)
     assert (packed.net.D, packed.net.W) == (D, W) and packed.net.skip == (skip if 0 <= skip and skip + 1 < D else -1)
+    deep = D > 10 and skip == D - 2                              # the full-depth cases: the wide kernel's 512 instantiation and a padded width, skip at the last position
     x = torch.rand(333, 90, generator=torch.Generator().manual_seed(W)) * 2 - 1
     for fine, blob in ((False, packed.coarse), (True, packed.fine)):
         y = ops.mlp_embedded(packed.net, blob, x.to(DEV))
-        ref = R.mlp_forward(sd, "model_fine." if fine else "model_coarse.", x, D, 63, 27, skips=skips, dtype=torch.float64)
-        assert err(y, ref) <= 5e-5, (fine, err(y, ref))
+        prefix = "model_fine." if fine else "model_coarse."
+        ref = R.mlp_forward(sd, prefix, x, D, 63, 27, skips=skips, dtype=torch.float64)
+        e_gpu, e_ref = err(y, ref), err(R.mlp_forward(sd, prefix, x, D, 63, 27, skips=skips), ref) if deep else 0.0
+        if deep:
+            print(f"D={D} W={W} skip={skip} embedded rows ({prefix[6:-1]}): |gpu-fp64| {e_gpu:.2e}  |torch fp32-fp64| {e_ref:.2e}")
+        assert e_gpu <= measured_bar(e_ref, 5e-5, deep), (fine, e_gpu)
     n, S = 70, 96
     rays = lego_rays[:n].contiguous()
     z = torch.sort(T(R.counter_uniform(4, 0, 0, n, S)) * 4 + 2, -1)[0]
     raw = ops.mlp_rays(packed.net, packed.fine, rays, z.to(DEV))
-    ref = R.mlp_forward(sd, "model_fine.", R.embed(rays.cpu(), z, 10, 4).double(), D, 63, 27, skips=skips, dtype=torch.float64).reshape(n, S, 4)
-    assert err(raw, ref) <= 2e-4, err(raw, ref)
+    emb = R.embed(rays.cpu(), z, 10, 4)
+    ref = R.mlp_forward(sd, "model_fine.", emb.double(), D, 63, 27, skips=skips, dtype=torch.float64).reshape(n, S, 4)
+    e_gpu, e_ref = err(raw, ref), err(R.mlp_forward(sd, "model_fine.", emb, D, 63, 27, skips=skips).reshape(n, S, 4), ref) if deep else 0.0
+    if deep:
+        print(f"D={D} W={W} skip={skip} fused rays: |gpu-fp64| {e_gpu:.2e}  |torch fp32-fp64| {e_ref:.2e}")
+    assert e_gpu <= measured_bar(e_ref, 2e-4, deep), e_gpu
     # the whole step, depths pinned to the oracle's (sample_pdf is discontinuous), through a module model built at this width
     opts = make_opts()
     model = NeRF(D, W, 63, 27, skips=list(skips)).to(DEV)
@@ -629,10 +653,14 @@ def test_network_widths_without_a_kernel_of_their_own(D, W, skip, lego_rays):
     if W <= 256:
         for src in (packed, model):                                       # host packer (state dict) and device packer (live module)
             with torch.no_grad():
-                g16 = NP.render_rays(rays, src, None, opts, t_rand=t_rand, u=u, f16s=True)
+                if D > ops.F16S_FWD_MAX_D:                                # the split-precision forward holds 14 layers: refused by name, before the render starts
+                    with pytest.raises(MiNerfError, match=r"D = %d does not fit \(D <= 14\)" % D):
+                        NP.render_rays(rays, src, None, opts, t_rand=t_rand, u=u, f16s=True)
+                else:
+                    g16 = NP.render_rays(rays, src, None, opts, t_rand=t_rand, u=u, f16s=True)
+                    assert err(g16["rgb_c"], want["rgb_c"]) <= 2e-5, err(g16["rgb_c"], want["rgb_c"])              # fp32-grade
+                    assert float(SA.rays_beyond(g16["rgb_f"], want["rgb_f"]).float().mean()) <= 0.03
                 gb = NP.render_rays(rays, src, None, opts, t_rand=t_rand, u=u, bf16=True)
-            assert err(g16["rgb_c"], want["rgb_c"]) <= 2e-5, err(g16["rgb_c"], want["rgb_c"])              # fp32-grade
-            assert float(SA.rays_beyond(g16["rgb_f"], want["rgb_f"]).float().mean()) <= 0.03
             mse = float(torch.mean((gb["rgb_c"].cpu() - want["rgb_c"]) ** 2))
             assert torch.isfinite(gb["rgb_f"]).all() and -10.0 * np.log10(max(mse, 1e-20)) > 50.0, mse       # bf16-grade (observed 70-80 dB coarse)
     else:
@@ -733,6 +761,32 @@ def test_error_behaviour(packed_big, lego_rays):
         weights.PackedNeRF.from_state_dict(synthetic.make_state_dict(0, 4, 600), DEV)              # wider than the widest kernel (narrower ones pad)
     with pytest.raises(MiNerfError):
         NP.render_rays(lego_rays[:4].cpu(), weights.packed_for(packed_big), None, opts, t_rand=torch.rand(4, 63))   # wrong t_rand shape
+
+
+@pytest.mark.parametrize("D", [17, 1])
+def test_depths_beyond_the_limits_are_refused_by_every_entry(D, lego_rays):
+    """netDepth 2..16 is what every kernel family accepts: one layer more or less is refused by argument checking, with an error that says
+    which depth was asked for -- by the packer behind PackedNeRF, by the fused forward in fp32 and in each 16-bit mode, by the training forward
+    and backward.  The device pointers handed over are never read (a blob of this depth cannot be packed): a launch would fault on them."""
+    from nerf_pytorch_paeng_amd._lib import MiNerfError
+    with pytest.raises(MiNerfError, match=rf"D={D}\b"):
+        weights.PackedNeRF.from_state_dict(synthetic.make_state_dict(0, D, 128, skips=()), DEV)
+    n, S = 4, 8
+    rays, z = lego_rays[:n].contiguous(), torch.full((n, S), 3.0, device=DEV)
+    dummy = torch.zeros(4096, dtype=torch.uint8, device=DEV)
+    for W, flags in ((128, {}), (256, {}), (512, {}), (256, dict(bf16=True)), (256, dict(bf16=True, points_per_wave=32)), (256, dict(f16s=True))):
+        with pytest.raises(MiNerfError, match=rf"D={D}\b"):
+            ops.mlp_rays(ops.make_net(D, W, -1), dummy, rays, z, **flags)
+    with pytest.raises(MiNerfError, match=rf"D={D}\b"):
+        ops.time_mlp_rays(ops.make_net(D, 256, -1), dummy, rays, z, torch.empty(n, S, 4, device=DEV), 1, f16=True)
+    for W in (128, 256):
+        net = ops.make_net(D, W, -1)
+        for f16s in (False, True):
+            with pytest.raises(MiNerfError, match=rf"D={D}\b"):
+                ops.mlp_rays_train(net, dummy, rays, z, stash=dummy, f16s=f16s)
+        for bw in (dict(), dict(f16s_wgrad=True), dict(f16s_wgrad=True, f16s_dgrad=True)):
+            with pytest.raises(MiNerfError, match=rf"D={D}\b"):
+                ops.mlp_backward(net, dummy, dummy, rays, z, torch.zeros(n, S, 4, device=DEV), dummy, work=dummy, **bw)
 
 
 def test_bf16_through_module_model(lego_rays):
@@ -852,13 +906,16 @@ def test_bf16_small_coarse_launch_does_the_middle_of_render_rays_itself(n, Sc, N
         assert bool((z_f[:, 1:] >= z_f[:, :-1]).all()) and torch.isfinite(res[0][0][2]).all()
 
 
-@pytest.mark.parametrize("D,skip", [(7, 5), (3, -1), (8, 3), (2, -1), (6, 4), (9, 0)])
+@pytest.mark.parametrize("D,skip", [(7, 5), (3, -1), (8, 3), (2, -1), (6, 4), (9, 0), (16, 14), (16, 0), (12, -1)])
 def test_bf16_other_depths_and_skip_positions(D, skip, lego_rays):
     """The bf16 kernel addresses its B fragments by explicit AGPR number, with two statically unrolled polarities (which fragment
     set a layer reads) and a separate instantiation for the skip layer at odd / even l -- a polarity error would give silently
     wrong colours.  check_net_half accepts D = 2..16 and any skip position (config.py:54-57 --netDepth; NeRF.py:25 skips), so each
     code path runs here against the bf16 oracle: odd D (tail reads set 0), even D (set 1), the skip layer at even l
-    (skip = 3, 5: layer_10<SKIP>) and at odd l (skip = 0, 4: layer_01<SKIP>), no skip at all."""
+    (skip = 3, 5: layer_10<SKIP>) and at odd l (skip = 0, 4: layer_01<SKIP>), no skip at all.
+    The 64-point shape keeps 12 layers' side tables in LDS (ops.HALF_64PT_MAX_D; D = 12 is its largest footprint): a deeper network is
+    refused there by name and runs at 32 points per wave, which is what the launch plan (points_per_wave = 0) picks for it at any size."""
+    from nerf_pytorch_paeng_amd._lib import MiNerfError
     skips = (skip,) if skip >= 0 else ()
     sd = synthetic.make_state_dict(31 + D, D, 256, skips=skips)
     packed = weights.PackedNeRF.from_state_dict(sd, DEV)
@@ -866,7 +923,17 @@ def test_bf16_other_depths_and_skip_positions(D, skip, lego_rays):
     n, S = 37, 96
     rays = lego_rays[:n].contiguous()
     z = torch.sort(T(R.counter_uniform(4, 0, 0, n, S)) * 4 + 2, -1)[0]
-    raw16 = ops.mlp_rays(packed.net, packed.bf16()[1], rays, z.to(DEV), bf16=True, points_per_wave=64).cpu()
+    if D > ops.HALF_64PT_MAX_D:
+        with pytest.raises(MiNerfError, match=r"D = %d does not fit \(D <= 12\)" % D):
+            ops.mlp_rays(packed.net, packed.bf16()[1], rays, z.to(DEV), bf16=True, points_per_wave=64)
+        # 2200 rays x 3 tiles: more than three rounds of 64-point units on 256 CUs, where the plan would otherwise open with the 64-point shape
+        big, zb = lego_rays[:2200].contiguous(), z[torch.arange(2200) % n].to(DEV)
+        raw_plan = ops.mlp_rays(packed.net, packed.bf16()[1], big, zb, bf16=True)
+        assert torch.equal(raw_plan, ops.mlp_rays(packed.net, packed.bf16()[1], big, zb, bf16=True, points_per_wave=32))
+        raw16 = ops.mlp_rays(packed.net, packed.bf16()[1], rays, z.to(DEV), bf16=True).cpu()
+        assert torch.equal(raw16, raw_plan[:n].cpu())          # a ray's result does not depend on the launch it is part of
+    else:
+        raw16 = ops.mlp_rays(packed.net, packed.bf16()[1], rays, z.to(DEV), bf16=True, points_per_wave=64).cpu()
     assert torch.equal(raw16, ops.mlp_rays(packed.net, packed.bf16()[1], rays, z.to(DEV), bf16=True, points_per_wave=32).cpu())
     ref = R.mlp_forward_bf16(sd, "model_fine.", R.embed(rays.cpu(), z, 10, 4), D, 63, 27, skips=skips).reshape(n, S, 4)
     e = (raw16 - ref).abs()
@@ -876,8 +943,11 @@ def test_bf16_other_depths_and_skip_positions(D, skip, lego_rays):
     assert max(rel) < 2e-3 and float(e.max()) < 0.2, (rel, float(e.max()))
     # and the fp32 kernel on the same network (its depth / skip position are run-time values)
     raw32 = ops.mlp_rays(packed.net, packed.fine, rays, z.to(DEV)).cpu()
-    ref32 = R.mlp_forward(sd, "model_fine.", R.embed(rays.cpu(), z, 10, 4).double(), D, 63, 27, skips=skips, dtype=torch.float64).reshape(n, S, 4)
-    assert err(raw32, ref32) <= 2e-4, err(raw32, ref32)
+    emb = R.embed(rays.cpu(), z, 10, 4)
+    ref32 = R.mlp_forward(sd, "model_fine.", emb.double(), D, 63, 27, skips=skips, dtype=torch.float64).reshape(n, S, 4)
+    e_gpu, e_ref = err(raw32, ref32), err(R.mlp_forward(sd, "model_fine.", emb, D, 63, 27, skips=skips).reshape(n, S, 4), ref32)
+    print(f"fp32 kernel D={D} skip={skip}: |gpu-fp64| {e_gpu:.2e}  |torch fp32-fp64| {e_ref:.2e}")
+    assert e_gpu <= measured_bar(e_ref, 2e-4, D > 10), e_gpu
 
 
 @pytest.mark.parametrize("bf16", [False, True])
