@@ -52,6 +52,7 @@ def main(argv=None):
     ap.add_argument("--fused-adam", action="store_true", help="optim.FusedAdam instead of torch.optim.Adam")
     ap.add_argument("--lr-min", type=float, default=None, help="warm-up cosine schedule from this rate up to 5e-4 and back over --steps")
     ap.add_argument("--warmup", type=int, default=None, help="warm-up steps of the schedule (default with --lr-min: a twentieth of --steps)")
+    ap.add_argument("--lpips", default=None, metavar="VGG_PTH:LIN_PTH", help="also report LPIPS: a torchvision vgg16 state dict and the lpips package's linear layers, two files for torch.load")
     a = ap.parse_args(argv)
     if a.warmup is not None and not 0 <= a.warmup < a.steps:
         ap.error("--warmup takes a number of steps below --steps")
@@ -76,6 +77,13 @@ def main(argv=None):
             ap.error("--train-occupancy takes two non-negative integers")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    lpips_model = None
+    if a.lpips is not None:
+        if a.lpips.count(":") != 1:
+            ap.error("--lpips takes VGG_PTH:LIN_PTH, two files")
+        from nerf_pytorch_paeng_amd.perceptual import Lpips
+        vgg_pth, lin_pth = a.lpips.split(":")
+        lpips_model = Lpips.from_state_dicts(torch.load(vgg_pth, map_location="cpu"), torch.load(lin_pth, map_location="cpu"), input="lpips", device=dev)
     H = W = a.size
     # config.py:105-111 -- the fields the path reads, with lego.txt's values
     opts = SimpleNamespace(near=2.0, far=6.0, N_samples_c=64, N_samples_f=128, perturb=1.0, chunk_rays=4096, chunk_pts=524288, data_type="blender",
@@ -136,9 +144,11 @@ def main(argv=None):
                 print(f"             evaluated share {occupancy.evaluated_share(grid.last_stats):.3f}, padded share {occupancy.padded_share(grid.last_stats):.3f}", flush=True)
     fresh = NeRF(8, a.net_width, 63, 27, skips=[4]).to(dev)                                      # test() loads the checkpoint train() saved (test.py:20-21)
     res = harness.test(a.steps, i_test, posenc, fresh, images[i_test], K, poses[i_test].to(dev), (H, W), opts, log_dir=a.out,
-                       save_dir=os.path.join(a.out, "test_result"), ssim=True)                   # main.py:140-149
+                       save_dir=os.path.join(a.out, "test_result"), ssim=True, lpips=lpips_model)   # main.py:140-149
     print(f"test: PSNR {['%.2f' % p for p in res['psnr']]} dB (mean {res['mean_psnr']:.2f}), SSIM {['%.4f' % v for v in res['ssim']]} "
           f"(mean {res['mean_ssim']:.4f}); PNGs and _result.txt in {a.out}/test_result")
+    if lpips_model is not None:
+        print(f"test: LPIPS {['%.4f' % v for v in res['lpips']]} (mean {res['mean_lpips']:.4f})")
     rgbs, disps = harness.render(a.steps, posenc, fresh, K, None, (H, W), opts, log_dir=a.out, save_dir=os.path.join(a.out, "render_result"))   # main.py:150-158
     print(f"render: {rgbs.shape[0]} frames {rgbs.shape[1]}x{rgbs.shape[2]} in {a.out}/render_result")
     if a.mesh:

@@ -250,13 +250,19 @@ def _render_pose(model, posenc, K, pose, hw, opts):
 
 
 def test(idx, i_test, posenc, model, test_imgs, gt_intrinsic, gt_extrinsic, hw, opts, *, log_dir: Optional[str] = None,
-         save_dir: Optional[str] = None, keep_frames: bool = False, ssim: bool = False) -> Dict:
+         save_dir: Optional[str] = None, keep_frames: bool = False, ssim: bool = False, lpips=None) -> Dict:
     """Counterpart of test.py:17-108.  ``log_dir`` given: load ``{log_dir}/{exp_name}/{exp_name}_{idx}.pth.tar`` first
     (test.py:20-21).  ``save_dir`` given: write ``NNN.png``, ``NNN_disp.png`` and ``_result.txt`` like the reference.
     Returns per-frame loss / PSNR (Python floats), best / mean PSNR, and the uint8 frames when ``keep_frames``.
     ``ssim=True`` (or a true ``opts.ssim``): also the per-frame SSIM of test.py:71 (``ops.ssim``: the definition of include/mi_nerf_iqa.h,
-    not verified against the package the reference imports), ``best_ssim`` / ``mean_ssim``, and the numbers in ``_result.txt``."""
+    not verified against the package the reference imports), ``best_ssim`` / ``mean_ssim``, and the numbers in ``_result.txt``.
+    ``lpips=model`` (or a non-None ``opts.lpips``), a ``perceptual.Lpips``: also the per-frame LPIPS of test.py:75 (``ops.lpips``: the
+    definition of include/mi_nerf_lpips.h under the caller's weights), ``best_lpips`` (the smallest, test.py:102) / ``mean_lpips``, and the
+    numbers in ``_result.txt``."""
     want_ssim = bool(ssim) or bool(getattr(opts, "ssim", False))
+    lpips_model = lpips if lpips is not None else getattr(opts, "lpips", None)
+    want_lpips = lpips_model is not None
+    col_lpips = 3 if want_ssim else 2
     if isinstance(model, torch.nn.Module):
         model.eval()
         if log_dir is not None:
@@ -267,9 +273,9 @@ def test(idx, i_test, posenc, model, test_imgs, gt_intrinsic, gt_extrinsic, hw, 
     dev = next(model.parameters()).device if isinstance(model, torch.nn.Module) else model.device
     n_pose = len(gt_extrinsic)
     want_frames = save_dir is not None or keep_frames
-    # everything a frame produces stays on the device until the loop is over: [mse, psnr] per frame in one [N, 2] tensor, the uint8
+    # everything a frame produces stays on the device until the loop is over: [mse, psnr (, ssim) (, lpips)] per frame in one tensor, the uint8
     # frames in two stacks -- ONE device -> host copy each after the last pose, no host synchronisation per frame
-    metrics = torch.empty(n_pose, 3 if want_ssim else 2, dtype=torch.float32, device=dev)
+    metrics = torch.empty(n_pose, col_lpips + int(want_lpips), dtype=torch.float32, device=dev)
     rgbs8 = torch.empty(n_pose, img_h, img_w, 3, dtype=torch.uint8, device=dev) if want_frames else None
     disps8 = torch.empty(n_pose, img_h, img_w, 1, dtype=torch.uint8, device=dev) if want_frames else None
     with torch.no_grad():
@@ -280,7 +286,9 @@ def test(idx, i_test, posenc, model, test_imgs, gt_intrinsic, gt_extrinsic, hw, 
             target = as_f32_dev(test_imgs[i], pred_rgb.device).reshape(-1, 3)             # test.py:63
             metrics[i, :2] = ops.image_metrics(pred_rgb, target)                          # img2mse, mse2psnr: test.py:65-67
             if want_ssim:
-                metrics[i, 2:] = ops.ssim(pred_rgb.reshape(-1, 3), target, hw=(img_h, img_w))     # getSSIM: test.py:71
+                metrics[i, 2:3] = ops.ssim(pred_rgb.reshape(-1, 3), target, hw=(img_h, img_w))    # getSSIM: test.py:71
+            if want_lpips:
+                metrics[i, col_lpips:] = ops.lpips(pred_rgb.reshape(-1, 3), target, hw=(img_h, img_w), model=lpips_model)   # getLPIPS: test.py:75
             if want_frames:
                 rgbs8[i] = ops.to8b(pred_rgb).reshape(img_h, img_w, 3)                        # test.py:55
                 disps8[i] = ops.to8b(pred_disp, ops.nanmax(pred_disp)).reshape(img_h, img_w, 1)   # test.py:56
@@ -297,20 +305,24 @@ def test(idx, i_test, posenc, model, test_imgs, gt_intrinsic, gt_extrinsic, hw, 
             if keep_frames:
                 frames.append((rgbs_np[i], disps_np[i]))
     ssims: Optional[List[float]] = [float(v) for v in m_host[:, 2]] if want_ssim else None
+    lpipss: Optional[List[float]] = [float(v) for v in m_host[:, col_lpips]] if want_lpips else None
     best = int(np.argmax(psnrs)) if psnrs else -1
-    res = {"loss": losses, "psnr": psnrs, "ssim": ssims, "lpips": None, "best_idx": best,
+    res = {"loss": losses, "psnr": psnrs, "ssim": ssims, "lpips": lpipss, "best_idx": best,
            "best_psnr": psnrs[best] if psnrs else None, "mean_psnr": float(np.mean(psnrs)) if psnrs else None}
     if want_ssim:                                                                         # test.py:102, 107: the largest and the mean
         res["best_ssim"] = max(ssims) if ssims else None
         res["mean_ssim"] = float(np.mean(ssims)) if ssims else None
+    if want_lpips:                                                                        # test.py:102, 107: the smallest and the mean
+        res["best_lpips"] = min(lpipss) if lpipss else None
+        res["mean_lpips"] = float(np.mean(lpipss)) if lpipss else None
     if keep_frames:
         res["frames"] = frames
     if save_dir is not None:                                                              # test.py:92-108
         with open(os.path.join(save_dir, "_result.txt"), "w") as f:
             for i in range(len(losses)):
-                f.write(f"idx:{i}\tloss:{losses[i]}\tpsnr:{psnrs[i]}\tssim:{ssims[i] if want_ssim else 'n/a'}\tlpips:n/a\n")
-            f.write(f"\nBest Value ) PSNR : {res['best_psnr']}\tSSIM : {res['best_ssim'] if want_ssim else 'n/a'}\tLPIPS : n/a\n")
-            f.write(f"Mean Value ) PSNR : {res['mean_psnr']}\tSSIM : {res['mean_ssim'] if want_ssim else 'n/a'}\tLPIPS : n/a")
+                f.write(f"idx:{i}\tloss:{losses[i]}\tpsnr:{psnrs[i]}\tssim:{ssims[i] if want_ssim else 'n/a'}\tlpips:{lpipss[i] if want_lpips else 'n/a'}\n")
+            f.write(f"\nBest Value ) PSNR : {res['best_psnr']}\tSSIM : {res['best_ssim'] if want_ssim else 'n/a'}\tLPIPS : {res['best_lpips'] if want_lpips else 'n/a'}\n")
+            f.write(f"Mean Value ) PSNR : {res['mean_psnr']}\tSSIM : {res['mean_ssim'] if want_ssim else 'n/a'}\tLPIPS : {res['mean_lpips'] if want_lpips else 'n/a'}")
     return res
 
 

@@ -601,6 +601,14 @@ def ssim(pred: torch.Tensor, target: torch.Tensor, *, hw=None, downsample: int =
     return (out, smap) if return_map else out
 
 
+def lpips(pred: torch.Tensor, target: torch.Tensor, hw=None, model=None, per_tap: bool = False):
+    """LPIPS of ``pred`` against ``target`` (include/mi_nerf_lpips.h has the definition; the number test.py:75 prints) under ``model``, a
+    ``perceptual.Lpips``: a device tensor of N floats, never synchronised.  Shapes as ``ssim``."""
+    if model is None:
+        raise MiNerfError("lpips needs model=perceptual.Lpips(...): the weights are the caller's, there is no default network")
+    return model(pred, target, hw=hw, per_tap=per_tap)
+
+
 def nanmax(x: torch.Tensor) -> torch.Tensor:
     if x.numel() == 0:
         raise MiNerfError("nanmax of an empty tensor")
