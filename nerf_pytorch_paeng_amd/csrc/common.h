@@ -27,6 +27,8 @@ constexpr int MN_MAX_DEVICES = 64;
 struct LdsOptIn { std::atomic<bool> done[MN_MAX_DEVICES]; };
 int device_cus();                                             // multiProcessorCount of the current device (cached per device)
 int ensure_lds_opt_in(LdsOptIn& state, const void* kernel);  // hipFuncSetAttribute(MaxDynamicSharedMemorySize = 160 KB), once per device
+// grid of a persistent kernel: one workgroup per CU, fewer when the launch has fewer workgroups' worth of work
+static inline int persistent_grid(long long n_wg) { const long long cus = device_cus(); return (int)(n_wg < cus ? n_wg : cus); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -137,5 +139,67 @@ __device__ __forceinline__ float sin_cos_fast(float y, int quad_shift) {
 // largest argument and use the libm path (sinf/cosf, Payne-Hanek) for anything bigger or non-finite.  (4e6 until the far-point tests.)
 constexpr float SINCOS_FAST_LIMIT = 1048576.0f;      // 2^20
 __device__ __forceinline__ float sin_cos_slow(float y, int quad_shift) { return quad_shift ? cosf(y) : sinf(y); }
+__device__ __forceinline__ float sin_cos_any(float y, bool fast, int quad_shift) { return fast ? sin_cos_fast(y, quad_shift) : sin_cos_slow(y, quad_shift); }
+
+// ---------------------------------------------------------------------------------------------
+// the ray prologue of the fused MLP kernels (mlp_fp32.hip, mlp_fp32_wide.hip, mlp_half_core.h, mlp_f16s_core.h)
+// ---------------------------------------------------------------------------------------------
+// pts = rays_o + rays_d * z : separate multiply and add (nerf_process.py:69-70), no contraction
+__device__ __forceinline__ void sample_point(float (&pt)[3], const float (&o)[3], const float (&d)[3], float z) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pt[c] = o[c] + d[c] * z;
+}
+// the ONE branch per point: every argument 2^k pt_c, k < LX, is below SINCOS_FAST_LIMIT (false for huge or non-finite coordinates: libm path)
+template <int LX>
+__device__ __forceinline__ bool point_is_fast(const float (&pt)[3]) {
+    const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(pt[0]), __builtin_fabsf(pt[1])), __builtin_fabsf(pt[2])) * (float)(1 << (LX - 1));
+    return amax < SINCOS_FAST_LIMIT;
+}
+// sin / cos of 2^k pt_c, every channel evaluated on its own (the argument is exact: a power-of-two scale)
+template <int LX>
+__device__ __forceinline__ void sincos_octaves(const float (&pt)[3], bool fast, float (&sn)[LX][3], float (&cs)[LX][3]) {
+#pragma unroll
+    for (int k = 0; k < LX; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float y = pt[c] * (float)(1 << k);
+            sn[k][c] = sin_cos_any(y, fast, 0);
+            cs[k][c] = sin_cos_any(y, fast, 1);
+        }
+}
+// channel u of gamma(x) in the reference's order (PositionalEncoding.py:18-24), zero beyond the last; u is a constant at every use
+template <int LX>
+__device__ __forceinline__ float gamma_channel(int u, const float (&pt)[3], const float (&sn)[LX][3], const float (&cs)[LX][3]) {
+    if (u >= 3 + 6 * LX) return 0.0f;
+    if (u < 3) return pt[u];
+    const int k = (u - 3) / 6, r = (u - 3) % 6;
+    return r < 3 ? sn[k][r] : cs[k][r - 3];
+}
+// hoisted view-direction term of linear_d (fp32), constant over a ray's samples: dst[n] = b_d[n] + sum_f Wd[n][W + f] * gamma(d / |d|)[f] for the
+// W / 2 outputs, lane `lane` of the wave taking n = lane, lane + 64, ...  wdt: that block of Wd transposed, [3 + 6 LD][W / 2]; all three in LDS.
+template <int W, int LD>
+__device__ __forceinline__ void hoisted_dir_bias(float* dst, float dx, float dy, float dz, const float* wdt, const float* bd, int lane) {
+    constexpr int IN_D = 3 + 6 * LD;
+    const float nrm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
+    const float v[3] = {dx / nrm, dy / nrm, dz / nrm};
+    float g[IN_D];
+    g[0] = v[0]; g[1] = v[1]; g[2] = v[2];
+#pragma unroll
+    for (int k = 0; k < LD; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float y = v[c] * (float)(1 << k);
+            g[3 + 6 * k + c] = sin_cos_fast(y, 0);       // |y| <= 2^(LD-1): no fallback needed
+            g[3 + 6 * k + 3 + c] = sin_cos_fast(y, 1);
+        }
+#pragma unroll
+    for (int n0 = 0; n0 < W / 2; n0 += 64) {
+        const int n = n0 + lane;
+        float s = bd[n];
+#pragma unroll
+        for (int f = 0; f < IN_D; ++f) s = __builtin_fmaf(wdt[f * (W / 2) + n], g[f], s);
+        dst[n] = s;
+    }
+}
 
 }  // namespace minerf

@@ -119,10 +119,6 @@ void dgrad_f16s_kernel(const DArgs a) {
     for (int i = 0; i < LA; ++i) { aq[i][0] = ring_read(smem, ring, lane, 2 * i); aq[i][1] = ring_read(smem, ring, lane, 2 * i + 1); }
 
     const unsigned NW = gridDim.x * 4, wid = blockIdx.x * 4 + wave;
-    auto unit_of = [&](unsigned it) -> unsigned {
-        if (a.ppr) { const unsigned blk = it / a.ppr; return (blk * NW + wid) * a.ppr + (it - blk * a.ppr); }
-        return it * NW + wid;
-    };
     f32x4 ah[NP], al[NP], ph[NP], pl[NP];
     const f32x4 czero = {0.f, 0.f, 0.f, 0.f};
     auto csel0 = [&](int) __attribute__((always_inline)) -> const f32x4& { return czero; };
@@ -132,7 +128,7 @@ void dgrad_f16s_kernel(const DArgs a) {
     const unsigned mlds_m0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + HRING_BYTES + (3 * (W / 2) + W) * 4 + wave * (a.D * 1024);
 
     for (unsigned it = 0; it < a.n_iter; ++it) {
-        const unsigned n_tile = unit_of(it);
+        const unsigned n_tile = walk_unit(it, a.ppr, NW, wid);
         const bool active = n_tile < a.n_wtiles;
         const unsigned tcur = active ? n_tile : a.n_wtiles - 1;
         const unsigned tray = tcur / (unsigned)a.tpr, chunk = tcur - tray * (unsigned)a.tpr;
@@ -318,11 +314,8 @@ int dgrad_f16s(const mi_nerf_net* net, const void* packed_bwd_f16s_dev, const fl
     const size_t lds = lds_bytes(net->D);
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)dgrad_f16s_kernel)) return rc;
-    const int n_cus = device_cus();
-    const long long n_wg = (n_wtiles + 3) / 4;
-    const int grid = (int)(n_wg < n_cus ? n_wg : n_cus);
-    const long long NW = (long long)grid * 4;
-    a.ppr = 0; a.n_iter = (unsigned)((n_wtiles + NW - 1) / NW);
+    const int grid = persistent_grid((n_wtiles + 3) / 4);
+    a.ppr = 0; a.n_iter = (unsigned)walk_plan(n_rays, a.tpr, n_wtiles, grid, 4, false).n_iter;      // always the flat walk
     hipLaunchKernelGGL(dgrad_f16s_kernel, dim3(grid), dim3(256), lds, st, a);
     MN_LAUNCH_CHECK("dgrad_f16s_kernel");
     return MI_NERF_OK;

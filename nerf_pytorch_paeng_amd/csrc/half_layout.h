@@ -52,6 +52,19 @@ inline HalfLayout make_half_layout(int D, int W, int skip, HalfStream kind) {
     b.total_bytes = b.side_off + b.side_floats * 4;
     return b;
 }
+// the record the forward kernels read (layout.h); stream_bytes: L.walk_bytes (mlp_half_core.h's ring) or L.stream_bytes (mlp_f16s_core.h's)
+inline SideTables side_tables(const HalfLayout& L, const void* packed_dev, int D, int skip, uint32_t stream_bytes) {
+    SideTables t{};
+    t.stream = (const char*)packed_dev + L.stream_off;
+    t.side = (const float*)((const char*)packed_dev + L.side_off);
+    t.D = D;
+    t.skip_layer = skip_layer_of(D, skip);
+    t.stream_bytes = stream_bytes;
+    t.side_floats = L.side_floats;
+    t.o_bias_trunk = L.bias_trunk; t.o_bias_feat = L.bias_feat; t.o_bias_d = L.bias_d; t.o_wdir_t = L.wdir_t;
+    t.o_head_b = L.head_b;
+    return t;
+}
 // the split-precision backward stream (W = 256): linear_d^T's feature block, linear_feat^T, linear_x[D-1 .. 1]^T, as pairs
 inline uint32_t bwd_stream_bytes_s(int D) { return (uint32_t)(16 * 4 + 16 * 8 * D) * 2u * QUAD_BYTES; }
 

@@ -108,6 +108,36 @@ inline BlobLayout make_layout(int D, int W_net, int skip, int /*L_x*/, int /*L_d
     return b;
 }
 
+// What a forward kernel reads of a packed blob on the device: the weight stream, the fp32 side tables and where each table starts (floats
+// from `side`).  Every forward kernel's argument struct begins with this record; side_tables() fills it per layout type (half_layout.h: the
+// 16-bit blobs').
+struct SideTables {
+    const char* stream;       // device: blob + stream_off
+    const float* side;        // device: blob + side_off
+    int D;
+    int skip_layer;           // trunk layer index that consumes [gamma(x), h]; -1: none
+    unsigned stream_bytes;    // what the weight ring walks before it wraps
+    unsigned side_floats;
+    unsigned o_bias_trunk, o_bias_feat, o_bias_d, o_wdir_t;
+    unsigned o_dens_w, o_dens_b, o_color_w, o_color_b;      // fp32 blobs: the heads run on the VALU
+    unsigned o_head_b;                                      // 16-bit blobs: colour bias (3), density bias (the heads are stream tiles)
+};
+// opts.skips names the layer whose OUTPUT is concatenated with gamma(x) (model/NeRF.py:37-38): the layer after it consumes the wider input
+inline int skip_layer_of(int D, int skip) { return (skip >= 0 && skip + 1 < D) ? skip + 1 : -1; }
+
+inline SideTables side_tables(const BlobLayout& L, const void* packed_dev, int D, int skip, bool full_stream) {
+    SideTables t{};
+    t.stream = (const char*)packed_dev + L.stream_off;
+    t.side = (const float*)((const char*)packed_dev + L.side_off);
+    t.D = D;
+    t.skip_layer = skip_layer_of(D, skip);
+    t.stream_bytes = full_stream ? L.stream_bytes_full : L.stream_bytes_hoist;
+    t.side_floats = L.side_floats;
+    t.o_bias_trunk = L.bias_trunk; t.o_bias_feat = L.bias_feat; t.o_bias_d = L.bias_d; t.o_wdir_t = L.wdir_t;
+    t.o_dens_w = L.dens_w; t.o_dens_b = L.dens_b; t.o_color_w = L.color_w; t.o_color_b = L.color_b;
+    return t;
+}
+
 // ---------------------------------------------------------------------------------------------
 // training path
 // ---------------------------------------------------------------------------------------------

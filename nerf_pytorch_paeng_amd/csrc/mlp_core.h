@@ -1,14 +1,100 @@
-// mlp_core.h -- device-side building blocks shared by the fp32 MLP kernels (forward: mlp_fp32.hip,
-// backward-data: mlp_train.hip): the LDS weight ring fed by LDS-DMA, the register-resident GEMM part,
-// accumulator <-> B-operand moves and the small VALU helpers.  Device code only (.hip translation units).
+// mlp_core.h -- what the fp32 MLP kernels share (forward: mlp_fp32.hip, mlp_fp32_wide.hip; backward-data: mlp_train.hip): the LDS weight
+// ring fed by LDS-DMA, the register-resident GEMM part, accumulator <-> B-operand moves and the small VALU helpers; and the front end of
+// the two forward kernels: their argument struct, its filler, the tile walk of a wave (RayTileWalk) and the launch plan behind it
+// (walk_plan.h).  .hip translation units only.
 #pragma once
 #include "common.h"
 #include "layout.h"
+#include "walk_plan.h"
 
 namespace minerf {
 
 constexpr int NSLOT = 4;
 constexpr int RING_BYTES = NSLOT * SLOT_BYTES;
+
+// ---------------------------------------------------------------------------------------------
+// front end of the forward kernels (mlp_fp32_kernel: 32-point wave tiles, mlp_fp32_wide_kernel: 16-point ones)
+// ---------------------------------------------------------------------------------------------
+struct MlpArgs : SideTables {  // stream_bytes: hoisted (MODE 0) or full (MODE 1) length, a multiple of SLOT_BYTES
+    const float* rays;        // MODE 0: [n_rays, 6]
+    const float* z;           // MODE 0: [n_rays, S]
+    const float* x;           // MODE 1: [n_pts, in_x + in_d] with the NETWORK's own widths in_x = 3 + 6 Lx_net, in_d = 3 + 6 Ld_net
+    int Lx_net, Ld_net;       // the network's frequencies (<= the kernel's LX / LD; the missing channels carry zero weights, layout.h)
+    float* out;               // [n_pts, 4]
+    long long n_wtiles;       // wave tiles
+    long long n_pts;          // MODE 1
+    // MODE 0 tile walk of one wave (walk_plan.h: tile_start, then tile_advance by these per step); n_iter steps for every wave
+    long long n_rays, walk_ray, walk_carry, n_iter;
+    int walk_chunk, ray_major;
+    int S;                    // MODE 0
+    int tpr;                  // MODE 0: wave tiles per ray = ceil(S / points per tile)
+    unsigned long long* diag;  // MN_DIAG builds only: per-wave segment cycle sums + one tile's k-quad stamps
+    // STASH kernels (training forward): row-major activations kept for the backward pass, P = stash_rows points
+    float* stash_h;           // [D][P][W]   post-ReLU output of trunk layer l
+    float* stash_f;           // [P][W]      linear_feat output
+    float* stash_g;           // [P][W/2]    post-ReLU linear_d output
+    unsigned* mask_h;         // [D][n_wtiles][64 lanes][4]  ReLU' bits of stash_h in the kernel's register order
+    unsigned* mask_g;         // [n_wtiles][64 lanes][2]     ... of stash_g
+    long long stash_rows;
+};
+
+static void fill_common(MlpArgs& a, const mi_nerf_net* net, const void* packed_dev, bool full_stream) {
+    (SideTables&)a = side_tables(make_layout(net->D, net->W, net->skip, net->L_x, net->L_d), packed_dev, net->D, net->skip, full_stream);
+    a.Lx_net = net->L_x; a.Ld_net = net->L_d;
+}
+// MODE 0: rays x their S depths in wave tiles of PTS points
+template <int PTS>
+static void fill_rays(MlpArgs& a, const float* rays_dev, const float* z_dev, int64_t n_rays, int S, float* raw_dev) {
+    a.rays = rays_dev; a.z = z_dev; a.out = raw_dev; a.S = S; a.tpr = (S + PTS - 1) / PTS;
+    a.n_wtiles = (long long)n_rays * a.tpr; a.n_rays = n_rays;
+}
+
+// What a launch needs beside its arguments: the LDS size (ring | side tables | per wave: the hoisted direction bias [W/2]), the opt-in for
+// it, the grid (four wave tiles per workgroup) and the tile walk (MODE 1 walks flat: it has no rays).  opt_in: per kernel instantiation.
+template <int W, int MODE>
+static int plan_launch(MlpArgs& args, const void* kern, LdsOptIn& opt_in, size_t& lds, int& grid) {
+    lds = RING_BYTES + (size_t)args.side_floats * 4 + 4 * (W / 2) * 4;
+    MN_CHECK_ARG(lds <= 160 * 1024, "LDS budget exceeded: %zu bytes (a %d-deep network of width %d)", lds, args.D, W);
+    if (int rc = ensure_lds_opt_in(opt_in, kern)) return rc;
+    grid = persistent_grid((args.n_wtiles + 3) / 4);
+    const long long tpr = MODE == 0 ? args.tpr : 1;
+    const WalkPlan plan = walk_plan(args.n_rays, tpr, args.n_wtiles, grid, 4, MODE == 0);
+    const TileStep step = tile_step(plan.ray_major, (long long)grid * 4, tpr);
+    args.ray_major = plan.ray_major ? 1 : 0;
+    args.n_iter = plan.n_iter;
+    args.walk_ray = step.ray; args.walk_chunk = step.chunk; args.walk_carry = step.carry;
+    return MI_NERF_OK;
+}
+
+// MODE 0: a wave's walk over its tiles of PTS points (lane column `col` < PTS owns one of them), the inputs of the NEXT tile (six ray
+// scalars, one depth per lane) loaded a whole tile ahead.  No 64-bit division per tile: (ray, chunk) is stepped (walk_plan.h).  Per
+// iteration: read this tile through ray() / chunk() / o / d / z, then advance() -- which issues the next tile's loads -- BEFORE building the
+// point, so the loads have the whole tile to land.  A wave past the last ray recomputes the last tile (active() false: it stores nothing).
+template <int PTS>
+struct RayTileWalk {
+    long long t_ray;
+    int t_chunk;
+    float o[3], d[3], z;
+    __device__ __forceinline__ bool active(const MlpArgs& a) const { return t_ray < a.n_rays; }
+    __device__ __forceinline__ long long ray(const MlpArgs& a) const { return active(a) ? t_ray : a.n_rays - 1; }
+    __device__ __forceinline__ int chunk(const MlpArgs& a) const { return active(a) ? t_chunk : a.tpr - 1; }
+    __device__ __forceinline__ void load(const MlpArgs& a, int col) {
+        const long long r = ray(a);
+        const int sample = chunk(a) * PTS + col;
+        const int sc = sample < a.S ? sample : a.S - 1;
+        const float* rp = a.rays + r * 6;
+        o[0] = rp[0]; o[1] = rp[1]; o[2] = rp[2]; d[0] = rp[3]; d[1] = rp[4]; d[2] = rp[5];
+        z = a.z[r * a.S + sc];
+    }
+    __device__ __forceinline__ void start(const MlpArgs& a, long long wid, int col) {
+        tile_start(a.ray_major != 0, wid, a.tpr, t_ray, t_chunk);
+        load(a, col);
+    }
+    __device__ __forceinline__ void advance(const MlpArgs& a, int col) {
+        tile_advance(a.walk_ray, a.walk_chunk, a.walk_carry, a.tpr, t_ray, t_chunk);
+        load(a, col);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // weight ring: NSLOT x 16 KiB in LDS, filled by LDS-DMA three slots ahead of the consumer.

@@ -1,6 +1,8 @@
 // mlp_f16s_core.h -- the split-precision machinery shared by the translation units of that variant (mlp_f16s.hip: the
 // inference launch; mlp_f16s_stash.hip: the training forward; dgrad_f16s.hip: the backward-data chain): constants, the weight
 // ring's aliases, the fragment file, packing schedule, job(), and the forward kernel template.  See mlp_f16s.hip for the design.
+// Shared with the other families: the launch plan and the walk's closed form (walk_plan.h), the point encoder and the hoisted
+// view-direction term (common.h), the side-table record at the head of the arguments (layout.h).
 #pragma once
 #include "wstream_ring.h"
 
@@ -22,18 +24,14 @@ __host__ __device__ constexpr size_t fwd_lds_bytes(int D) { return (size_t)HRING
 // ---------------------------------------------------------------------------------------------
 // device
 // ---------------------------------------------------------------------------------------------
-struct Args {
-    const char* stream;
-    const float* side;
+struct Args : SideTables {      // (layout.h; filled by half_layout.h's side_tables)
     const float* rays;
     const float* z;
     float* out;
     unsigned n_wtiles;          // 32-point tiles (n_rays * tpr); a wave's unit of work is ONE tile = 2 point tiles
     unsigned n_iter;            // units per wave (the same for every wave: the ring barriers are workgroup-wide)
     unsigned ppr;               // ray-major walk: units per ray (tpr); 0: flat walk
-    int S, tpr, D, skip_layer;
-    unsigned stream_bytes, side_floats;
-    unsigned o_bias_trunk, o_bias_feat, o_bias_d, o_head_b, o_wdir_t;
+    int S, tpr;
     // STASH instantiation (training forward): what mlp_fp32_kernel<..., STASH = true> leaves for the backward pass, in ITS layouts
     float* stash_h;             // [D][P][W]   post-ReLU output of trunk layer l
     float* stash_f;             // [P][W]      linear_feat output
@@ -193,9 +191,9 @@ __device__ __forceinline__ void job(f32x4 (&ah)[NP], f32x4 (&al)[NP], CSel csel,
 template <bool STASH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void mlp_f16s_kernel(const Args a) {
-    constexpr int W = 256, LX = KERNEL_LX, LD = KERNEL_LD, IN_X = 3 + 6 * LX, IN_D = 3 + 6 * LD;
+    constexpr int W = 256, LX = KERNEL_LX, LD = KERNEL_LD;
     constexpr int BIG = 1 << 30;
-    asm volatile("" ::: "a255");                             // reserve the whole accumulation-register file
+    asm volatile("" ::: "a255");                            // reserve the whole accumulation-register file
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* side = (float*)(smem + HRING_BYTES);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -218,15 +216,11 @@ void mlp_f16s_kernel(const Args a) {
 #pragma unroll
     for (int i = 0; i < LA; ++i) { aq[i][0] = ring_read(smem, ring, lane, 2 * i); aq[i][1] = ring_read(smem, ring, lane, 2 * i + 1); }
 
-    // ---- tile walk: a wave takes one 32-sample tile (two 16-point MFMA tiles) per unit; ray-major when every wave gets whole rays
+    // ---- tile walk: a wave takes one 32-sample tile (two 16-point MFMA tiles) per unit; ray-major when every wave gets whole rays (walk_plan.h)
     const unsigned NW = gridDim.x * 4, wid = blockIdx.x * 4 + wave;
-    auto unit_of = [&](unsigned it) -> unsigned {
-        if (a.ppr) { const unsigned blk = it / a.ppr; return (blk * NW + wid) * a.ppr + (it - blk * a.ppr); }
-        return it * NW + wid;
-    };
     unsigned n_tile; float nx_r[6], nx_z;
     auto load_inputs = [&](unsigned it) __attribute__((always_inline)) {
-        unsigned t = unit_of(it);
+        unsigned t = walk_unit(it, a.ppr, NW, wid);
         n_tile = t;
         if (t >= a.n_wtiles) t = a.n_wtiles - 1;                    // inactive: recompute the last tile, store nothing
         const unsigned ray = t / (unsigned)a.tpr, chunk = t - ray * (unsigned)a.tpr;
@@ -321,25 +315,12 @@ void mlp_f16s_kernel(const Args a) {
         const float in_o[3] = {nx_r[0], nx_r[1], nx_r[2]}, in_d[3] = {nx_r[3], nx_r[4], nx_r[5]};
         const float in_z = nx_z;
         {
-            // pts = rays_o + rays_d * z (nerf_process.py:69-70); gamma(x) per channel with the fp32 kernel's accurate sin / cos
-            const float pt[3] = {in_o[0] + in_d[0] * in_z, in_o[1] + in_d[1] * in_z, in_o[2] + in_d[2] * in_z};
-            const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(pt[0]), __builtin_fabsf(pt[1])), __builtin_fabsf(pt[2])) * (float)(1 << (LX - 1));
-            const bool fast = amax < SINCOS_FAST_LIMIT;
+            // gamma(x) per channel with the fp32 kernel's accurate sin / cos (the point encoder of common.h)
+            float pt[3];
+            sample_point(pt, in_o, in_d, in_z);
             float sn[LX][3], cs[LX][3];
-#pragma unroll
-            for (int k = 0; k < LX; ++k)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float y = pt[c] * (float)(1 << k);
-                    sn[k][c] = fast ? sin_cos_fast(y, 0) : sin_cos_slow(y, 0);
-                    cs[k][c] = fast ? sin_cos_fast(y, 1) : sin_cos_slow(y, 1);
-                }
-            auto chan = [&](int u) __attribute__((always_inline)) -> float {     // channel u of gamma(x); u is a constant at every use
-                if (u >= IN_X) return 0.0f;
-                if (u < 3) return pt[u];
-                const int k = (u - 3) / 6, r = (u - 3) % 6;
-                return r < 3 ? sn[k][r] : cs[k][r - 3];
-            };
+            sincos_octaves<LX>(pt, point_is_fast<LX>(pt), sn, cs);
+            auto chan = [&](int u) __attribute__((always_inline)) -> float { return gamma_channel<LX>(u, pt, sn, cs); };
             // fragment (part, point tile pq, k-step ks): lane quarter qq reads channels 32 ks + 8 qq + j of point `col` at
             // [fragment][(qq * 16 + col) * 16 bytes]: this lane writes those 16 bytes for every qq, hi and lo
             char* wr_h = pe_wave + ((0 * NP + pq) * KPE) * QUAD_BYTES + col * 16;
@@ -374,29 +355,7 @@ void mlp_f16s_kernel(const Args a) {
         // hoisted view-direction term of linear_d (fp32): scratch[n] = b_d[n] + sum_f Wd[n][W+f] * gamma(d/|d|)[f], once per ray
         if (tray != bias_ray) {
             bias_ray = tray;
-            const float dx = in_d[0], dy = in_d[1], dz = in_d[2];
-            const float nrm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-            const float vdir[3] = {dx / nrm, dy / nrm, dz / nrm};
-            float g[IN_D];
-            g[0] = vdir[0]; g[1] = vdir[1]; g[2] = vdir[2];
-#pragma unroll
-            for (int k = 0; k < LD; ++k)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float y = vdir[c] * (float)(1 << k);
-                    g[3 + 6 * k + c] = sin_cos_fast(y, 0);
-                    g[3 + 6 * k + 3 + c] = sin_cos_fast(y, 1);
-                }
-            const float* wdt = side + a.o_wdir_t;
-            const float* bd = side + a.o_bias_d;
-#pragma unroll
-            for (int n0 = 0; n0 < W / 2; n0 += 64) {
-                const int n = n0 + lane;
-                float s = bd[n];
-#pragma unroll
-                for (int f = 0; f < IN_D; ++f) s = __builtin_fmaf(wdt[f * (W / 2) + n], g[f], s);
-                scratch[n] = s;
-            }
+            hoisted_dir_bias<W, LD>(scratch, in_d[0], in_d[1], in_d[2], side + a.o_wdir_t, side + a.o_bias_d, lane);
         }
         // ---- layer 0: 16 jobs of 2 k-steps over gamma(x) (VGPR fragments), output into set 0 -------------------------------------------
         if constexpr (STASH) {                                   // (re-stated here so that the eight words are not live across the prologue, the kernel's register peak)
@@ -584,28 +543,20 @@ static int launch_f16s(const mi_nerf_net* net, const void* packed_dev, const flo
     MN_CHECK_ARG(packed_dev && rays_dev && z_dev && raw_dev, "NULL device pointer");
     const HalfLayout L = make_half_layout(net->D, net->W, net->skip, HalfStream::PAIRS);
     Args a{};
-    a.stream = (const char*)packed_dev + L.stream_off;
-    a.side = (const float*)((const char*)packed_dev + L.side_off);
+    (SideTables&)a = side_tables(L, packed_dev, net->D, net->skip, L.stream_bytes);
     a.rays = rays_dev; a.z = z_dev; a.out = raw_dev;
     a.S = S; a.tpr = (S + 31) / 32;
     const long long n_wtiles = (long long)n_rays * a.tpr;
     MN_CHECK_ARG(n_wtiles < (1LL << 30), "too many points for one launch: %lld rays x %d samples", (long long)n_rays, S);
     a.n_wtiles = (unsigned)n_wtiles;
-    a.D = net->D;
-    a.skip_layer = (net->skip >= 0 && net->skip + 1 < net->D) ? net->skip + 1 : -1;
-    a.stream_bytes = L.stream_bytes; a.side_floats = L.side_floats;
-    a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d; a.o_head_b = L.head_b; a.o_wdir_t = L.wdir_t;
     const size_t lds = fwd_lds_bytes(net->D);
     MN_CHECK_ARG((size_t)a.side_floats * 4 == half_side_bytes(net->D) && lds <= LDS_BYTES, "internal: the forward launch of a %d-deep network needs %zu bytes of LDS", net->D, lds);
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)mlp_f16s_kernel<STASH>)) return rc;
-    const int n_cus = device_cus();
-    const long long n_wg = (n_wtiles + 3) / 4;
-    const int grid = (int)(n_wg < n_cus ? n_wg : n_cus);
-    const long long NW = (long long)grid * 4;
-    const long long it_flat = (n_wtiles + NW - 1) / NW, it_ray = (((long long)n_rays + NW - 1) / NW) * a.tpr;
-    if ((long long)n_rays >= NW && it_ray <= it_flat) { a.ppr = (unsigned)a.tpr; a.n_iter = (unsigned)it_ray; }      // ray-major: whole rays per wave
-    else { a.ppr = 0; a.n_iter = (unsigned)it_flat; }
+    const int grid = persistent_grid((n_wtiles + 3) / 4);
+    const WalkPlan plan = walk_plan(n_rays, a.tpr, n_wtiles, grid, 4);
+    a.ppr = plan.ray_major ? (unsigned)a.tpr : 0;
+    a.n_iter = (unsigned)plan.n_iter;
     if constexpr (STASH) {
         a.stash_h = stash->h; a.stash_f = stash->f; a.stash_g = stash->g; a.mask_h = stash->mask_h; a.mask_g = stash->mask_g;
         a.stash_rows = (long long)n_rays * S;

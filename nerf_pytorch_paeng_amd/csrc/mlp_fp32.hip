@@ -14,6 +14,9 @@
 //   * gamma(x) is computed in registers per lane (sin on lanes 0-31, cos on lanes 32-63 of each k-step);
 //     in fused mode the view-direction block of linear_d is hoisted to a per-ray bias (it is constant
 //     over a ray's samples), density and colour heads run on the VALU as register dot products.
+// Where the parts that are not this kernel's matrix schedule live: the arguments, their fillers, the tile walk (RayTileWalk) and the launch
+// plan -- mlp_core.h, shared with mlp_fp32_wide.hip (the ray-major / flat decision itself: walk_plan.h); the point build, the fast / libm
+// test and the hoisted view-direction term -- common.h, shared with the 16-bit kernels; the side-table record -- layout.h.
 #include <stdlib.h>
 #include <vector>
 #include "common.h"
@@ -22,38 +25,6 @@
 
 
 namespace minerf {
-
-
-struct MlpArgs {
-    const char* stream;       // device: blob + stream_off
-    const float* side;        // device: blob + side_off
-    const float* rays;        // MODE 0: [n_rays, 6]
-    const float* z;           // MODE 0: [n_rays, S]
-    const float* x;           // MODE 1: [n_pts, in_x + in_d] with the NETWORK's own widths in_x = 3 + 6 Lx_net, in_d = 3 + 6 Ld_net
-    int Lx_net, Ld_net;       // the network's frequencies (<= the kernel's LX / LD; the missing channels carry zero weights, layout.h)
-    float* out;               // [n_pts, 4]
-    long long n_wtiles;       // 32-point wave tiles
-    long long n_pts;          // MODE 1
-    // MODE 0 tile walk of one wave: start at wave id w (ray-major: ray w, chunk 0; tile-major: tile w), then per step
-    // (ray, chunk) += (walk_ray, walk_chunk), chunk overflow carries walk_carry rays.  n_iter steps for every wave.
-    long long n_rays, walk_ray, walk_carry, n_iter;
-    int walk_chunk, ray_major;
-    int S;                    // MODE 0
-    int tpr;                  // MODE 0: wave tiles per ray = ceil(S / 32)
-    int D;
-    int skip_layer;           // trunk layer index that consumes [gamma(x), h]; -1: none
-    unsigned stream_bytes;    // hoisted or full length, multiple of SLOT_BYTES
-    unsigned side_floats;
-    unsigned o_bias_trunk, o_bias_feat, o_bias_d, o_dens_w, o_dens_b, o_color_w, o_color_b, o_wdir_t;
-    unsigned long long* diag;  // MN_DIAG builds only: per-wave segment cycle sums + one tile's k-quad stamps
-    // STASH kernels (training forward): row-major activations kept for the backward pass, P = stash_rows points
-    float* stash_h;           // [D][P][W]   post-ReLU output of trunk layer l
-    float* stash_f;           // [P][W]      linear_feat output
-    float* stash_g;           // [P][W/2]    post-ReLU linear_d output
-    unsigned* mask_h;         // [D][n_wtiles][64 lanes][4]  ReLU' bits of stash_h in the kernel's register order
-    unsigned* mask_g;         // [n_wtiles][64 lanes][2]     ... of stash_g
-    long long stash_rows;
-};
 
 
 // encoded-input registers for k-step s: level k = s/3, axis c = s%3
@@ -85,6 +56,35 @@ __device__ __forceinline__ void gather_regs(float (&pe)[NPE], const float* row, 
     for (int s = 3 * L + 2; s < NPE; ++s) pe[s] = 0.0f;
 }
 
+// One GEMM part over a trunk layer's output: acc += stream x h, h = the post-ReLU output of trunk layer `layer`; NEXT = tiles of the part that
+// follows.  STASH (training forward): every activation row is written while this GEMM consumes the same registers as its B operand -- one
+// 16-byte store per k-quad from the group hook -- and the ReLU' bit masks are packed there too, then stored for tile `wt`.
+// (A function, not a lambda of the kernel: as a closure it cost the 256-wide MODE 1 kernels, at 506 of 512 registers, 67 spilled ones.)
+template <int W, bool STASH, int NEXT, int AL, int HN>
+__device__ __forceinline__ void hidden_gemm(const MlpArgs& a, int layer, long long out_idx, long long wt, bool wave_active, f32x16 (&acc)[8],
+                                            const float (&h)[HN], f32x4 (&aq)[8], const char* smem, WRing& ring, int lane, int hh) {
+    constexpr int NT = W / 32;
+    // groups (t) of a k-quad that carry the training hooks: ReLU' bits, their merge, the row store
+    constexpr int HK_B = NT - 3, HK_M = NT - 2, HK_S = NT - 1;
+    if constexpr (STASH) {
+        float* row = a.stash_h + ((long long)layer * a.stash_rows + out_idx) * W + 4 * hh;
+        unsigned mw[4] = {0u, 0u, 0u, 0u};
+        unsigned mb[4];
+        auto hook = [&](int kq, int t) __attribute__((always_inline)) {
+            if (t == HK_B) mask_bits_chunk(h, kq, mb);
+            if (t == HK_M) mask_merge_chunk(mb, kq, mw);
+            if (t == HK_S) store_chunk(h, kq, row);
+        };
+        gemm_part<NT, HN, NEXT, AL>(acc, h, aq, smem, ring, lane, hook);
+        if (wave_active) {
+            u32x4 m; m[0] = mw[0]; m[1] = mw[1]; m[2] = mw[2]; m[3] = mw[3];
+            *(u32x4*)(a.mask_h + (((long long)layer * a.n_wtiles + wt) * 64 + lane) * 4) = m;
+        }
+    } else {
+        gemm_part<NT, HN, NEXT, AL>(acc, h, aq, smem, ring, lane);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // the kernel.  MODE 0: rays + z (fused posenc, hoisted view-direction bias).  MODE 1: embedded rows.
 // ---------------------------------------------------------------------------------------------
@@ -95,9 +95,6 @@ void mlp_fp32_kernel(const MlpArgs a) {
     constexpr int HN = W / 2;           // activation registers per lane
     constexpr int KPE = pe_ksteps(LX);  // 32
     constexpr int KDE = pe_ksteps(LD);  // 16
-    constexpr int IN_D = 3 + 6 * LD;
-    // groups (t) of a k-quad that carry the training hooks: ReLU' bits, their merge, the row store
-    constexpr int HK_B = NT - 3, HK_M = NT - 2, HK_S = NT - 1;
     constexpr int AL = STASH ? 8 : 4;         // ring_advance<ALLOW>: the training forward interleaves row stores with the DMAs
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* side = (float*)(smem + RING_BYTES);
@@ -130,25 +127,12 @@ void mlp_fp32_kernel(const MlpArgs a) {
     // w + #waves, ...) and their 32-sample chunks back to back, so the per-ray work of the prologue (view-direction
     // encoding and its hoisted linear_d term, ~550 VALU per lane) is done once per ray instead of once per tile.  Small
     // batches keep the tile-major walk (tile w, w + #waves, ...), which spreads few rays over more workgroups.
-    // The inputs of the NEXT tile (six ray scalars, one depth per lane) are loaded a whole tile ahead.
-    long long t_ray = 0;
-    int t_chunk = 0;
+    // The inputs of the NEXT tile (six ray scalars, one depth per lane) are loaded a whole tile ahead (RayTileWalk, mlp_core.h; the
+    // host side of the decision: plan_launch).
+    RayTileWalk<32> walk = {};
     long long bias_ray = -1;            // ray whose hoisted direction term sits in `scratch`
-    float nx_o[3] = {0.f, 0.f, 0.f}, nx_d[3] = {0.f, 0.f, 0.f}, nx_z = 0.f;
-    auto tile_inputs = [&](long long ray, int chunk) __attribute__((always_inline)) {
-        const int sample = chunk * 32 + col;
-        const int sc = sample < a.S ? sample : a.S - 1;
-        const float* rp = a.rays + ray * 6;
-        nx_o[0] = rp[0]; nx_o[1] = rp[1]; nx_o[2] = rp[2]; nx_d[0] = rp[3]; nx_d[1] = rp[4]; nx_d[2] = rp[5];
-        nx_z = a.z[ray * a.S + sc];
-    };
     const long long wid = (long long)blockIdx.x * 4 + wave;
-    if constexpr (MODE == 0) {
-        if (a.ray_major) { t_ray = wid; t_chunk = 0; }
-        else { t_ray = wid / a.tpr; t_chunk = (int)(wid - t_ray * a.tpr); }
-        const bool in = t_ray < a.n_rays;
-        tile_inputs(in ? t_ray : a.n_rays - 1, in ? t_chunk : a.tpr - 1);
-    }
+    if constexpr (MODE == 0) walk.start(a, wid, col);
     for (long long it = 0; it < a.n_iter; ++it) {
 #ifdef MN_DIAG
         ring.dlog = (a.diag && it == 2 && blockIdx.x < 4) ? a.diag + (size_t)gridDim.x * 32 + ((size_t)blockIdx.x * 4 + wave) * 512 : nullptr;
@@ -160,55 +144,25 @@ void mlp_fp32_kernel(const MlpArgs a) {
         long long out_idx;
         float de[KDE];
         if constexpr (MODE == 0) {
-            wave_active = t_ray < a.n_rays;
-            const long long ray = wave_active ? t_ray : a.n_rays - 1;          // the tail recomputes the last tile
-            const int chunk = wave_active ? t_chunk : a.tpr - 1;
+            wave_active = walk.active(a);
+            const long long ray = walk.ray(a);                                 // the tail recomputes the last tile
+            const int chunk = walk.chunk(a);
             wt = ray * a.tpr + chunk;
             const int sample = chunk * 32 + col;
             valid = wave_active && sample < a.S;
             const int sc = sample < a.S ? sample : a.S - 1;
             out_idx = ray * a.S + sc;
-            const float ox = nx_o[0], oy = nx_o[1], oz = nx_o[2], dx = nx_d[0], dy = nx_d[1], dz = nx_d[2];
-            const float zv = nx_z;
-            // advance to this wave's next tile and start loading its inputs now
-            t_ray += a.walk_ray;
-            t_chunk += a.walk_chunk;
-            if (t_chunk >= a.tpr) { t_chunk -= a.tpr; t_ray += a.walk_carry; }
-            {
-                const bool in = t_ray < a.n_rays;
-                tile_inputs(in ? t_ray : a.n_rays - 1, in ? t_chunk : a.tpr - 1);
-            }
-            // pts = rays_o + rays_d * z : separate multiply and add (nerf_process.py:69-70), no contraction
-            const float p[3] = {ox + dx * zv, oy + dy * zv, oz + dz * zv};
-            const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(p[0]), __builtin_fabsf(p[1])), __builtin_fabsf(p[2])) * (float)(1 << (LX - 1));
-            if (__builtin_expect(amax < SINCOS_FAST_LIMIT, 1)) encode_regs<LX, false>(pe, p, hh);
+            const float o[3] = {walk.o[0], walk.o[1], walk.o[2]}, d[3] = {walk.d[0], walk.d[1], walk.d[2]};
+            const float zv = walk.z;
+            walk.advance(a, col);       // to this wave's next tile: its loads start now
+            float p[3];
+            sample_point(p, o, d, zv);
+            if (__builtin_expect(point_is_fast<LX>(p), 1)) encode_regs<LX, false>(pe, p, hh);
             else encode_regs<LX, true>(pe, p, hh);               // huge or non-finite coordinates: libm path
-            // hoisted view-direction term of linear_d: scratch[n] = b_d[n] + sum_f Wd[n][W+f] * gamma(d/|d|)[f]
-            // (per RAY: kept in this wave's LDS scratch while the wave stays on the ray)
+            // hoisted view-direction term of linear_d, per RAY: kept in this wave's LDS scratch while the wave stays on the ray
             if (ray != bias_ray) {
                 bias_ray = ray;
-                const float nrm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-                const float v[3] = {dx / nrm, dy / nrm, dz / nrm};
-                float g[IN_D];
-                g[0] = v[0]; g[1] = v[1]; g[2] = v[2];
-#pragma unroll
-                for (int k = 0; k < LD; ++k)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float y = v[c] * (float)(1 << k);
-                        g[3 + 6 * k + c] = sin_cos_fast(y, 0);       // |y| <= 2^(LD-1): no fallback needed
-                        g[3 + 6 * k + 3 + c] = sin_cos_fast(y, 1);
-                    }
-                const float* wdt = side + a.o_wdir_t;
-                const float* bd = side + a.o_bias_d;
-#pragma unroll
-                for (int n0 = 0; n0 < W / 2; n0 += 64) {
-                    const int n = n0 + lane;
-                    float sacc = bd[n];
-#pragma unroll
-                    for (int f = 0; f < IN_D; ++f) sacc = __builtin_fmaf(wdt[f * (W / 2) + n], g[f], sacc);
-                    scratch[n] = sacc;
-                }
+                hoisted_dir_bias<W, LD>(scratch, d[0], d[1], d[2], side + a.o_wdir_t, side + a.o_bias_d, lane);
             }
         } else {
             wt = it * ((long long)gridDim.x * 4) + wid;
@@ -235,23 +189,7 @@ void mlp_fp32_kernel(const MlpArgs a) {
             acc_to_b<NT, true>(acc, h);
             acc_init<NT>(acc, side + a.o_bias_trunk + l * W, hh);
             if (l == a.skip_layer) gemm_part<NT, KPE, NT, AL>(acc, pe, aq, smem, ring, lane);   // cat([gamma(x), h]) order
-            if constexpr (STASH) {
-                float* row = a.stash_h + ((long long)(l - 1) * a.stash_rows + out_idx) * W + 4 * hh;
-                unsigned mw[4] = {0u, 0u, 0u, 0u};
-                unsigned mb[4];
-                auto hook = [&](int kq, int t) __attribute__((always_inline)) {
-                    if (t == HK_B) mask_bits_chunk(h, kq, mb);
-                    if (t == HK_M) mask_merge_chunk(mb, kq, mw);
-                    if (t == HK_S) store_chunk(h, kq, row);
-                };
-                gemm_part<NT, HN, NT, AL>(acc, h, aq, smem, ring, lane, hook);
-                if (wave_active) {
-                    u32x4 m; m[0] = mw[0]; m[1] = mw[1]; m[2] = mw[2]; m[3] = mw[3];
-                    *(u32x4*)(a.mask_h + (((long long)(l - 1) * a.n_wtiles + wt) * 64 + lane) * 4) = m;
-                }
-            } else {
-                gemm_part<NT, HN, NT, AL>(acc, h, aq, smem, ring, lane);
-            }
+            hidden_gemm<W, STASH, NT, AL>(a, l - 1, out_idx, wt, wave_active, acc, h, aq, smem, ring, lane, hh);
         }
         acc_to_b<NT, true>(acc, h);
         MN_STAMP(2);   // trunk layers 1..D-1
@@ -259,48 +197,21 @@ void mlp_fp32_kernel(const MlpArgs a) {
         const float dens = xhalf_sum(dot_half<HN>(h, side + a.o_dens_w, hh)) + side[a.o_dens_b];
         // ---- feature layer (no activation) ----
         acc_init<NT>(acc, side + a.o_bias_feat, hh);
-        if constexpr (STASH) {
-            float* row = a.stash_h + ((long long)(a.D - 1) * a.stash_rows + out_idx) * W + 4 * hh;
-            unsigned mw[4] = {0u, 0u, 0u, 0u};
-            unsigned mb[4];
-            auto hook = [&](int kq, int t) __attribute__((always_inline)) {
-                if (t == HK_B) mask_bits_chunk(h, kq, mb);
-                if (t == HK_M) mask_merge_chunk(mb, kq, mw);
-                if (t == HK_S) store_chunk(h, kq, row);
-            };
-            gemm_part<NT, HN, NT / 2, AL>(acc, h, aq, smem, ring, lane, hook);
-            if (wave_active) {
-                u32x4 m; m[0] = mw[0]; m[1] = mw[1]; m[2] = mw[2]; m[3] = mw[3];
-                *(u32x4*)(a.mask_h + (((long long)(a.D - 1) * a.n_wtiles + wt) * 64 + lane) * 4) = m;
-            }
-        } else {
-            gemm_part<NT, HN, NT / 2, AL>(acc, h, aq, smem, ring, lane);
-        }
+        hidden_gemm<W, STASH, NT / 2, AL>(a, a.D - 1, out_idx, wt, wave_active, acc, h, aq, smem, ring, lane, hh);
         acc_to_b<NT, false>(acc, h);
         MN_STAMP(3);   // density head + feature layer
-        // ---- view-direction layer ----
+        // ---- view-direction layer: over linear_feat's output (STASH: its rows leave from the last tile's groups), then MODE 0 has gamma(d)'s
+        // term in its bias, MODE 1 multiplies it ----
+        float* const row_f = STASH ? a.stash_f + out_idx * W + 4 * hh : nullptr;
+        auto feat_hook = [&](int kq, int t) __attribute__((always_inline)) {
+            if (STASH && t == NT / 2 - 1) store_chunk(h, kq, row_f);
+        };
         if constexpr (MODE == 0) {
             acc_init<NT / 2>(acc, scratch, hh);
-            if constexpr (STASH) {
-                float* row = a.stash_f + out_idx * W + 4 * hh;
-                auto hook = [&](int kq, int t) __attribute__((always_inline)) {
-                    if (t == NT / 2 - 1) store_chunk(h, kq, row);
-                };
-                gemm_part<NT / 2, HN, NT, AL>(acc, h, aq, smem, ring, lane, hook);
-            } else {
-                gemm_part<NT / 2, HN, NT, AL>(acc, h, aq, smem, ring, lane);
-            }
+            gemm_part<NT / 2, HN, NT, AL>(acc, h, aq, smem, ring, lane, feat_hook);
         } else {
             acc_init<NT / 2>(acc, side + a.o_bias_d, hh);
-            if constexpr (STASH) {
-                float* row = a.stash_f + out_idx * W + 4 * hh;
-                auto hook = [&](int kq, int t) __attribute__((always_inline)) {
-                    if (t == NT / 2 - 1) store_chunk(h, kq, row);
-                };
-                gemm_part<NT / 2, HN, NT / 2, AL>(acc, h, aq, smem, ring, lane, hook);
-            } else {
-                gemm_part<NT / 2, HN, NT / 2, AL>(acc, h, aq, smem, ring, lane);
-            }
+            gemm_part<NT / 2, HN, NT / 2, AL>(acc, h, aq, smem, ring, lane, feat_hook);
             gemm_part<NT / 2, KDE, NT, AL>(acc, de, aq, smem, ring, lane);
         }
         float h2[HN / 2];
@@ -351,37 +262,18 @@ static int check_net(const mi_nerf_net* net) {
     return MI_NERF_OK;
 }
 
-static int num_cus() { return device_cus(); }
-
 // networks wider than 256 (padded to 512): mlp_fp32_wide.hip
 int mlp_rays_fp32_wide(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, hipStream_t);
 int mlp_embedded_fp32_wide(const mi_nerf_net*, const void*, const float*, int64_t, float*, hipStream_t);
 
 template <int W, int MODE, bool STASH = false>
-static int launch(const MlpArgs& args_in, long long n_wtiles, hipStream_t st) {
+static int launch(const MlpArgs& args_in, hipStream_t st) {
     MlpArgs args = args_in;
-    const size_t lds = RING_BYTES + (size_t)args.side_floats * 4 + 4 * (W / 2) * 4;
-    MN_CHECK_ARG(lds <= 160 * 1024, "LDS budget exceeded: %zu bytes", lds);
     auto kern = mlp_fp32_kernel<W, MODE, 10, 4, STASH>;
     static LdsOptIn opt_in = {};                              // per template instantiation, per device
-    if (int rc = ensure_lds_opt_in(opt_in, (const void*)kern)) return rc;
-    const long long n_wg = (n_wtiles + 3) / 4;
-    const int grid = (int)(n_wg < (long long)num_cus() ? n_wg : (long long)num_cus());
-    {   // the tile walk (see the kernel): ray-major once every wave of the grid gets at least one whole ray
-        const long long NW = (long long)grid * 4;
-        // ... and dealing whole rays does not cost a round more than dealing tiles (1500 rays x 6 tiles on 1024 waves: 12 steps
-        // ray-major, 9 tile-major)
-        const long long it_ray = (args.n_rays + NW - 1) / NW * args.tpr, it_flat = (n_wg + grid - 1) / grid;
-        args.ray_major = (MODE == 0 && args.n_rays >= NW && it_ray <= it_flat) ? 1 : 0;
-        if (args.ray_major) {
-            args.walk_ray = 0; args.walk_chunk = 1; args.walk_carry = NW;
-            args.n_iter = (args.n_rays + NW - 1) / NW * args.tpr;
-        } else {
-            const long long tpr = MODE == 0 ? args.tpr : 1;
-            args.walk_ray = NW / tpr; args.walk_chunk = (int)(NW % tpr); args.walk_carry = 1;
-            args.n_iter = (n_wg + grid - 1) / grid;
-        }
-    }
+    size_t lds;
+    int grid;
+    if (int rc = plan_launch<W, MODE>(args, (const void*)kern, opt_in, lds, grid)) return rc;
 #ifdef MN_DIAG
     {   // diagnostic build: run once with stamps and print the per-segment averages (cycles per tile per wave)
         MlpArgs da = args;
@@ -395,7 +287,7 @@ static int launch(const MlpArgs& args_in, long long n_wtiles, hipStream_t st) {
         std::vector<unsigned long long> hbuf(n);
         MN_HIP(hipMemcpy(hbuf.data(), dbuf, n * 8, hipMemcpyDeviceToHost));
         (void)hipFree(dbuf);
-        const double tiles = (double)((n_wg + grid - 1) / grid);
+        const double tiles = (double)((args.n_wtiles + 4 * grid - 1) / (4 * grid));
         static const char* names[6] = {"prologue", "layer0", "trunk", "dens+feature", "viewdir", "colour+store"};
         double tot = 0;
         fprintf(stderr, "[mn_diag] W=%d MODE=%d grid=%d tiles/wg=%.1f  cycles per tile (mean over waves):\n", W, MODE, grid, tiles);
@@ -422,20 +314,6 @@ static int launch(const MlpArgs& args_in, long long n_wtiles, hipStream_t st) {
     return MI_NERF_OK;
 }
 
-static void fill_common(MlpArgs& a, const mi_nerf_net* net, const void* packed_dev, bool full_stream) {
-    const BlobLayout L = make_layout(net->D, net->W, net->skip, net->L_x, net->L_d);
-    a.stream = (const char*)packed_dev + L.stream_off;
-    a.side = (const float*)((const char*)packed_dev + L.side_off);
-    a.D = net->D;
-    a.Lx_net = net->L_x; a.Ld_net = net->L_d;
-    a.skip_layer = (net->skip >= 0 && net->skip + 1 < net->D) ? net->skip + 1 : -1;
-    a.stream_bytes = full_stream ? L.stream_bytes_full : L.stream_bytes_hoist;
-    a.side_floats = L.side_floats;
-    a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d;
-    a.o_dens_w = L.dens_w; a.o_dens_b = L.dens_b; a.o_color_w = L.color_w; a.o_color_b = L.color_b;
-    a.o_wdir_t = L.wdir_t;
-}
-
 int mlp_rays_fp32(const mi_nerf_net* net, const void* packed_dev, const float* rays_dev, const float* z_dev,
                   int64_t n_rays, int S, float* raw_dev, hipStream_t st) {
     if (int rc = check_net(net)) return rc;
@@ -445,9 +323,8 @@ int mlp_rays_fp32(const mi_nerf_net* net, const void* packed_dev, const float* r
     if (wide_kernel_width(kernel_width(net->W))) return mlp_rays_fp32_wide(net, packed_dev, rays_dev, z_dev, n_rays, S, raw_dev, st);
     MlpArgs a{};
     fill_common(a, net, packed_dev, false);
-    a.rays = rays_dev; a.z = z_dev; a.out = raw_dev; a.S = S; a.tpr = (S + 31) / 32;
-    a.n_wtiles = (long long)n_rays * a.tpr; a.n_rays = n_rays;
-    return kernel_width(net->W) == 256 ? launch<256, 0>(a, a.n_wtiles, st) : launch<128, 0>(a, a.n_wtiles, st);
+    fill_rays<32>(a, rays_dev, z_dev, n_rays, S, raw_dev);
+    return kernel_width(net->W) == 256 ? launch<256, 0>(a, st) : launch<128, 0>(a, st);
 }
 
 // training forward: same kernel, additionally keeping every layer's activations row-major for the backward pass
@@ -461,11 +338,10 @@ int mlp_rays_fp32_stash(const mi_nerf_net* net, const void* packed_dev, const fl
     MN_CHECK_ARG(packed_dev && rays_dev && z_dev && raw_dev && stash_h && stash_f && stash_g && mask_h && mask_g, "NULL device pointer");
     MlpArgs a{};
     fill_common(a, net, packed_dev, false);
-    a.rays = rays_dev; a.z = z_dev; a.out = raw_dev; a.S = S; a.tpr = (S + 31) / 32;
-    a.n_wtiles = (long long)n_rays * a.tpr; a.n_rays = n_rays;
+    fill_rays<32>(a, rays_dev, z_dev, n_rays, S, raw_dev);
     a.stash_h = stash_h; a.stash_f = stash_f; a.stash_g = stash_g; a.stash_rows = (long long)n_rays * S;
     a.mask_h = mask_h; a.mask_g = mask_g;
-    return net->W == 256 ? launch<256, 0, true>(a, a.n_wtiles, st) : launch<128, 0, true>(a, a.n_wtiles, st);
+    return net->W == 256 ? launch<256, 0, true>(a, st) : launch<128, 0, true>(a, st);
 }
 
 // training forward over pre-embedded rows (model/NeRF.py:33-52 called directly with gradients enabled): flat 32-row tiles;
@@ -483,7 +359,7 @@ int mlp_embedded_fp32_stash(const mi_nerf_net* net, const void* packed_dev, cons
     a.n_wtiles = (n + 31) / 32;
     a.stash_h = stash_h; a.stash_f = stash_f; a.stash_g = stash_g; a.stash_rows = a.n_wtiles * 32;
     a.mask_h = mask_h; a.mask_g = mask_g;
-    return net->W == 256 ? launch<256, 1, true>(a, a.n_wtiles, st) : launch<128, 1, true>(a, a.n_wtiles, st);
+    return net->W == 256 ? launch<256, 1, true>(a, st) : launch<128, 1, true>(a, st);
 }
 
 int mlp_embedded_fp32(const mi_nerf_net* net, const void* packed_dev, const float* x_dev, int64_t n, float* out_dev,
@@ -497,7 +373,7 @@ int mlp_embedded_fp32(const mi_nerf_net* net, const void* packed_dev, const floa
     fill_common(a, net, packed_dev, true);
     a.x = x_dev; a.out = out_dev; a.n_pts = n;
     a.n_wtiles = (n + 31) / 32;
-    return kernel_width(net->W) == 256 ? launch<256, 1>(a, a.n_wtiles, st) : launch<128, 1>(a, a.n_wtiles, st);
+    return kernel_width(net->W) == 256 ? launch<256, 1>(a, st) : launch<128, 1>(a, st);
 }
 
 }  // namespace minerf

@@ -13,6 +13,7 @@
 // Two differences: the 8-pass MFMA needs 40 cycles before its accumulator can be chained, so a group interleaves TWO output tiles (each
 // accumulator every 64 cycles); and a k-quad of a 512-wide layer is 32 quads = two ring slots, so the A-operand pipeline is a rotating
 // file of 8 quads read 8 positions ahead instead of one register per output tile.
+// The front end is literally that kernel's: MlpArgs, fill_common / fill_rays<16>, plan_launch and RayTileWalk<16> of mlp_core.h.
 #include <stdlib.h>
 #include "common.h"
 #include "layout.h"
@@ -20,23 +21,7 @@
 
 namespace minerf {
 
-struct WideArgs {
-    const char* stream;
-    const float* side;
-    const float* rays;        // MODE 0: [n_rays, 6]
-    const float* z;           // MODE 0: [n_rays, S]
-    const float* x;           // MODE 1: [n_pts, in_x + in_d], the network's own widths
-    int Lx_net, Ld_net;
-    float* out;               // [n_pts, 4]
-    long long n_wtiles;       // 16-point wave tiles
-    long long n_pts;          // MODE 1
-    long long n_rays, walk_ray, walk_carry, n_iter;      // MODE 0 tile walk (mlp_fp32.hip)
-    int walk_chunk, ray_major;
-    int S, tpr;               // MODE 0: wave tiles per ray = ceil(S / 16)
-    int D, skip_layer;
-    unsigned stream_bytes, side_floats;
-    unsigned o_bias_trunk, o_bias_feat, o_bias_d, o_dens_w, o_dens_b, o_color_w, o_color_b, o_wdir_t;
-};
+// (the arguments, MlpArgs with 16-point wave tiles, their fillers, the tile walk and the launch plan are mlp_core.h's, shared with mlp_fp32.hip)
 
 // ---- building blocks in the 16x16 layout (lane = (col = lane & 15: the point, q4 = lane >> 4: the quarter)) ----------------------------------
 template <int NTP>
@@ -142,12 +127,11 @@ __device__ __forceinline__ void gather_regs16(float (&pe)[NPE], const float* row
 
 template <int W, int MODE, int LX, int LD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void mlp_fp32_wide_kernel(const WideArgs a) {
+void mlp_fp32_wide_kernel(const MlpArgs a) {
     constexpr int NT = W / 16;            // output tiles of a W-wide layer (32)
     constexpr int HN = W / 4;             // activation registers per lane (128)
     constexpr int KPE = pe_ksteps16(LX);  // 16
     constexpr int KDE = pe_ksteps16(LD);  // 8
-    constexpr int IN_D = 3 + 6 * LD;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* side = (float*)(smem + RING_BYTES);
     const int tid = threadIdx.x;
@@ -169,72 +153,29 @@ void mlp_fp32_wide_kernel(const WideArgs a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) aq[i] = ring_read(smem, ring, lane, i);
 
-    long long t_ray = 0;
-    int t_chunk = 0;
+    RayTileWalk<16> walk = {};              // MODE 0: this wave's tiles, the next one's inputs loaded a tile ahead (mlp_core.h)
     long long bias_ray = -1;
-    float nx_o[3] = {0.f, 0.f, 0.f}, nx_d[3] = {0.f, 0.f, 0.f}, nx_z = 0.f;
-    auto tile_inputs = [&](long long ray, int chunk) __attribute__((always_inline)) {
-        const int sample = chunk * 16 + col;
-        const int sc = sample < a.S ? sample : a.S - 1;
-        const float* rp = a.rays + ray * 6;
-        nx_o[0] = rp[0]; nx_o[1] = rp[1]; nx_o[2] = rp[2]; nx_d[0] = rp[3]; nx_d[1] = rp[4]; nx_d[2] = rp[5];
-        nx_z = a.z[ray * a.S + sc];
-    };
     const long long wid = (long long)blockIdx.x * 4 + wave;
-    if constexpr (MODE == 0) {
-        if (a.ray_major) { t_ray = wid; t_chunk = 0; }
-        else { t_ray = wid / a.tpr; t_chunk = (int)(wid - t_ray * a.tpr); }
-        const bool in = t_ray < a.n_rays;
-        tile_inputs(in ? t_ray : a.n_rays - 1, in ? t_chunk : a.tpr - 1);
-    }
+    if constexpr (MODE == 0) walk.start(a, wid, col);
     for (long long it = 0; it < a.n_iter; ++it) {
         bool valid;
         long long out_idx;
         float de[KDE];
         if constexpr (MODE == 0) {
-            const bool wave_active = t_ray < a.n_rays;
-            const long long ray = wave_active ? t_ray : a.n_rays - 1;          // the tail recomputes the last tile
-            const int chunk = wave_active ? t_chunk : a.tpr - 1;
-            const int sample = chunk * 16 + col;
-            valid = wave_active && sample < a.S;
+            const long long ray = walk.ray(a);                                 // the tail recomputes the last tile
+            const int sample = walk.chunk(a) * 16 + col;
+            valid = walk.active(a) && sample < a.S;
             out_idx = ray * a.S + (sample < a.S ? sample : a.S - 1);
-            const float ox = nx_o[0], oy = nx_o[1], oz = nx_o[2], dx = nx_d[0], dy = nx_d[1], dz = nx_d[2];
-            const float zv = nx_z;
-            t_ray += a.walk_ray;
-            t_chunk += a.walk_chunk;
-            if (t_chunk >= a.tpr) { t_chunk -= a.tpr; t_ray += a.walk_carry; }
-            {
-                const bool in = t_ray < a.n_rays;
-                tile_inputs(in ? t_ray : a.n_rays - 1, in ? t_chunk : a.tpr - 1);
-            }
-            const float p[3] = {ox + dx * zv, oy + dy * zv, oz + dz * zv};     // nerf_process.py:69-70, no contraction
-            const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(p[0]), __builtin_fabsf(p[1])), __builtin_fabsf(p[2])) * (float)(1 << (LX - 1));
-            if (__builtin_expect(amax < SINCOS_FAST_LIMIT, 1)) encode_regs16<LX, false>(pe, p, q4);
+            const float o[3] = {walk.o[0], walk.o[1], walk.o[2]}, d[3] = {walk.d[0], walk.d[1], walk.d[2]};
+            const float zv = walk.z;
+            walk.advance(a, col);
+            float p[3];
+            sample_point(p, o, d, zv);
+            if (__builtin_expect(point_is_fast<LX>(p), 1)) encode_regs16<LX, false>(pe, p, q4);
             else encode_regs16<LX, true>(pe, p, q4);
-            if (ray != bias_ray) {        // hoisted view-direction term of linear_d, per ray: scratch[n] = b_d[n] + sum_f Wd[n][W + f] gamma(d / |d|)[f]
+            if (ray != bias_ray) {        // hoisted view-direction term of linear_d, per ray
                 bias_ray = ray;
-                const float nrm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-                const float v[3] = {dx / nrm, dy / nrm, dz / nrm};
-                float g[IN_D];
-                g[0] = v[0]; g[1] = v[1]; g[2] = v[2];
-#pragma unroll
-                for (int k = 0; k < LD; ++k)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float y = v[c] * (float)(1 << k);
-                        g[3 + 6 * k + c] = sin_cos_fast(y, 0);
-                        g[3 + 6 * k + 3 + c] = sin_cos_fast(y, 1);
-                    }
-                const float* wdt = side + a.o_wdir_t;
-                const float* bd = side + a.o_bias_d;
-#pragma unroll
-                for (int n0 = 0; n0 < W / 2; n0 += 64) {
-                    const int n = n0 + lane;
-                    float sacc = bd[n];
-#pragma unroll
-                    for (int f = 0; f < IN_D; ++f) sacc = __builtin_fmaf(wdt[f * (W / 2) + n], g[f], sacc);
-                    scratch[n] = sacc;
-                }
+                hoisted_dir_bias<W, LD>(scratch, d[0], d[1], d[2], side + a.o_wdir_t, side + a.o_bias_d, lane);
             }
         } else {
             long long wt = it * ((long long)gridDim.x * 4) + wid;
@@ -294,61 +235,33 @@ void mlp_fp32_wide_kernel(const WideArgs a) {
 // host side
 // ---------------------------------------------------------------------------------------------
 template <int W, int MODE>
-static int launch_wide(const WideArgs& args_in, long long n_wtiles, hipStream_t st) {
-    WideArgs args = args_in;
-    const size_t lds = RING_BYTES + (size_t)args.side_floats * 4 + 4 * (W / 2) * 4;
-    MN_CHECK_ARG(lds <= 160 * 1024, "LDS budget exceeded: %zu bytes (a %d-deep network of width > 256)", lds, args.D);
+static int launch_wide(const MlpArgs& args_in, hipStream_t st) {
+    MlpArgs args = args_in;
     auto kern = mlp_fp32_wide_kernel<W, MODE, KERNEL_LX, KERNEL_LD>;
     static LdsOptIn opt_in = {};
-    if (int rc = ensure_lds_opt_in(opt_in, (const void*)kern)) return rc;
-    const long long n_wg = (n_wtiles + 3) / 4;
-    const int grid = (int)(n_wg < (long long)device_cus() ? n_wg : (long long)device_cus());
-    const long long NW = (long long)grid * 4;
-    const long long it_ray = (args.n_rays + NW - 1) / NW * args.tpr, it_flat = (n_wg + grid - 1) / grid;
-    args.ray_major = (MODE == 0 && args.n_rays >= NW && it_ray <= it_flat) ? 1 : 0;
-    if (args.ray_major) {
-        args.walk_ray = 0; args.walk_chunk = 1; args.walk_carry = NW;
-        args.n_iter = it_ray;
-    } else {
-        const long long tpr = MODE == 0 ? args.tpr : 1;
-        args.walk_ray = NW / tpr; args.walk_chunk = (int)(NW % tpr); args.walk_carry = 1;
-        args.n_iter = it_flat;
-    }
+    size_t lds;
+    int grid;
+    if (int rc = plan_launch<W, MODE>(args, (const void*)kern, opt_in, lds, grid)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, args);
     MN_LAUNCH_CHECK("mlp_fp32_wide_kernel");
     return MI_NERF_OK;
 }
 
-static void fill_wide(WideArgs& a, const mi_nerf_net* net, const void* packed_dev, bool full_stream) {
-    const BlobLayout L = make_layout(net->D, net->W, net->skip, net->L_x, net->L_d);
-    a.stream = (const char*)packed_dev + L.stream_off;
-    a.side = (const float*)((const char*)packed_dev + L.side_off);
-    a.D = net->D;
-    a.Lx_net = net->L_x; a.Ld_net = net->L_d;
-    a.skip_layer = (net->skip >= 0 && net->skip + 1 < net->D) ? net->skip + 1 : -1;
-    a.stream_bytes = full_stream ? L.stream_bytes_full : L.stream_bytes_hoist;
-    a.side_floats = L.side_floats;
-    a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d;
-    a.o_dens_w = L.dens_w; a.o_dens_b = L.dens_b; a.o_color_w = L.color_w; a.o_color_b = L.color_b;
-    a.o_wdir_t = L.wdir_t;
-}
-
 // callers (mlp_fp32.hip) have checked the net and the pointers
 int mlp_rays_fp32_wide(const mi_nerf_net* net, const void* packed_dev, const float* rays_dev, const float* z_dev, int64_t n_rays, int S,
                        float* raw_dev, hipStream_t st) {
-    WideArgs a{};
-    fill_wide(a, net, packed_dev, false);
-    a.rays = rays_dev; a.z = z_dev; a.out = raw_dev; a.S = S; a.tpr = (S + 15) / 16;
-    a.n_wtiles = (long long)n_rays * a.tpr; a.n_rays = n_rays;
-    return kernel_width(net->W) == 384 ? launch_wide<384, 0>(a, a.n_wtiles, st) : launch_wide<512, 0>(a, a.n_wtiles, st);
+    MlpArgs a{};
+    fill_common(a, net, packed_dev, false);
+    fill_rays<16>(a, rays_dev, z_dev, n_rays, S, raw_dev);
+    return kernel_width(net->W) == 384 ? launch_wide<384, 0>(a, st) : launch_wide<512, 0>(a, st);
 }
 
 int mlp_embedded_fp32_wide(const mi_nerf_net* net, const void* packed_dev, const float* x_dev, int64_t n, float* out_dev, hipStream_t st) {
-    WideArgs a{};
-    fill_wide(a, net, packed_dev, true);
+    MlpArgs a{};
+    fill_common(a, net, packed_dev, true);
     a.x = x_dev; a.out = out_dev; a.n_pts = n;
     a.n_wtiles = (n + 15) / 16;
-    return kernel_width(net->W) == 384 ? launch_wide<384, 1>(a, a.n_wtiles, st) : launch_wide<512, 1>(a, a.n_wtiles, st);
+    return kernel_width(net->W) == 384 ? launch_wide<384, 1>(a, st) : launch_wide<512, 1>(a, st);
 }
 
 }  // namespace minerf

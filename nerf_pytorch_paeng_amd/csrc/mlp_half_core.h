@@ -1,6 +1,7 @@
 // mlp_half_core.h -- the one-MFMA-per-product kernel shared by the bf16 (mlp_bf16.hip) and f16 (mlp_f16.hip) variants: constants, the
 // fragment file, packing schedule, job(), the forward kernel body, its launcher and launch plan (the weight ring and the MFMA wrappers:
-// wstream_ring.h).  The element type is a template parameter (F16) decided with `if constexpr`; see mlp_bf16.hip for the design and
+// wstream_ring.h; the ray-major / flat decision and the walk's closed form: walk_plan.h; the f16 point encoder and the hoisted
+// view-direction term: common.h; the side-table record at the head of the arguments: layout.h).  The element type is a template parameter (F16) decided with `if constexpr`; see mlp_bf16.hip for the design and
 // mlp_f16.hip for what the f16 instantiation changes.
 #pragma once
 #include "wstream_ring.h"
@@ -27,9 +28,7 @@ struct PhaseB {
     unsigned n_iter;            // units per wave (the same for every wave: the ring barriers are workgroup-wide); a unit = NP / 2 tiles
     unsigned ppr;               // ray-major walk: units per ray (tpr / (NP / 2)); 0: flat walk
 };
-struct MlpArgsB {
-    const char* stream;
-    const float* side;
+struct MlpArgsB : SideTables {  // (layout.h; filled by half_layout.h's side_tables)
     const float* rays;
     const float* z;             // [n_rays, S] depths; NULL: the coarse pass draws its own stratified depths (strat_*) and writes them to z_out
     float* z_out;
@@ -38,9 +37,7 @@ struct MlpArgsB {
     float* out;
     PhaseB ph[2];               // one or two phases (see run_phase); the kernel's template arguments say how many and of which shape
     unsigned n_rays;
-    int S, tpr, D, skip_layer;
-    unsigned stream_bytes, side_floats;
-    unsigned o_bias_trunk, o_bias_feat, o_bias_d, o_head_b, o_wdir_t;
+    int S, tpr;
     unsigned long long* diag;   // MN_DIAG builds only: per-wave cycle sums of the kernel's segments
     // small coarse launches (one 32-point unit per wave, two units per ray: a workgroup's four waves hold rays 2b and 2b + 1 whole): the
     // workgroup composites its two rays and draws their fine depths in the kernel's epilogue (stage_dev.h), fz_on != 0
@@ -207,7 +204,7 @@ __device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, ch
                                           , unsigned long long (&seg)[8], unsigned long long& tprev
 #endif
                                           ) {
-    constexpr int NT = W / MT, KH = W / KF, KPE = enc_ksteps32(LX), IN_X = 3 + 6 * LX, IN_D = 3 + 6 * LD;
+    constexpr int NT = W / MT, KH = W / KF, KPE = enc_ksteps32(LX);
     constexpr int NTL = NP / 2;                              // 32-sample tiles per unit of work (point tile p: tile p >> 1, half p & 1)
     static_assert(KPE == 2 && NT == 16 && KH == 8 && (NP == 4 || NP == 2), "stream positions and the fragment file are laid out for 63 -> 64 encoded channels, W = 256, 4 or 2 point tiles");
     constexpr int BIG = 1 << 30;
@@ -218,19 +215,15 @@ __device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, ch
     char* pe_lds = pe_wave + lane * 16;
     // ---- tile walk: a wave takes UNITS of NTL consecutive 32-sample tiles = NP 16-point MFMA tiles (point tile p: 32-sample tile
     // p >> 1, half p & 1; a pair of tiles at NP = 4, one tile at NP = 2).  Ray-major (ppr > 0): a wave walks whole rays, so the
-    // hoisted view-direction term is computed once per ray; flat otherwise.  Inputs of the next unit are loaded a unit ahead.
+    // hoisted view-direction term is computed once per ray; flat otherwise (walk_plan.h).  Inputs of the next unit are loaded a unit ahead.
     const unsigned NW = gridDim.x * NWV, wid = blockIdx.x * NWV + wave;
-    auto pair_of = [&](unsigned it) -> unsigned {
-        if (ph.ppr) { const unsigned blk = it / ph.ppr; return (blk * NW + wid) * ph.ppr + (it - blk * ph.ppr); }
-        return it * NW + wid;
-    };
     // gamma(x) is computed ONCE per point: lane (q4, col) owns point `col` of point tile q4 (32-sample tile q4 >> 1, half q4 & 1),
     // encodes it and writes its fragments' dwords where the other lane quarters read them (the fragments are parked in LDS for the
     // skip layer anyway).  Each lane therefore loads one depth; the rays of both 32-sample tiles are loaded by every lane (the
     // hoisted view-direction term is computed per tile by the whole wave).
     unsigned n_tile[NTL];  float nx_r[NTL][6], nx_z;
     auto load_inputs = [&](unsigned it) __attribute__((always_inline)) {
-        const unsigned pr = pair_of(it);
+        const unsigned pr = walk_unit(it, ph.ppr, NW, wid);
         unsigned my_ray = 0, my_chunk = 0;                        // the tile this lane's own point belongs to (selected, not branched on: a lane-
 #pragma unroll
         for (int tl = 0; tl < NTL; ++tl) {                        // dependent branch inside the MFMA stream costs a lone wave more than the select)
@@ -326,22 +319,13 @@ __device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, ch
                 if constexpr (NTL == 2) return t1 ? v[1][c] : v[0][c];
                 else return v[0][c];
             };
-            // pts = rays_o + rays_d * z (nerf_process.py:69-70)
-            const float pt[3] = {mine(in_o, 0) + mine(in_d, 0) * in_z, mine(in_o, 1) + mine(in_d, 1) * in_z, mine(in_o, 2) + mine(in_d, 2) * in_z};
+            const float my_o[3] = {mine(in_o, 0), mine(in_o, 1), mine(in_o, 2)}, my_d[3] = {mine(in_d, 0), mine(in_d, 1), mine(in_d, 2)};
+            float pt[3];
+            sample_point(pt, my_o, my_d, in_z);
             float sn[LX][3], cs[LX][3];
-            if constexpr (F16) {
-                // f16: every channel evaluated on its own, as the split-precision kernel does (mlp_f16.hip: why not angle doubling)
-                const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(pt[0]), __builtin_fabsf(pt[1])), __builtin_fabsf(pt[2])) * (float)(1 << (LX - 1));
-                const bool fast = amax < SINCOS_FAST_LIMIT;
-#pragma unroll
-                for (int k = 0; k < LX; ++k)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float y = pt[c] * (float)(1 << k);
-                        sn[k][c] = fast ? sin_cos_fast(y, 0) : sin_cos_slow(y, 0);
-                        cs[k][c] = fast ? sin_cos_fast(y, 1) : sin_cos_slow(y, 1);
-                    }
-            } else
+            // f16: every channel evaluated on its own, as the split-precision kernel does (mlp_f16.hip: why not angle doubling)
+            if constexpr (F16) sincos_octaves<LX>(pt, point_is_fast<LX>(pt), sn, cs);
+            else
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 // octave 0: Cody-Waite + Cephes as in the fp32 kernel, with no libm path.  The multiple count rint(y * 2/pi) is an fp32
@@ -362,12 +346,7 @@ __device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, ch
                     cs[k][c] = __builtin_fmaf(-s2, sn[k - 1][c], 1.0f);
                 }
             }
-            auto chan = [&](int u) __attribute__((always_inline)) -> float {     // channel u of gamma(x); u is a constant at every use
-                if (u >= IN_X) return 0.0f;
-                if (u < 3) return pt[u];
-                const int k = (u - 3) / 6, r = (u - 3) % 6;
-                return r < 3 ? sn[k][r] : cs[k][r - 3];
-            };
+            auto chan = [&](int u) __attribute__((always_inline)) -> float { return gamma_channel<LX>(u, pt, sn, cs); };
             // fragment (point tile pq, k-step ks): lane quarter qq reads channels 32 ks + 8 qq + j of point `col` at
             // [fragment][(qq * 16 + col) * 16 bytes]: this lane writes those 16 bytes for every qq (at NP = 2 lane quarters 2, 3
             // write what quarters 0, 1 write: same bytes, same addresses)
@@ -397,29 +376,7 @@ __device__ __forceinline__ void run_phase(const MlpArgsB& a, const PhaseB ph, ch
 #pragma unroll
                     for (int n0 = 0; n0 < W / 2; n0 += 64) sc_t[n0 + lane] = scratch[n0 + lane];
                 } else {
-                    const float dx = in_d[tl][0], dy = in_d[tl][1], dz = in_d[tl][2];
-                    const float nrm = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-                    const float vdir[3] = {dx / nrm, dy / nrm, dz / nrm};
-                    float g[IN_D];
-                    g[0] = vdir[0]; g[1] = vdir[1]; g[2] = vdir[2];
-#pragma unroll
-                    for (int k = 0; k < LD; ++k)
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const float y = vdir[c] * (float)(1 << k);
-                            g[3 + 6 * k + c] = sin_cos_fast(y, 0);
-                            g[3 + 6 * k + 3 + c] = sin_cos_fast(y, 1);
-                        }
-                    const float* wdt = side + a.o_wdir_t;
-                    const float* bd = side + a.o_bias_d;
-#pragma unroll
-                    for (int n0 = 0; n0 < W / 2; n0 += 64) {
-                        const int n = n0 + lane;
-                        float s = bd[n];
-#pragma unroll
-                        for (int f = 0; f < IN_D; ++f) s = __builtin_fmaf(wdt[f * (W / 2) + n], g[f], s);
-                        sc_t[n] = s;
-                    }
+                    hoisted_dir_bias<W, LD>(sc_t, in_d[tl][0], in_d[tl][1], in_d[tl][2], side + a.o_wdir_t, side + a.o_bias_d, lane);
                 }
             }
         }
@@ -671,17 +628,12 @@ static PhaseB make_phase(const MlpArgsB& a, long long tile0, long long tile_end,
     constexpr int NTL = NP / 2;
     PhaseB ph{};
     ph.tile0 = (unsigned)tile0; ph.tile_end = (unsigned)tile_end;
-    const long long NW = (long long)grid * NWV;
     const long long n_units = (tile_end - tile0 + NTL - 1) / NTL;
     const long long n_rays = (tile_end + a.tpr - 1) / a.tpr;     // rays this phase touches when it starts at tile 0
-    const long long it_flat = (n_units + NW - 1) / NW, it_ray = ((n_rays + NW - 1) / NW) * (a.tpr / NTL);
-    if (tile0 == 0 && a.tpr % NTL == 0 && n_rays >= NW && it_ray <= it_flat) {
-        ph.ppr = (unsigned)(a.tpr / NTL);                    // ray-major: every wave gets whole rays (tiles >= tile_end are skipped), unless
-        ph.n_iter = (unsigned)it_ray;                        // dealing whole rays would cost a round more than dealing units
-    } else {
-        ph.ppr = 0;
-        ph.n_iter = (unsigned)it_flat;
-    }
+    // whole rays per wave (tiles >= tile_end are skipped) only for a phase that starts at a ray's first tile, with rays of whole units
+    const WalkPlan plan = walk_plan(n_rays, a.tpr / NTL, n_units, grid, NWV, tile0 == 0 && a.tpr % NTL == 0);
+    ph.ppr = plan.ray_major ? (unsigned)(a.tpr / NTL) : 0;
+    ph.n_iter = (unsigned)plan.n_iter;
     return ph;
 }
 
@@ -703,12 +655,10 @@ static int launch_half(MlpArgsB a, long long split, long long n_wtiles, hipStrea
     }();
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)kern)) return rc;
-    const int n_cus = device_cus();
     const long long wg_a = ((split + NPA / 2 - 1) / (NPA / 2) + NWV - 1) / NWV;
     constexpr int TPB = NPB ? NPB / 2 : 1;                    // tiles per unit of the second phase (1: no second phase, wg_b unused)
     const long long wg_b = NPB ? ((n_wtiles - split + TPB - 1) / TPB + NWV - 1) / NWV : 0;
-    const long long n_wg = wg_a > wg_b ? wg_a : wg_b;
-    const int grid = (int)(n_wg < n_cus ? n_wg : n_cus);
+    const int grid = persistent_grid(wg_a > wg_b ? wg_a : wg_b);
     a.ph[0] = make_phase<NPA, NWV>(a, 0, split, grid);
     if constexpr (NPB != 0) a.ph[1] = make_phase<NPB, NWV>(a, split, n_wtiles, grid);
 #ifdef MN_DIAG
@@ -765,17 +715,12 @@ static int mlp_rays_half(const mi_nerf_net* net, const HalfLayout& L, const void
         a.strat_step = S > 1 ? 1.0f / (float)(S - 1) : 0.0f;
         a.strat_jitter = Jitter{strat->t_rand, strat->seed, 0u, (long long)strat->ray0};
     }
-    a.stream = (const char*)packed_dev + L.stream_off;
-    a.side = (const float*)((const char*)packed_dev + L.side_off);
+    (SideTables&)a = side_tables(L, packed_dev, net->D, net->skip, L.walk_bytes);
     a.rays = rays_dev; a.z = z_dev; a.out = raw_dev;
     a.S = S; a.tpr = (S + 31) / 32;
     const long long n_wtiles = (long long)n_rays * a.tpr;
     MN_CHECK_ARG(n_wtiles < (1LL << 30), "too many points for one launch: %lld rays x %d samples", (long long)n_rays, S);
     a.n_rays = (unsigned)n_rays;
-    a.D = net->D;
-    a.skip_layer = (net->skip >= 0 && net->skip + 1 < net->D) ? net->skip + 1 : -1;
-    a.stream_bytes = L.walk_bytes; a.side_floats = L.side_floats;
-    a.o_bias_trunk = L.bias_trunk; a.o_bias_feat = L.bias_feat; a.o_bias_d = L.bias_d; a.o_head_b = L.head_b; a.o_wdir_t = L.wdir_t;
     if (points_per_wave == 64) return launch_half<4, 0, 4, F16>(a, n_wtiles, n_wtiles, st);
     // ... and a network deeper than the 64-point shape's LDS holds (HALF_64PT_MAX_D: half_layout.h) runs every launch at 32 points per wave
     if (points_per_wave == 32 || net->D > HALF_64PT_MAX_D) return launch_half<2, 0, 4, F16>(a, n_wtiles, n_wtiles, st);

@@ -765,7 +765,6 @@ __global__ __launch_bounds__(256) void pack_apply_kernel(const int32_t* __restri
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int num_cus_t() { return device_cus(); }
 
 static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // Slack behind the operands whose rows are narrower than 1 KB.  The first weight-gradient kernels ran their load pipelines past the
@@ -822,7 +821,7 @@ static int run_wgrad_batch(const WideProduct* pr, int n, long long P, float* par
         const int total = q.M * q.N + (q.bias ? q.M : 0);
         if (total > max_total) max_total = total;
     }
-    int slices = num_cus_t() / n;                              // one workgroup per CU owns all registers
+    int slices = device_cus() / n;                              // one workgroup per CU owns all registers
     const long long all_groups = (P + 11) / 12;                // groups of 2 x U points, dealt round robin to the slices
     if (slices > all_groups) slices = (int)all_groups;
     if (slices < 1) slices = 1;
@@ -857,7 +856,7 @@ static int run_wgrad(const float* dlt, int ldd, int M, const float* x, int ldx, 
     const int WQ = a.Mw > 128 ? 2 : 1, NN = a.Nn > 32 ? 2 : 1;
     const int Wp = 128 * WQ, Np = 32 * NN;
     const size_t per_slice = (size_t)Wp * Np + Wp + Np;
-    long long wslices = 4LL * num_cus_t();                 // one point slice per wave, one partial per workgroup
+    long long wslices = 4LL * device_cus();                 // one point slice per wave, one partial per workgroup
     long long pps = (P + wslices - 1) / wslices;
     pps = (pps + 23) / 24 * 24;                          // whole load groups for U = 4 and U = 6
     wslices = (P + pps - 1) / pps;
@@ -940,7 +939,7 @@ static int launch_dgrad(const DgradArgs& a, hipStream_t st) {
     static LdsOptIn opt_in = {};
     if (int rc = ensure_lds_opt_in(opt_in, (const void*)kern)) return rc;
     const long long n_wg = (a.n_wtiles + 3) / 4;
-    const int grid = (int)(n_wg < (long long)num_cus_t() ? n_wg : (long long)num_cus_t());
+    const int grid = persistent_grid(n_wg);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
     MN_LAUNCH_CHECK("mlp_dgrad_kernel");
     return MI_NERF_OK;

@@ -150,9 +150,9 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ ra
 #pragma unroll
             for (int c = 0; c < 3; ++c) {                                   // PositionalEncoding.py:20-24
                 const float y = b[c] * (float)(1 << k);
-                const bool fast = __builtin_fabsf(y) < SINCOS_FAST_LIMIT;
-                row[3 + 6 * k + c] = fast ? sin_cos_fast(y, 0) : sin_cos_slow(y, 0);
-                row[3 + 6 * k + 3 + c] = fast ? sin_cos_fast(y, 1) : sin_cos_slow(y, 1);
+                const bool fast = __builtin_fabsf(y) < SINCOS_FAST_LIMIT;    // per ARGUMENT here (the fused kernels branch once per point)
+                row[3 + 6 * k + c] = sin_cos_any(y, fast, 0);
+                row[3 + 6 * k + 3 + c] = sin_cos_any(y, fast, 1);
             }
         }
     }
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void posenc_kernel(const float* __restrict__ x
     if (ch >= 3) {
         const int k = (ch - 3) / 6, is_cos = ((ch - 3) % 6) >= 3;
         const float y = base * (float)(1 << k);
-        v = (__builtin_fabsf(y) < SINCOS_FAST_LIMIT) ? sin_cos_fast(y, is_cos) : sin_cos_slow(y, is_cos);
+        v = sin_cos_any(y, __builtin_fabsf(y) < SINCOS_FAST_LIMIT, is_cos);
     }
     out[idx] = v;
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include <type_traits>
 #include "half_layout.h"
+#include "walk_plan.h"
 
 namespace minerf {
 
