@@ -1,0 +1,134 @@
+/*
+ * mi_nerf_vox.h -- C ABI of libmi_nerf_vox.so: a trained NeRF baked into a radiance grid, and frames rendered from the grid alone, on the
+ * MI355X (gfx950).
+ *
+ * A library of its own BESIDE the path: include/mi_nerf.h and the other side headers stay what they are, nothing here is declared there,
+ * and libmi_nerf_vox.so exports no symbol of the other libraries and links against none of them.  Same conventions: plain C99, raw device
+ * pointers, the caller allocates everything, int status (0 = ok), hipStream_t passed as void*, every argument checked before any HIP call,
+ * error text through mi_vox_last_error().  No entry synchronises with the host, copies, allocates, or uses an atomic.
+ * All arithmetic below is fp32, every operation rounded once (no contraction), evaluated as it is written.
+ *
+ * THE LATTICE is the one of include/mi_nerf_mesh.h: res_i cells and P_i = res_i + 1 points per axis, 1 <= res_i <= MI_VOX_MAX_RES,
+ *     step_i = (hi_i - lo_i) / (float)res_i,   x_i(j) = lo_i + (float)j_i * step_i,   flat(j) = (j_z * P_y + j_y) * P_x + j_x,
+ * so the density lattice of that header, after a ReLU, is this grid's sigma plane.  inv_i = (float)res_i / (hi_i - lo_i).
+ *
+ * THE GRID.
+ *   sigma   float [P_z, P_y, P_x], finite and >= 0.
+ *   coef    float [P_z, P_y, P_x, R]: B = 1, 4 or 9 real spherical-harmonic functions (degree 0, 1, 2) per colour channel; coefficient b of
+ *           channel c at 3 b + c; the record padded with zeros to R = mi_vox_record_floats(B) = 4 / 16 / 32 floats, so that a record is
+ *           one aligned piece of 16 / 64 / 128 bytes.  The padding is written as zero and never read into a result.
+ *   skip    uint8 [ceil(res_z / 8), ceil(res_y / 8), ceil(res_x / 8)], one byte per block of 8^3 cells: 0 iff sigma == 0 at every lattice
+ *           point of the block's cells EXTENDED BY ONE CELL on every side (clipped to the lattice), i.e. at the points
+ *           max(8 b_i - 1, 0) .. min(min(8 b_i + 8, res_i) + 1, res_i) per axis; 1 otherwise.
+ *   The basis at a unit vector (x, y, z):
+ *       Y_0 = 0.28209479
+ *       Y_1 = -0.48860251 y      Y_2 = 0.48860251 z      Y_3 = -0.48860251 x
+ *       Y_4 = 1.0925484 (x y)    Y_5 = -1.0925484 (y z)  Y_6 = 0.31539157 (((2 z) z - x x) - y y)
+ *       Y_7 = -1.0925484 (x z)   Y_8 = 0.54627422 (x x - y y)
+ *
+ * THE RENDER RULE (mi_vox_render), per ray (o, d) of rays [n, 6]:
+ *   1. Slab.    L = sqrtf((d_x d_x + d_y d_y) + d_z d_z).  entry = -inf, exit = +inf; per axis in the order x, y, z: when d_i != 0,
+ *               ta = (lo_i - o_i) / d_i, tb = (hi_i - o_i) / d_i, entry = fmaxf(entry, fminf(ta, tb)), exit = fminf(exit, fmaxf(ta, tb));
+ *               when d_i == 0 the axis bounds nothing if lo_i <= o_i <= hi_i and makes the ray a miss otherwise.
+ *               t0 = fmaxf(t_near, entry), t1 = fminf(t_far, exit).  A ray with a non-finite component, L == 0 or not t1 > t0 is a MISS:
+ *               rgb = bg, acc = depth = disp = 0, visited = 0.
+ *   2. Intervals.  dt = step / L.  For k = 0, 1, ... while a_k < t1 and k < mi_vox_max_steps(grid, step):
+ *               a_k = t0 + (float)k * dt,  b_k = fminf(t0 + (float)(k + 1) * dt, t1),  m_k = 0.5f * (a_k + b_k),
+ *               delta_k = (b_k - a_k) * L.
+ *               The last interval is truncated at t1, not dropped and not overshot: the result is continuous in the ray.
+ *   3. Sample.  p_i = o_i + m_k * d_i;  g_i = (p_i - lo_i) * inv_i;  c_i = min(max((int)floorf(g_i), 0), res_i - 1);
+ *               f_i = fminf(fmaxf(g_i - (float)c_i, 0), 1).  Corner e = 0..7 is the lattice point c + (e & 1, (e >> 1) & 1, e >> 2) with
+ *               weight w_e = (wx wy) wz, w = f_i on the far side of axis i and 1 - f_i on the near side.  Interpolation of a quantity q:
+ *               v_e = w_e q_e, summed in pairs: x neighbours first, then y, then z:
+ *               ((v_0 + v_1) + (v_2 + v_3)) + ((v_4 + v_5) + (v_6 + v_7)).
+ *               sigma_s = the interpolation of sigma;  alpha_k = 1 - expf(-(sigma_s * delta_k)).
+ *               Only when sigma_s > 0: with u = d / L and q_e[c] = sum over b of coef_e[3 b + c] * Y_b(u), in increasing b from
+ *               coef_e[c] * Y_0, colour[c] = fminf(fmaxf(interpolation of q[c], 0), 1).  (Interpolation and the sum over b commute: this
+ *               is the basis applied to the interpolated coefficients, evaluated corner by corner.)
+ *   4. Compositing.  T = 1, sums 0.  w = T alpha_k;  rgb += w colour (skipped when sigma_s == 0);  acc += w;  depth += w m_k;
+ *               T = T (1 - alpha_k).  Marching stops after a sample that leaves T < T_min (T_min = 0 never stops).  Then
+ *               rgb += (1 - acc) bg, and disp as the path forms it from depth and acc: q = depth / acc, 1 / fmaxf(1e-10, q) with a NaN
+ *               q kept, NaN -> 0, capped at 5.
+ *               Unlike the path's compositing there is no 1e-10 inside the transmittance product and no 1e10 last interval: density at
+ *               the far clip does not become opaque.
+ *   5. Skipping.  With use_skip, a sample whose cell's block byte is 0 is not fetched: its eight sigma values are 0, so it adds exactly
+ *               nothing.  The march may then jump ahead to a later k, never past a sample whose cell lies outside that block extended by
+ *               one cell; positions are functions of the integer k alone, so rgb, disp, acc and depth are BIT-IDENTICAL with use_skip
+ *               0 and 1.  visited counts the samples whose sigma was fetched; it is the only output that differs.  A ray whose fp32
+ *               position error could reach an eighth of a cell (a far origin) never jumps.
+ *
+ * THE PROJECTION (mi_vox_project).  raw [M, D, 4] is a network's answer at M lattice points for D directions, proj [B, D] a matrix:
+ *     sigma[index[m]] = fmaxf(raw[m, 0, 3], 0)                                    (a NaN becomes 0)
+ *     coef[index[m], 3 b + c] = sum over j of proj[b, j] * s(raw[m, j, c]),  s(x) = 1 / (1 + expf(-x)),  in increasing j from 0;
+ * the rest of the record is written as zero.  One thread writes one record; an index outside [0, P_x P_y P_z) is ignored; indices are
+ * distinct.
+ */
+#ifndef MI_NERF_VOX_H
+#define MI_NERF_VOX_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MI_VOX_ABI_VERSION 1
+
+/* status codes (the values of mi_nerf.h) */
+#define MI_VOX_OK 0
+#define MI_VOX_EINVAL 1   /* bad argument / unsupported shape */
+#define MI_VOX_EHIP 2     /* HIP runtime error */
+
+#define MI_VOX_MAX_RES 512        /* largest res[i] */
+#define MI_VOX_BLOCK 8            /* cells per axis of one skip block */
+#define MI_VOX_MAX_DIRS 256       /* largest D of mi_vox_project */
+#define MI_VOX_MAX_STEPS 65536    /* largest mi_vox_max_steps that mi_vox_render takes */
+
+int mi_vox_abi_version(void);
+/* Thread-local text of the last error on this thread ("" if none). */
+const char* mi_vox_last_error(void);
+
+/* Axis-aligned box cut into res[0] x res[1] x res[2] cells (x, y, z).  lo_i < hi_i, both finite, with a finite fp32 step > 0. */
+typedef struct mi_vox_grid {
+    float lo[3];
+    float hi[3];
+    int32_t res[3];
+} mi_vox_grid;
+
+/* What a render reads beside the grid and the rays.  step > 0 is the world length of an interval; t_near < t_far, not NaN (they may be
+ * infinite); 0 <= T_min < 1; bg finite; use_skip 0 or 1. */
+typedef struct mi_vox_render_cfg {
+    float step;
+    float t_near, t_far;
+    float T_min;
+    float bg[3];
+    int32_t use_skip;
+} mi_vox_render_cfg;
+
+/* The two sizes a caller needs: floats per record (4 / 16 / 32 for B = 1 / 4 / 9, 0 for any other B) and bytes of the skip plane
+ * (0 + error text if the grid is refused). */
+int mi_vox_record_floats(int B);
+size_t mi_vox_skip_bytes(const mi_vox_grid* grid);
+/* The bound on the samples of one ray: ceil(|hi - lo| / step) + 1, |hi - lo| the box's diagonal, formed in double.  0 + error text if
+ * the grid is refused or step is not a positive finite number. */
+int64_t mi_vox_max_steps(const mi_vox_grid* grid, float step);
+
+/* THE PROJECTION.  B <= D <= MI_VOX_MAX_DIRS; raw_dev and coef_dev 16-byte aligned, index_dev (int64) 8-byte aligned; M >= 0 (0: nothing
+ * is launched and the arrays are not looked at).  sigma_dev may be NULL: the density is then not written (a caller that filled the sigma plane from a density lattice). */
+int mi_vox_project(const mi_vox_grid* grid, int B, int D, const float* raw_dev, const float* proj_dev, const int64_t* index_dev, int64_t M,
+                   float* sigma_dev, float* coef_dev, void* stream);
+
+/* skip from sigma by the rule of THE GRID. */
+int mi_vox_build_skip(const mi_vox_grid* grid, const float* sigma_dev, uint8_t* skip_dev, void* stream);
+
+/* THE RENDER RULE.  rays [n, 6], rgb [n, 3]; disp, acc, depth [n] float and visited [n] uint32 may each be NULL; skip_dev may be NULL when
+ * use_skip is 0; coef_dev 16-byte aligned; n >= 0 (0: nothing is launched and the arrays are not looked at).  Refused when mi_vox_max_steps exceeds MI_VOX_MAX_STEPS. */
+int mi_vox_render(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev, const float* rays_dev,
+                  int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev,
+                  uint32_t* visited_dev, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MI_NERF_VOX_H */

@@ -1,0 +1,44 @@
+"""ctypes binding of libmi_nerf_vox.so (include/mi_nerf_vox.h): the radiance grid -- projection, empty-space plane, renderer.
+
+A table of its own: ``_lib.SIGNATURES`` mirrors include/mi_nerf.h and does not know these entries.  The library stands alone (it links
+against no other library of the package).  Like the rest of the package there is NO fallback: a missing library or a failed call raises
+``MiNerfError``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+from ._lib import loader
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libmi_nerf_vox.so")
+ABI_VERSION = 1
+MAX_RES, BLOCK, MAX_DIRS, MAX_STEPS = 512, 8, 256, 65536          # MI_VOX_MAX_RES / _BLOCK / _MAX_DIRS / _MAX_STEPS
+
+
+class Grid(C.Structure):              # mi_vox_grid
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("res", C.c_int32 * 3)]
+
+
+class RenderCfg(C.Structure):         # mi_vox_render_cfg
+    _fields_ = [("step", C.c_float), ("t_near", C.c_float), ("t_far", C.c_float), ("T_min", C.c_float), ("bg", C.c_float * 3),
+                ("use_skip", C.c_int32)]
+
+
+_P, _I, _I64, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+_GRIDP, _CFGP = C.POINTER(Grid), C.POINTER(RenderCfg)
+
+# name -> (restype, argtypes); mirrors include/mi_nerf_vox.h declaration by declaration
+SIGNATURES = {
+    "mi_vox_abi_version": (_I, []),
+    "mi_vox_last_error": (C.c_char_p, []),
+    "mi_vox_record_floats": (_I, [_I]),
+    "mi_vox_skip_bytes": (_SZ, [_GRIDP]),
+    "mi_vox_max_steps": (_I64, [_GRIDP, _F]),
+    "mi_vox_project": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _P]),
+    "mi_vox_build_skip": (_I, [_GRIDP, _P, _P, _P]),
+    "mi_vox_render": (_I, [_GRIDP, _I, _P, _P, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P]),
+}
+
+lib, check, last_error = loader(globals(), "mi_vox")

@@ -1,0 +1,306 @@
+"""A trained NeRF baked into a radiance grid, and frames rendered from the grid alone (include/mi_nerf_vox.h, libmi_nerf_vox.so).
+
+    grid = baked.RadianceGrid(-1.2, 1.2, 256, B=9).bake(model)          # density + 9 spherical-harmonic colour coefficients per lattice point
+    rgb, disp, acc, depth = grid.render(rays)                            # marching through the table: no network
+    opts.baked = grid                                                    # harness.test / harness.render then render every pose from it
+
+The lattice is the one of mesh.density_lattice (include/mi_nerf_mesh.h): the grid's sigma plane is that lattice after a ReLU.  Colour is
+the network's post-sigmoid colour at the lattice point, seen from D fixed directions, projected by least squares onto B real spherical
+harmonics (``projection_matrix``); the renderer interpolates trilinearly and composites front to back by THE RENDER RULE of the header.
+Baking is not the hot path (torch ops build the active-point list); rendering is one launch.  There is no fallback: a missing library or a
+failed call raises ``MiNerfError``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Callable, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _vox, ops
+from ._lib import MiNerfError, as_f32_dev, dev_ptr, stream_ptr
+from ._vox import Grid, RenderCfg
+
+BASES = (1, 4, 9)
+# lattice points handed to the field per slab by bake_field (D one-sample rays each)
+SLAB_POINTS = 1 << 16
+# the header's constants
+_C0, _C1, _C2, _C20, _C22 = 0.28209479, 0.48860251, 1.0925484, 0.31539157, 0.54627422
+
+
+def _triple(v, cast) -> Tuple:
+    if isinstance(v, (int, float)):
+        return (cast(v),) * 3
+    t = tuple(cast(x) for x in v)
+    if len(t) != 3:
+        raise MiNerfError(f"expected a scalar or three values (x, y, z), got {v!r}")
+    return t
+
+
+def _check_basis(B: int) -> int:
+    if B not in BASES:
+        raise MiNerfError(f"B={B!r}: 1, 4 or 9 basis functions (degree 0, 1, 2)")
+    return int(B)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the basis and the projection: host, float64
+# ---------------------------------------------------------------------------------------------------
+def sh_basis(dirs, B: int) -> np.ndarray:
+    """Y [n, B] (float64) of the header's real spherical harmonics at unit vectors dirs [n, 3]."""
+    B = _check_basis(B)
+    u = np.asarray(dirs, np.float64).reshape(-1, 3)
+    x, y, z = u[:, 0], u[:, 1], u[:, 2]
+    Y = [np.full_like(x, _C0), -_C1 * y, _C1 * z, -_C1 * x, _C2 * (x * y), -_C2 * (y * z), _C20 * (((2.0 * z) * z - x * x) - y * y), -_C2 * (x * z),
+         _C22 * (x * x - y * y)]
+    return np.stack(Y[:B], 1)
+
+
+def fibonacci_directions(D: int) -> np.ndarray:
+    """D unit vectors [D, 3] (float64) on the spherical Fibonacci spiral: near-uniform for any D, no randomness."""
+    if D < 1:
+        raise MiNerfError(f"D={D}: at least one direction")
+    i = np.arange(D, dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / D
+    phi = 2.0 * math.pi * i / ((1.0 + math.sqrt(5.0)) / 2.0)
+    r = np.sqrt(1.0 - z * z)
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
+
+
+def projection_matrix(D: int = 32, B: int = 9) -> np.ndarray:
+    """pinv(Y) [B, D] (float64) of the basis at fibonacci_directions(D): the least-squares coefficients of D colour samples.  For
+    D = 9 .. 64 the condition number of Y runs from 2.1 to 1.01 and pinv(Y) Y = I to 4e-15."""
+    B = _check_basis(B)
+    if not B <= D <= _vox.MAX_DIRS:
+        raise MiNerfError(f"D={D}: B={B} .. {_vox.MAX_DIRS} directions")
+    return np.linalg.pinv(sh_basis(fibonacci_directions(D), B))
+
+
+# ---------------------------------------------------------------------------------------------------
+# the grid
+# ---------------------------------------------------------------------------------------------------
+class RadianceGrid:
+    """``sigma`` float [P_z, P_y, P_x], ``coef`` float [P_z, P_y, P_x, R], ``skip`` uint8 [B_z, B_y, B_x] on ``device`` (THE GRID of the
+    header); None until ``allocate`` / ``bake`` / ``load``."""
+
+    def __init__(self, lo, hi, res, B: int = 9):
+        # the box is fp32, as the library reads it: what save() writes is what load() reads
+        self.lo, self.hi, self.res = _triple(lo, lambda v: float(np.float32(v))), _triple(hi, lambda v: float(np.float32(v))), _triple(res, int)
+        self.B = _check_basis(B)
+        self.sigma: Optional[torch.Tensor] = None
+        self.coef: Optional[torch.Tensor] = None
+        self.skip: Optional[torch.Tensor] = None
+        g = self.c_grid()
+        if int(_vox.lib().mi_vox_skip_bytes(C.byref(g))) == 0:
+            raise MiNerfError(f"the grid is refused: {_vox.last_error()}")
+
+    # ---- shape ---------------------------------------------------------------------------------------
+    def c_grid(self) -> Grid:
+        return Grid((C.c_float * 3)(*self.lo), (C.c_float * 3)(*self.hi), (C.c_int32 * 3)(*self.res))
+
+    @property
+    def points(self) -> Tuple[int, int, int]:
+        """(P_z, P_y, P_x)"""
+        return tuple(r + 1 for r in reversed(self.res))
+
+    @property
+    def record_floats(self) -> int:
+        return int(_vox.lib().mi_vox_record_floats(self.B))
+
+    @property
+    def skip_shape(self) -> Tuple[int, int, int]:
+        return tuple(-(-r // _vox.BLOCK) for r in reversed(self.res))
+
+    @property
+    def device(self):
+        return None if self.sigma is None else self.sigma.device
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the three arrays (whether or not they are allocated)."""
+        n = self.points[0] * self.points[1] * self.points[2]
+        return 4 * n * (1 + self.record_floats) + self.skip_shape[0] * self.skip_shape[1] * self.skip_shape[2]
+
+    def cell_edge(self) -> float:
+        """The smallest cell edge."""
+        return min((np.float32(self.hi[i]) - np.float32(self.lo[i])) / np.float32(self.res[i]) for i in range(3)).item()
+
+    def allocate(self, device) -> "RadianceGrid":
+        """Zero arrays on ``device``: an empty scene."""
+        device = torch.device(device)
+        self.sigma = torch.zeros(self.points, dtype=torch.float32, device=device)
+        self.coef = torch.zeros(*self.points, self.record_floats, dtype=torch.float32, device=device)
+        self.skip = torch.zeros(self.skip_shape, dtype=torch.uint8, device=device)
+        return self
+
+    def to(self, device) -> "RadianceGrid":
+        self._need()
+        self.sigma, self.coef, self.skip = (t.to(device) for t in (self.sigma, self.coef, self.skip))
+        return self
+
+    def _need(self) -> None:
+        if self.sigma is None or self.coef is None or self.skip is None:
+            raise MiNerfError("the grid holds nothing yet: bake(), bake_field(), allocate() or load() first")
+
+    # ---- the library's entries -----------------------------------------------------------------------
+    def project(self, raw: torch.Tensor, proj: torch.Tensor, index: torch.Tensor, write_sigma: bool = True) -> "RadianceGrid":
+        """mi_vox_project: raw [M, D, 4], proj [B, D], index [M] (int64 flat lattice indices, distinct) -> records (and sigma)."""
+        self._need()
+        dev = self.sigma.device
+        if raw.dim() != 3 or raw.shape[2] != 4 or tuple(proj.shape) != (self.B, raw.shape[1]) or tuple(index.shape) != (raw.shape[0],):
+            raise MiNerfError(f"raw [M,D,4], proj [{self.B},D] and index [M] expected, got {tuple(raw.shape)} / {tuple(proj.shape)} / {tuple(index.shape)}")
+        g = self.c_grid()
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_project(C.byref(g), self.B, int(raw.shape[1]), dev_ptr(raw, "raw", torch.float32, 16), dev_ptr(proj, "proj"),
+                                                 dev_ptr(index, "index", torch.int64, 8), int(raw.shape[0]),
+                                                 dev_ptr(self.sigma, "sigma") if write_sigma else None, dev_ptr(self.coef, "coef", torch.float32, 16),
+                                                 stream_ptr(dev)), "mi_vox_project")
+        return self
+
+    def build_skip(self) -> "RadianceGrid":
+        """mi_vox_build_skip: the empty-space plane from sigma."""
+        self._need()
+        dev = self.sigma.device
+        g = self.c_grid()
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_build_skip(C.byref(g), dev_ptr(self.sigma, "sigma"), dev_ptr(self.skip, "skip", torch.uint8, 1), stream_ptr(dev)),
+                       "mi_vox_build_skip")
+        return self
+
+    def render(self, rays: torch.Tensor, step: Optional[float] = None, near: float = 0.0, far: float = math.inf, T_min: float = 0.0,
+               bg=(1.0, 1.0, 1.0), skip: bool = True, want_all: bool = True, visited: bool = False):
+        """(rgb [n,3], disp [n], acc [n], depth [n]) of rays [n,6] by THE RENDER RULE (mi_vox_render); ``want_all=False``: rgb alone, the
+        other outputs are not written; ``visited=True`` appends the per-ray count of fetched samples (int32).  ``step=None``: half the
+        smallest cell edge.  The default background is white, as the path's compositing always uses."""
+        self._need()
+        dev = self.sigma.device
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+            raise MiNerfError(f"rays [n,6] expected, got {tuple(rays.shape) if isinstance(rays, torch.Tensor) else type(rays).__name__}")
+        if rays.device != dev:
+            raise MiNerfError(f"rays live on {rays.device}, the grid on {dev}")
+        n = rays.shape[0]
+        cfg = RenderCfg(float(0.5 * self.cell_edge() if step is None else step), float(near), float(far), float(T_min),
+                        (C.c_float * 3)(*(float(v) for v in bg)), int(bool(skip)))
+        rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        disp, acc, depth = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3)) if want_all else (None, None, None)
+        seen = torch.empty(n, dtype=torch.int32, device=dev) if visited else None
+        g = self.c_grid()
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_render(C.byref(g), self.B, dev_ptr(self.sigma, "sigma"), dev_ptr(self.coef, "coef", torch.float32, 16),
+                                                dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
+                                                dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
+                                                dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render")
+        out = (rgb, disp, acc, depth) if want_all else (rgb,)
+        out = out + (seen,) if visited else out
+        return out if len(out) > 1 else out[0]
+
+    # ---- baking --------------------------------------------------------------------------------------
+    def bake(self, model_or_packed, network: str = "fine", D: int = 32, sigma_min: float = 0.0, precision=None,
+             slab_points: int = SLAB_POINTS, shell: str = "field") -> "RadianceGrid":
+        """Bake one network: sigma from mesh.density_lattice (values <= sigma_min become 0), colour from one-sample rays through
+        ops.mlp_rays (fp32) at every point within one lattice step of density.  See ``bake_field``."""
+        from . import mesh
+        from .weights import packed_for
+        packed = packed_for(model_or_packed)                                # packed once for the lattice and the colour rays
+        dev, net, blob = mesh._blob(packed, network, mesh.check_precision(None))
+        density = mesh.density_lattice(packed, self.lo, self.hi, self.res, network=network, precision=precision)
+        return bake_field(lambda rays, z: ops.mlp_rays(net, blob, rays, z), self.lo, self.hi, self.res, B=self.B, D=D, sigma_min=sigma_min,
+                          slab_points=slab_points, device=dev, density=density, grid=self, shell=shell)
+
+    # ---- persistence ---------------------------------------------------------------------------------
+    def save(self, path: str) -> None:
+        """npz: lo, hi, res, B and the three arrays."""
+        self._need()
+        np.savez_compressed(path, lo=np.asarray(self.lo, np.float32), hi=np.asarray(self.hi, np.float32), res=np.asarray(self.res, np.int32),
+                            B=np.asarray(self.B, np.int32), sigma=self.sigma.cpu().numpy(), coef=self.coef.cpu().numpy(), skip=self.skip.cpu().numpy())
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "RadianceGrid":
+        with np.load(path, allow_pickle=False) as f:
+            grid = cls(f["lo"].tolist(), f["hi"].tolist(), f["res"].tolist(), int(f["B"]))
+            sigma, coef, skip = (torch.from_numpy(np.ascontiguousarray(f[k])) for k in ("sigma", "coef", "skip"))
+        if tuple(sigma.shape) != grid.points or tuple(coef.shape) != grid.points + (grid.record_floats,) or tuple(skip.shape) != grid.skip_shape:
+            raise MiNerfError(f"{path}: the arrays do not fit the grid ({tuple(sigma.shape)}, {tuple(coef.shape)}, {tuple(skip.shape)})")
+        grid.sigma, grid.coef, grid.skip = sigma.float(), coef.float(), skip.to(torch.uint8)
+        return grid.to(device) if device is not None else grid
+
+
+def fill_shell(grid: RadianceGrid) -> RadianceGrid:
+    """Every point with sigma == 0 that has a neighbour (of the 26) with sigma > 0 takes the mean of those neighbours' records (torch ops:
+    baking is not the hot path).  Points with density and points without such a neighbour keep their records."""
+    grid._need()
+    dense = (grid.sigma > 0).to(torch.float32)[None, None]
+    count = torch.nn.functional.avg_pool3d(dense, 3, stride=1, padding=1)[0, 0]              # (dense neighbours) / 27, zero padding
+    shell = (grid.sigma == 0) & (count > 0)
+    for c in range(3 * grid.B):                                                             # plane by plane: no second copy of the table
+        plane = grid.coef[..., c]
+        mean = torch.nn.functional.avg_pool3d((plane * dense[0, 0])[None, None], 3, stride=1, padding=1)[0, 0] / count.clamp_min(1e-9)
+        grid.coef[..., c] = torch.where(shell, mean, plane)
+    return grid
+
+
+def lattice_positions(lo, hi, res, index: torch.Tensor) -> torch.Tensor:
+    """x [M, 3] (fp32, on index's device) of the lattice points with flat indices ``index``: x_i(j) = lo_i + (float)j_i * step_i, product
+    and sum rounded once each, step_i formed on the host in fp32 -- the rule of the header."""
+    f32 = np.float32
+    lo, hi, res = _triple(lo, float), _triple(hi, float), _triple(res, int)
+    Px, Py = res[0] + 1, res[1] + 1
+    j = (index % Px, (index // Px) % Py, index // (Px * Py))
+    cols = []
+    for i in range(3):
+        step = float((f32(hi[i]) - f32(lo[i])) / f32(res[i]))
+        cols.append(j[i].to(torch.float32) * step + float(f32(lo[i])))
+    return torch.stack(cols, -1)
+
+
+def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi, res, B: int = 9, D: int = 32, sigma_min: float = 0.0,
+               slab_points: int = SLAB_POINTS, device="cuda:0", density: Optional[torch.Tensor] = None,
+               grid: Optional[RadianceGrid] = None, shell: str = "field") -> RadianceGrid:
+    """Bake any field ``fn(rays [n,6], z [n,S]) -> raw [n,S,4]`` (a network's fused entry, ``SolidScene.field``) into a RadianceGrid.
+      1. sigma: ``density`` [P_z, P_y, P_x] (raw, before the ReLU) when given, else fn over the lattice rows of mesh.lattice_rows; values
+         <= sigma_min (and NaN) become 0.
+      2. the active points: those within one lattice step (all 26 neighbours) of a point with sigma > 0.
+      3. slab by slab, D one-sample rays (x, omega_j) with depth 0 per active point go through fn; mi_vox_project writes the records.
+         Inactive points keep zero records.
+      4. mi_vox_build_skip.
+    ``shell``: what the active points WITHOUT density hold (the one-step shell around the density, which every sample that straddles a
+    surface interpolates with).  "field" (default): the field's own colour there, as at every active point -- right for a network, whose
+    colour branch is continuous across its surfaces.  "neighbours": the mean of the records of the point's neighbours (of the 26) that
+    have density -- for a field whose colour outside its solids means nothing (``SolidScene.field``: frames come out washed with that
+    colour otherwise, docs/design/22_radiance_grid.md)."""
+    from . import mesh
+    grid = RadianceGrid(lo, hi, res, B) if grid is None else grid
+    dev = torch.device(device)
+    if slab_points < 1:
+        raise MiNerfError(f"slab_points={slab_points}: at least one point per slab")
+    if shell not in ("field", "neighbours"):
+        raise MiNerfError(f"shell={shell!r}: 'field' or 'neighbours'")
+    proj = torch.from_numpy(projection_matrix(D, grid.B).astype(np.float32)).to(dev).contiguous()
+    omega = torch.from_numpy(fibonacci_directions(D).astype(np.float32)).to(dev)
+    Pz, Py, Px = grid.points
+    with torch.no_grad():
+        if density is None:
+            rows, z = mesh.lattice_rows(grid.lo, grid.hi, grid.res, dev)
+            per = max(1, slab_points // Px)
+            density = torch.cat([fn(rows[a:a + per].contiguous(), z[a:a + per].contiguous())[..., 3] for a in range(0, rows.shape[0], per)]).reshape(Pz, Py, Px)
+        density = as_f32_dev(density, dev)
+        if tuple(density.shape) != grid.points:
+            raise MiNerfError(f"density must be {grid.points}, got {tuple(density.shape)}")
+        sigma = torch.where(density > float(sigma_min), density, torch.zeros_like(density)).clamp_(min=0.0, max=torch.finfo(torch.float32).max)
+        grid.allocate(dev)
+        grid.sigma.copy_(sigma)
+        active = torch.nn.functional.max_pool3d((sigma > 0).to(torch.float32)[None, None], 3, stride=1, padding=1)[0, 0] > 0
+        index = torch.nonzero(active.reshape(-1)).reshape(-1)
+        for a in range(0, index.numel(), slab_points):
+            idx = index[a:a + slab_points].contiguous()
+            x = lattice_positions(grid.lo, grid.hi, grid.res, idx)
+            m = idx.numel()
+            rays = torch.cat([x[:, None, :].expand(m, D, 3), omega[None].expand(m, D, 3)], -1).reshape(m * D, 6).contiguous()
+            raw = fn(rays, torch.zeros(m * D, 1, dtype=torch.float32, device=dev)).reshape(m, D, 4)
+            grid.project(raw, proj, idx, write_sigma=False)
+        if shell == "neighbours":
+            fill_shell(grid)
+        grid.build_skip()
+    return grid

@@ -1,0 +1,425 @@
+// vox.hip -- libmi_nerf_vox.so (include/mi_nerf_vox.h): a radiance grid (density plus spherical-harmonic colour per lattice point), the
+// projection of a network's answers onto it, its empty-space plane, and the renderer that marches rays through it with no network.  A
+// library of its own: it shares abi_error.h with the others at compile time and nothing at link time.
+//
+//   project_kernel<B>      one thread per lattice point of the index list: fmaxf of the density, 3 B dot products of proj rows with the
+//                          sigmoid of the D colours (increasing j), one record written with 16-byte stores, padding as zero.
+//   skip_kernel            one wave per block of 8^3 cells: the lanes sweep the points of the block extended by one cell, a ballot decides
+//                          the byte, lane 0 stores it.
+//   render_kernel<B>       a GROUP OF 8 LANES PER RAY, 32 rays per workgroup.  Every lane of a group carries the same ray state (origin,
+//                          interval counter, transmittance, sums): all control flow is uniform within a group, so the eight lanes are
+//                          always active together.  Lane e owns corner e of the sample's cell: it reads that corner's sigma (4 bytes; the
+//                          eight lanes read 4 pairs of neighbours), and only when the group's sigma_s > 0 its record with 16-byte loads --
+//                          one aligned 16 / 64 / 128-byte piece per lane, neighbouring corners in x adjacent -- evaluates the basis on it
+//                          and scales by its trilinear weight.  The group adds with DPP row operations (x neighbours, y neighbours, the
+//                          other half-row): no LDS, no bpermute.  A wave instruction whose 64 lanes read 64 unrelated rows runs ~17x below
+//                          the rate of contiguous segments; here a wave's 64 lanes are 8 rays of neighbouring pixels in neighbouring cells.
+//                          The skip byte and the sigma plane are read before any coefficient: in a baked scene most samples end there.
+//
+// No atomic, no host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "../../include/mi_nerf_vox.h"
+#include "abi_error.h"
+
+namespace mivox {
+
+// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
+ABI_ERROR_STATE(static, MI_VOX_EHIP)
+#define VOX_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::mivox, MI_VOX_EINVAL, cond, __VA_ARGS__)
+#define VOX_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::mivox, name)
+
+constexpr int THREADS = 256;
+constexpr int GROUP = 8;                                 // lanes per ray: the corners of a cell
+constexpr int RAYS_PER_BLOCK = THREADS / GROUP;
+constexpr int BLK = MI_VOX_BLOCK;
+constexpr float EPS32 = 5.9604645e-8f;                   // 2^-24
+
+__host__ __device__ constexpr int record_floats(int B) { return B == 1 ? 4 : B == 4 ? 16 : B == 9 ? 32 : 0; }
+
+// the grid as the kernels see it
+struct Lattice {
+    float lo[3], hi[3], inv[3];
+    int res[3];
+    int P[3];                                            // points per axis
+    int nb[3];                                           // blocks per axis
+};
+
+// the basis of the header at a unit vector
+template <int B>
+__device__ __forceinline__ void sh_basis(float x, float y, float z, float (&Y)[B]) {
+    Y[0] = 0.28209479f;
+    if constexpr (B >= 4) {
+        Y[1] = -0.48860251f * y;
+        Y[2] = 0.48860251f * z;
+        Y[3] = -0.48860251f * x;
+    }
+    if constexpr (B >= 9) {
+        Y[4] = 1.0925484f * (x * y);
+        Y[5] = -1.0925484f * (y * z);
+        Y[6] = 0.31539157f * (((2.0f * z) * z - x * x) - y * y);
+        Y[7] = -1.0925484f * (x * z);
+        Y[8] = 0.54627422f * (x * x - y * y);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// mi_vox_project
+// ------------------------------------------------------------------------------------------------
+template <int B>
+__global__ __launch_bounds__(THREADS) void project_kernel(const float4* __restrict__ raw, const float* __restrict__ proj,
+                                                          const long long* __restrict__ index, long long M, int D, long long N,
+                                                          float* __restrict__ sigma, float4* __restrict__ coef) {
+    constexpr int R4 = record_floats(B) / 4;
+    const long long m = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (m >= M) return;
+    const long long at = index[m];
+    if (at < 0 || at >= N) return;
+    float acc[R4 * 4];
+#pragma unroll
+    for (int i = 0; i < R4 * 4; ++i) acc[i] = 0.0f;
+    const float4* row = raw + m * D;
+    float dens = 0.0f;
+    for (int j = 0; j < D; ++j) {
+        const float4 v = row[j];
+        if (j == 0) dens = v.w;
+        const float s0 = 1.0f / (1.0f + expf(-v.x)), s1 = 1.0f / (1.0f + expf(-v.y)), s2 = 1.0f / (1.0f + expf(-v.z));
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+            const float p = proj[b * D + j];
+            if (j == 0) {
+                acc[3 * b + 0] = p * s0; acc[3 * b + 1] = p * s1; acc[3 * b + 2] = p * s2;
+            } else {
+                acc[3 * b + 0] += p * s0; acc[3 * b + 1] += p * s1; acc[3 * b + 2] += p * s2;
+            }
+        }
+    }
+    if (sigma) sigma[at] = fmaxf(dens, 0.0f);                          // fmaxf returns the other operand for a NaN
+    float4* rec = coef + at * R4;
+#pragma unroll
+    for (int q = 0; q < R4; ++q) rec[q] = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// mi_vox_build_skip
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void skip_kernel(const Lattice g, const float* __restrict__ sigma, uint8_t* __restrict__ skip) {
+    const int blk = blockIdx.x;
+    const int bx = blk % g.nb[0], by = (blk / g.nb[0]) % g.nb[1], bz = blk / (g.nb[0] * g.nb[1]);
+    const int b[3] = {bx, by, bz};
+    int p0[3], np[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int c1 = min(BLK * b[i] + BLK, g.res[i]);
+        p0[i] = max(BLK * b[i] - 1, 0);
+        np[i] = min(c1 + 1, g.res[i]) - p0[i] + 1;
+    }
+    const int total = np[0] * np[1] * np[2];
+    bool any = false;
+    for (int t = threadIdx.x; t < total; t += 64) {
+        const int x = p0[0] + t % np[0], y = p0[1] + (t / np[0]) % np[1], z = p0[2] + t / (np[0] * np[1]);
+        any |= sigma[((long long)z * g.P[1] + y) * g.P[0] + x] != 0.0f;
+    }
+    const bool found = __ballot(any) != 0ull;
+    if (threadIdx.x == 0) skip[blk] = found ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mi_vox_render
+// ------------------------------------------------------------------------------------------------
+// the sum over a group's eight lanes, in the header's order: x neighbours, y neighbours, then the two halves.  Every lane ends with the
+// same bits (an addition commutes).  quad_perm [1,0,3,2] and [2,3,0,1] exchange within a quad; after them a quad's four lanes agree, so
+// the mirror of the half-row (lane i <-> 7 - i) hands each lane the other quad's sum.
+__device__ __forceinline__ float dpp_quad_x(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)); }
+__device__ __forceinline__ float dpp_quad_y(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)); }
+__device__ __forceinline__ float dpp_half_mirror(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)); }
+__device__ __forceinline__ float group_sum(float v) {
+    v = v + dpp_quad_x(v);
+    v = v + dpp_quad_y(v);
+    return v + dpp_half_mirror(v);
+}
+
+struct RenderArgs {
+    Lattice g;
+    const float* sigma;
+    const float4* coef;
+    const uint8_t* skip;
+    const float* rays;
+    long long n;
+    float step, t_near, t_far, T_min;
+    float bg[3];
+    int use_skip;
+    int max_steps;
+    float *rgb, *disp, *acc, *depth;
+    unsigned* visited;
+};
+
+template <int B>
+__global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
+    constexpr int R4 = record_floats(B) / 4;               // 16-byte pieces of a record
+    constexpr int V4 = (3 * B + 3) / 4;                    // the pieces that hold coefficients
+    const int e = threadIdx.x & (GROUP - 1);               // this lane's corner
+    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 3);
+    if (ray >= a.n) return;                                // a whole group leaves together
+    const Lattice& g = a.g;
+    const float* rp = a.rays + ray * 6;
+    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
+    const float L = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    bool miss = !(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(L)) || L == 0.0f;
+    float entry = -INFINITY, exit_ = INFINITY;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (d[i] != 0.0f) {
+            const float ta = (g.lo[i] - o[i]) / d[i], tb = (g.hi[i] - o[i]) / d[i];
+            entry = fmaxf(entry, fminf(ta, tb));
+            exit_ = fminf(exit_, fmaxf(ta, tb));
+        } else if (!(g.lo[i] <= o[i] && o[i] <= g.hi[i])) {
+            miss = true;
+        }
+    }
+    const float t0 = fmaxf(a.t_near, entry), t1 = fminf(a.t_far, exit_);
+    if (!(t1 > t0)) miss = true;
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, sd = 0.0f;
+    unsigned seen = 0;
+    if (!miss) {
+        const float dt = a.step / L;
+        const float ux = d[0] / L, uy = d[1] / L, uz = d[2] / L;
+        float Y[B];
+        sh_basis<B>(ux, uy, uz, Y);
+        // jumping over an empty block: allowed only where the fp32 position error stays below an eighth of a cell
+        const float tmax = fmaxf(fabsf(t0), fabsf(t1));
+        float gu[3], gv[3];
+        bool can_jump = a.use_skip != 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            gu[i] = (o[i] - g.lo[i]) * g.inv[i];
+            gv[i] = d[i] * g.inv[i];
+            const float err = 16.0f * EPS32 * (fabsf(o[i]) + tmax * fabsf(d[i]) + fabsf(g.lo[i]) + fabsf(g.hi[i])) * g.inv[i];
+            can_jump = can_jump && err <= 0.125f;
+        }
+        const int ex = e & 1, ey = (e >> 1) & 1, ez = e >> 2;
+        float T = 1.0f;
+        int k = 0;
+        while (k < a.max_steps) {
+            const float ak = t0 + (float)k * dt;
+            if (!(ak < t1)) break;
+            const float bk = fminf(t0 + (float)(k + 1) * dt, t1);
+            const float mk = 0.5f * (ak + bk);
+            int c[3];
+            float f[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float p = o[i] + mk * d[i];
+                const float gi = (p - g.lo[i]) * g.inv[i];
+                c[i] = min(max((int)floorf(gi), 0), g.res[i] - 1);
+                f[i] = fminf(fmaxf(gi - (float)c[i], 0.0f), 1.0f);
+            }
+            if (a.use_skip) {
+                const int bx = c[0] >> 3, by = c[1] >> 3, bz = c[2] >> 3;
+                if (a.skip[(bz * g.nb[1] + by) * g.nb[0] + bx] == 0) {
+                    int next = k + 1;
+                    if (can_jump) {
+                        // where the ray leaves the block extended by half a cell, in lattice units; the first sample that is evaluated
+                        // again starts a whole interval before that
+                        const int bb[3] = {bx, by, bz};
+                        float t_exit = INFINITY;
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            const float far_ = (float)min(BLK * bb[i] + BLK, g.res[i]) + 0.5f, near_ = (float)(BLK * bb[i]) - 0.5f;
+                            if (gv[i] > 0.0f) t_exit = fminf(t_exit, (far_ - gu[i]) / gv[i]);
+                            else if (gv[i] < 0.0f) t_exit = fminf(t_exit, (near_ - gu[i]) / gv[i]);
+                        }
+                        const float kf = floorf((t_exit - t0) / dt) - 1.0f;
+                        if (kf > (float)next) next = (int)fminf(kf, (float)a.max_steps);
+                    }
+                    k = next;
+                    continue;
+                }
+            }
+            // lane e: corner e
+            const long long at = ((long long)(c[2] + ez) * g.P[1] + (c[1] + ey)) * g.P[0] + (c[0] + ex);
+            const float wx = ex ? f[0] : 1.0f - f[0], wy = ey ? f[1] : 1.0f - f[1], wz = ez ? f[2] : 1.0f - f[2];
+            const float w = (wx * wy) * wz;
+            const float sigma_s = group_sum(w * a.sigma[at]);
+            ++seen;
+            const float delta = (bk - ak) * L;
+            const float alpha = 1.0f - expf(-(sigma_s * delta));
+            const float wt = T * alpha;
+            if (sigma_s > 0.0f) {
+                const float4* rec = a.coef + at * R4;
+                float kc[V4 * 4];
+#pragma unroll
+                for (int q = 0; q < V4; ++q) {
+                    const float4 v = rec[q];
+                    kc[4 * q] = v.x; kc[4 * q + 1] = v.y; kc[4 * q + 2] = v.z; kc[4 * q + 3] = v.w;
+                }
+                float col[3];
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    float q = kc[ch] * Y[0];
+#pragma unroll
+                    for (int b = 1; b < B; ++b) q += kc[3 * b + ch] * Y[b];
+                    col[ch] = fminf(fmaxf(group_sum(w * q), 0.0f), 1.0f);
+                }
+                sr += wt * col[0]; sg += wt * col[1]; sb += wt * col[2];
+            }
+            sw += wt;
+            sd += wt * mk;
+            T = T * (1.0f - alpha);
+            ++k;
+            if (T < a.T_min) break;
+        }
+    }
+    if (e == 0) {
+        const float rest = 1.0f - sw;
+        a.rgb[ray * 3 + 0] = sr + rest * a.bg[0];
+        a.rgb[ray * 3 + 1] = sg + rest * a.bg[1];
+        a.rgb[ray * 3 + 2] = sb + rest * a.bg[2];
+        if (a.disp) {
+            const float q = sd / sw;
+            const float m = (q != q) ? q : fmaxf(1e-10f, q);
+            float disp = 1.0f / m;
+            if (disp != disp) disp = 0.0f;
+            if (disp > 5.0f) disp = 5.0f;
+            a.disp[ray] = disp;
+        }
+        if (a.acc) a.acc[ray] = sw;
+        if (a.depth) a.depth[ray] = sd;
+        if (a.visited) a.visited[ray] = seen;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side: checks, launches
+// ------------------------------------------------------------------------------------------------
+static inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+static int check_grid(const char* who, const mi_vox_grid* grid, Lattice* out) {
+    VOX_CHECK_ARG(grid != nullptr, "%s: grid is NULL", who);
+    Lattice g{};
+    for (int i = 0; i < 3; ++i) {
+        const float lo = grid->lo[i], hi = grid->hi[i];
+        const int res = grid->res[i];
+        VOX_CHECK_ARG(res >= 1 && res <= MI_VOX_MAX_RES, "%s: res[%d]=%d: 1 .. %d", who, i, res, MI_VOX_MAX_RES);
+        VOX_CHECK_ARG(isfinite(lo) && isfinite(hi) && lo < hi, "%s: axis %d: lo=%g, hi=%g must be finite with lo < hi", who, i, (double)lo, (double)hi);
+        const float step = (hi - lo) / (float)res, inv = (float)res / (hi - lo);
+        VOX_CHECK_ARG(isfinite(step) && step > 0.0f && isfinite(inv) && inv > 0.0f, "%s: axis %d: the step %g of [%g, %g] / %d is not a positive finite float",
+                      who, i, (double)step, (double)lo, (double)hi, res);
+        g.lo[i] = lo; g.hi[i] = hi; g.inv[i] = inv; g.res[i] = res; g.P[i] = res + 1; g.nb[i] = (res + BLK - 1) / BLK;
+    }
+    if (out) *out = g;
+    return MI_VOX_OK;
+}
+
+static int64_t max_steps_of(const mi_vox_grid* grid, float step) {
+    double s = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        const double e = (double)grid->hi[i] - (double)grid->lo[i];
+        s += e * e;
+    }
+    const double q = ceil(sqrt(s) / (double)step);
+    return q >= 9.0e18 ? INT64_MAX : (int64_t)q + 1;
+}
+
+}  // namespace mivox
+
+using namespace mivox;
+
+extern "C" {
+
+int mi_vox_abi_version(void) { return MI_VOX_ABI_VERSION; }
+const char* mi_vox_last_error(void) { return g_err; }
+
+int mi_vox_record_floats(int B) { return record_floats(B); }
+
+size_t mi_vox_skip_bytes(const mi_vox_grid* grid) {
+    Lattice g;
+    if (check_grid("mi_vox_skip_bytes", grid, &g)) return 0;
+    return (size_t)g.nb[0] * g.nb[1] * g.nb[2];
+}
+
+int64_t mi_vox_max_steps(const mi_vox_grid* grid, float step) {
+    if (check_grid("mi_vox_max_steps", grid, nullptr)) return 0;
+    if (!(isfinite(step) && step > 0.0f)) {
+        set_error("mi_vox_max_steps: step=%g must be a positive finite number", (double)step);
+        return 0;
+    }
+    return max_steps_of(grid, step);
+}
+
+int mi_vox_project(const mi_vox_grid* grid, int B, int D, const float* raw_dev, const float* proj_dev, const int64_t* index_dev, int64_t M,
+                   float* sigma_dev, float* coef_dev, void* stream) {
+    const char* who = "mi_vox_project";
+    Lattice g;
+    if (int rc = check_grid(who, grid, &g)) return rc;
+    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
+    VOX_CHECK_ARG(D >= B && D <= MI_VOX_MAX_DIRS, "%s: D=%d: B=%d .. %d directions", who, D, B, MI_VOX_MAX_DIRS);
+    VOX_CHECK_ARG(M >= 0 && M <= ((int64_t)1 << 31) * THREADS - 1, "%s: M=%lld out of range", who, (long long)M);
+    if (M == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty list may be NULL
+    VOX_CHECK_ARG(raw_dev && proj_dev && index_dev && coef_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(raw_dev, 16) && aligned(coef_dev, 16), "%s: raw and coef must be 16-byte aligned", who);
+    VOX_CHECK_ARG(aligned(proj_dev, 4) && aligned(sigma_dev, 4) && aligned(index_dev, 8), "%s: proj, sigma (4 bytes) or index (8 bytes) is misaligned", who);
+    const long long N = (long long)g.P[0] * g.P[1] * g.P[2];
+    const dim3 blocks((unsigned)((M + THREADS - 1) / THREADS));
+    hipStream_t st = (hipStream_t)stream;
+    const float4* raw4 = reinterpret_cast<const float4*>(raw_dev);
+    const long long* idx = reinterpret_cast<const long long*>(index_dev);
+    float4* coef4 = reinterpret_cast<float4*>(coef_dev);
+    if (B == 1) hipLaunchKernelGGL(project_kernel<1>, blocks, dim3(THREADS), 0, st, raw4, proj_dev, idx, (long long)M, D, N, sigma_dev, coef4);
+    else if (B == 4) hipLaunchKernelGGL(project_kernel<4>, blocks, dim3(THREADS), 0, st, raw4, proj_dev, idx, (long long)M, D, N, sigma_dev, coef4);
+    else hipLaunchKernelGGL(project_kernel<9>, blocks, dim3(THREADS), 0, st, raw4, proj_dev, idx, (long long)M, D, N, sigma_dev, coef4);
+    VOX_LAUNCH_CHECK("project_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_build_skip(const mi_vox_grid* grid, const float* sigma_dev, uint8_t* skip_dev, void* stream) {
+    const char* who = "mi_vox_build_skip";
+    Lattice g;
+    if (int rc = check_grid(who, grid, &g)) return rc;
+    VOX_CHECK_ARG(sigma_dev && skip_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(sigma_dev, 4), "%s: sigma must be 4-byte aligned", who);
+    hipLaunchKernelGGL(skip_kernel, dim3((unsigned)(g.nb[0] * g.nb[1] * g.nb[2])), dim3(64), 0, (hipStream_t)stream, g, sigma_dev, skip_dev);
+    VOX_LAUNCH_CHECK("skip_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_render(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev, const float* rays_dev,
+                  int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev,
+                  uint32_t* visited_dev, void* stream) {
+    const char* who = "mi_vox_render";
+    RenderArgs a{};
+    if (int rc = check_grid(who, grid, &a.g)) return rc;
+    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
+    VOX_CHECK_ARG(cfg != nullptr, "%s: cfg is NULL", who);
+    VOX_CHECK_ARG(isfinite(cfg->step) && cfg->step > 0.0f, "%s: step=%g must be a positive finite number", who, (double)cfg->step);
+    VOX_CHECK_ARG(cfg->t_near < cfg->t_far, "%s: t_near=%g must lie below t_far=%g", who, (double)cfg->t_near, (double)cfg->t_far);
+    VOX_CHECK_ARG(cfg->T_min >= 0.0f && cfg->T_min < 1.0f, "%s: T_min=%g: 0 <= T_min < 1", who, (double)cfg->T_min);
+    VOX_CHECK_ARG(isfinite(cfg->bg[0]) && isfinite(cfg->bg[1]) && isfinite(cfg->bg[2]), "%s: the background must be finite", who);
+    VOX_CHECK_ARG(cfg->use_skip == 0 || cfg->use_skip == 1, "%s: use_skip=%d must be 0 or 1", who, cfg->use_skip);
+    const int64_t steps = max_steps_of(grid, cfg->step);
+    VOX_CHECK_ARG(steps <= MI_VOX_MAX_STEPS, "%s: step=%g gives up to %lld samples per ray, more than %d", who, (double)cfg->step, (long long)steps,
+                  MI_VOX_MAX_STEPS);
+    VOX_CHECK_ARG(n >= 0 && n <= ((int64_t)1 << 31) * RAYS_PER_BLOCK - 1, "%s: n=%lld out of range", who, (long long)n);
+    if (n == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty ray set may be NULL
+    VOX_CHECK_ARG(sigma_dev && coef_dev && rays_dev && rgb_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(skip_dev || !cfg->use_skip, "%s: use_skip needs the skip plane", who);
+    VOX_CHECK_ARG(aligned(coef_dev, 16), "%s: coef must be 16-byte aligned", who);
+    VOX_CHECK_ARG(aligned(sigma_dev, 4) && aligned(rays_dev, 4) && aligned(rgb_dev, 4) && aligned(disp_dev, 4) && aligned(acc_dev, 4) &&
+                      aligned(depth_dev, 4) && aligned(visited_dev, 4),
+                  "%s: a float or uint32 array is not 4-byte aligned", who);
+    a.sigma = sigma_dev; a.coef = reinterpret_cast<const float4*>(coef_dev); a.skip = skip_dev; a.rays = rays_dev; a.n = n;
+    a.step = cfg->step; a.t_near = cfg->t_near; a.t_far = cfg->t_far; a.T_min = cfg->T_min;
+    a.bg[0] = cfg->bg[0]; a.bg[1] = cfg->bg[1]; a.bg[2] = cfg->bg[2];
+    a.use_skip = cfg->use_skip; a.max_steps = (int)steps;
+    a.rgb = rgb_dev; a.disp = disp_dev; a.acc = acc_dev; a.depth = depth_dev; a.visited = visited_dev;
+    const dim3 blocks((unsigned)((n + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK));
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 1) hipLaunchKernelGGL(render_kernel<1>, blocks, dim3(THREADS), 0, st, a);
+    else if (B == 4) hipLaunchKernelGGL(render_kernel<4>, blocks, dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL(render_kernel<9>, blocks, dim3(THREADS), 0, st, a);
+    VOX_LAUNCH_CHECK("render_kernel");
+    return MI_VOX_OK;
+}
+
+}  // extern "C"

@@ -233,6 +233,8 @@ def _frozen(model, opts):
     per call otherwise).  Split precision: the blobs are built here and the device packer's out-of-range count is read once -- a checkpoint
     with a weight beyond the f16 range raises instead of rendering from a clipped network."""
     from .weights import packed_for
+    if getattr(opts, "baked", None) is not None:                                          # frames come from the grid: the network is not packed
+        return None
     packed = packed_for(model)
     if ops.precision(**_precision(opts)).reads_f16s:
         packed.f16s()
@@ -240,9 +242,25 @@ def _frozen(model, opts):
     return packed
 
 
+def _device_of(model, opts):
+    """Where test() / render() work: the baked grid's device when opts.baked is set (``model`` may then be None), else the model's."""
+    grid = getattr(opts, "baked", None)
+    if grid is not None:
+        return grid.device
+    return next(model.parameters()).device if isinstance(model, torch.nn.Module) else model.device
+
+
 def _render_pose(model, posenc, K, pose, hw, opts):
     img_h, img_w = hw
     rays_o, rays_d = make_o_d(img_w, img_h, K, pose[:3, :4])
+    # opts.baked (not a flag of the reference's config.py; absent = None): a baked.RadianceGrid that test() / render() render every pose from, the
+    # network left out; opts.baked_step (absent = None: half the smallest cell edge) and opts.baked_T_min (absent = 0) are its march's step and
+    # early-stop transmittance.  The rays run from the camera through the whole box: opts.near / opts.far bound the network's samples, not the grid's.
+    grid = getattr(opts, "baked", None)
+    if grid is not None:
+        rays = torch.cat([rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)], -1)
+        rgb, disp, _, _ = grid.render(rays, step=getattr(opts, "baked_step", None), T_min=float(getattr(opts, "baked_T_min", 0.0) or 0.0))
+        return rgb, disp
     # opts.occupancy (not a flag of the reference's config.py; absent = None): an occupancy.OccupancyGrid that test() / render() skip empty space with
     rgb_c, disp_c, rgb_f, disp_f = NP.batchify_rays_and_render_by_chunk(rays_o, rays_d, model, posenc, img_h, img_w, K, opts, **_precision(opts),
                                                                         occupancy=getattr(opts, "occupancy", None))
@@ -270,7 +288,7 @@ def test(idx, i_test, posenc, model, test_imgs, gt_intrinsic, gt_extrinsic, hw, 
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
     img_h, img_w = hw
-    dev = next(model.parameters()).device if isinstance(model, torch.nn.Module) else model.device
+    dev = _device_of(model, opts)
     n_pose = len(gt_extrinsic)
     want_frames = save_dir is not None or keep_frames
     # everything a frame produces stays on the device until the loop is over: [mse, psnr (, ssim) (, lpips)] per frame in one tensor, the uint8
@@ -331,7 +349,7 @@ def render(idx, posenc, model, gt_intrinsic, render_pose, hw, opts, *, log_dir: 
     from opts (test.py:119-124); for llff data the spiral the loader produced (``llff_render_poses``; [n,3,5] or [n,4,4],
     the first 3x4 block is the camera) -- and returns ``(rgbs uint8 [N,H,W,3], disps uint8 [N,H,W])`` -- the arrays the reference
     hands to imageio.mimwrite (test.py:166-172).  ``save_dir``: also write ``{i}_rgb.png`` / ``{i}_disp.png``."""
-    dev = next(model.parameters()).device if isinstance(model, torch.nn.Module) else model.device
+    dev = _device_of(model, opts)
     if getattr(opts, "data_type", None) in ("blender", "custom"):
         render_pose = get_render_pose(n_angle=opts.n_angle, single_angle=opts.single_angle, phi=opts.phi, nf=opts.nf)
     elif render_pose is None:
