@@ -5,7 +5,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
-                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B]]
+                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -17,7 +17,7 @@ holds every sample) and the remaining steps skip the samples it marks empty (occ
 supervised by the analytic scene's own opacity and depth, so they need ``--scene solid``.  ``--fused-adam``: optim.FusedAdam (one launch per
 step, skipping a step whose gradients are not finite) instead of torch.optim.Adam.  ``--lr-min LR`` / ``--warmup STEPS``: the reference's
 schedule (main.py:83-90, optim.CosineAnnealingWarmupRestarts) over one cycle of ``--steps``, from LR up to 5e-4 in STEPS steps and back; with
-none of the three the run is what it was.  ``--bake RES[:B]``: after training, the fine network is baked into a radiance grid (baked.py:
+none of the three the run is what it was.  ``--bake RES[:B[:dense|sparse|sparse16]]``: after training, the fine network is baked into a radiance grid (baked.py:
 density and B = 1, 4 or 9 spherical-harmonic colour coefficients, default 9, on a (RES + 1)^3 lattice of the box +-``--mesh-box``), the video poses
 are rendered from the grid as well, with no network, and the PSNR of the grid's frames against the network's and both times are printed.
 """
@@ -54,19 +54,24 @@ def main(argv=None):
     ap.add_argument("--fused-adam", action="store_true", help="optim.FusedAdam instead of torch.optim.Adam")
     ap.add_argument("--lr-min", type=float, default=None, help="warm-up cosine schedule from this rate up to 5e-4 and back over --steps")
     ap.add_argument("--warmup", type=int, default=None, help="warm-up steps of the schedule (default with --lr-min: a twentieth of --steps)")
-    ap.add_argument("--bake", default=None, metavar="RES[:B]", help="bake the fine network into a radiance grid and render the video from it too")
+    ap.add_argument("--bake", default=None, metavar="RES[:B[:STORAGE]]",
+                    help="bake the fine network into a radiance grid and render the video from it too; STORAGE: dense (default), sparse or sparse16 (records of active points only, fp32 or f16)")
     ap.add_argument("--lpips", default=None, metavar="VGG_PTH:LIN_PTH", help="also report LPIPS: a torchvision vgg16 state dict and the lpips package's linear layers, two files for torch.load")
     a = ap.parse_args(argv)
     if a.warmup is not None and not 0 <= a.warmup < a.steps:
         ap.error("--warmup takes a number of steps below --steps")
     bake_res = bake_B = None
+    bake_storage = "dense"
     if a.bake is not None:
+        fields = a.bake.split(":")
         try:
-            bake_res, bake_B = (int(v) for v in (a.bake.split(":") + ["9"])[:2])
+            bake_res, bake_B = (int(v) for v in (fields + ["9"])[:2])
         except ValueError:
-            ap.error("--bake takes RES[:B], one or two integers")
-        if not 1 <= bake_res <= 512 or bake_B not in (1, 4, 9) or a.bake.count(":") > 1:
-            ap.error("--bake takes RES in 1..512 and B in 1, 4, 9")
+            ap.error("--bake takes RES[:B[:STORAGE]], one or two integers and a storage")
+        if len(fields) == 3:
+            bake_storage = fields[2]
+        if not 1 <= bake_res <= 512 or bake_B not in (1, 4, 9) or len(fields) > 3 or bake_storage not in ("dense", "sparse", "sparse16"):
+            ap.error("--bake takes RES in 1..512, B in 1, 4, 9 and STORAGE in dense, sparse, sparse16")
     geometry = None
     if a.geometry is not None:
         try:
@@ -168,7 +173,11 @@ def main(argv=None):
     if bake_res is not None:
         from nerf_pytorch_paeng_amd import baked
         t_bake = time.perf_counter()
-        grid = baked.RadianceGrid(-a.mesh_box, a.mesh_box, bake_res, B=bake_B).bake(fresh, network="fine", precision=a.precision)
+        if bake_storage == "dense":
+            grid = baked.RadianceGrid(-a.mesh_box, a.mesh_box, bake_res, B=bake_B)
+        else:
+            grid = baked.SparseRadianceGrid(-a.mesh_box, a.mesh_box, bake_res, B=bake_B, storage="f16" if bake_storage == "sparse16" else "fp32")
+        grid = grid.bake(fresh, network="fine", precision=a.precision)
         torch.cuda.synchronize()
         t_bake = time.perf_counter() - t_bake
         opts.baked = grid                                                                        # the same poses, from the grid alone
@@ -177,7 +186,7 @@ def main(argv=None):
         t_grid = time.perf_counter() - t_grid
         opts.baked = None
         mse = np.mean((rgbs_g.astype(np.float64) - rgbs.astype(np.float64)) ** 2, axis=(1, 2, 3)) / 255.0 ** 2
-        print(f"bake: {bake_res}^3 cells, B={bake_B}, {grid.nbytes / 2 ** 20:.1f} MiB in {t_bake:.2f} s; {rgbs_g.shape[0]} frames from the grid in {t_grid * 1e3:.1f} ms "
+        print(f"bake: {bake_res}^3 cells, B={bake_B}, {bake_storage}, {grid.nbytes / 2 ** 20:.1f} MiB in {t_bake:.2f} s; {rgbs_g.shape[0]} frames from the grid in {t_grid * 1e3:.1f} ms "
               f"(the network: {t_net * 1e3:.1f} ms, PNG writing included in both); PSNR of the grid's frames against the network's "
               f"{['%.2f' % (-10.0 * np.log10(max(m, 1e-12))) for m in mse]} dB; {a.out}/render_baked")
     if a.mesh:

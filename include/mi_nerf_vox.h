@@ -20,6 +20,18 @@
  *   skip    uint8 [ceil(res_z / 8), ceil(res_y / 8), ceil(res_x / 8)], one byte per block of 8^3 cells: 0 iff sigma == 0 at every lattice
  *           point of the block's cells EXTENDED BY ONE CELL on every side (clipped to the lattice), i.e. at the points
  *           max(8 b_i - 1, 0) .. min(min(8 b_i + 8, res_i) + 1, res_i) per axis; 1 otherwise.
+ *   THE COMPACT GRID keeps sigma and skip as they are and stores records only where the render rule can read one.
+ *   active  a lattice point is active iff it or one of its 26 neighbours (clipped to the lattice) has sigma > 0.  The rule reads a record
+ *           only when sigma_s > 0; weights are >= 0, so a corner of the sample's cell has sigma > 0, and all eight corners are then active.
+ *   slot    int32 [P_z, P_y, P_x]: at an active point the number of active points with a smaller flat index, -1 at any other.  Record
+ *           numbers follow flat lattice order: active x neighbours have consecutive slots.  M is the number of active points.
+ *   table   M records, 16-byte aligned, in one of two formats:
+ *           MI_VOX_FMT_F32  the R = 4 / 16 / 32 floats of the dense record, unchanged;
+ *           MI_VOX_FMT_F16  the same R values as IEEE binary16 (8 / 32 / 64 bytes), converted from fp32 by round-to-nearest-even, a value
+ *                           beyond the binary16 range becoming +-inf as that conversion gives it; the padding is zero.
+ *   The compact render rule (mi_vox_render_sparse) is THE RENDER RULE with one change in step 3: corner e's record is table[slot[corner]],
+ *   a binary16 record widened to fp32 (exactly) before any arithmetic.  A corner whose slot is < 0 or >= M contributes a zero record and
+ *   loads nothing: a hand-made slot plane cannot make the renderer read outside the table.
  *   The basis at a unit vector (x, y, z):
  *       Y_0 = 0.28209479
  *       Y_1 = -0.48860251 y      Y_2 = 0.48860251 z      Y_3 = -0.48860251 x
@@ -73,7 +85,7 @@
 extern "C" {
 #endif
 
-#define MI_VOX_ABI_VERSION 1
+#define MI_VOX_ABI_VERSION 2
 
 /* status codes (the values of mi_nerf.h) */
 #define MI_VOX_OK 0
@@ -84,6 +96,8 @@ extern "C" {
 #define MI_VOX_BLOCK 8            /* cells per axis of one skip block */
 #define MI_VOX_MAX_DIRS 256       /* largest D of mi_vox_project */
 #define MI_VOX_MAX_STEPS 65536    /* largest mi_vox_max_steps that mi_vox_render takes */
+#define MI_VOX_FMT_F32 0          /* record formats of THE COMPACT GRID */
+#define MI_VOX_FMT_F16 1
 
 int mi_vox_abi_version(void);
 /* Thread-local text of the last error on this thread ("" if none). */
@@ -127,6 +141,28 @@ int mi_vox_build_skip(const mi_vox_grid* grid, const float* sigma_dev, uint8_t* 
 int mi_vox_render(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev, const float* rays_dev,
                   int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev,
                   uint32_t* visited_dev, void* stream);
+
+/* THE COMPACT GRID.  Bytes of one record of the table: 16 / 64 / 128 for MI_VOX_FMT_F32, 8 / 32 / 64 for MI_VOX_FMT_F16; 0 for any other
+ * B or fmt. */
+size_t mi_vox_record_bytes(int B, int fmt);
+
+/* slot and M from sigma: per-workgroup counts of the active flag, an exclusive scan of the counts, the slot write -- deterministic, the
+ * sums in LDS.  slot_dev int32 [P_z, P_y, P_x] 4-byte aligned, count_dev one int64 (8-byte aligned) that receives M, scratch_dev 16-byte
+ * aligned with at least mi_vox_index_scratch_bytes(grid) bytes (0 + error text if the grid is refused).  The caller reads count_dev back. */
+size_t mi_vox_index_scratch_bytes(const mi_vox_grid* grid);
+int mi_vox_index(const mi_vox_grid* grid, const float* sigma_dev, int32_t* slot_dev, int64_t* count_dev, void* scratch_dev, size_t scratch_bytes,
+                 void* stream);
+
+/* The table from fp32 records, in format fmt.  With slot_dev, src_dev is a dense coef array [P_z, P_y, P_x, R]: the record of every point
+ * with 0 <= slot < M goes to table[slot].  With slot_dev NULL, src_dev is M fp32 records, converted one to one.  src_dev and table_dev
+ * 16-byte aligned; M >= 0 (0: nothing is launched and the arrays are not looked at). */
+int mi_vox_pack(const mi_vox_grid* grid, int B, int fmt, const float* src_dev, const int32_t* slot_dev, int64_t M, void* table_dev, void* stream);
+
+/* The compact render rule.  Everything as mi_vox_render, with slot_dev (4-byte aligned) and table_dev (16-byte aligned; may be NULL when
+ * M is 0) in the place of coef_dev. */
+int mi_vox_render_sparse(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev, int64_t M,
+                         const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev,
+                         float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream);
 
 #ifdef __cplusplus
 }

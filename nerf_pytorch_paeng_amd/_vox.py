@@ -13,8 +13,9 @@ from ._lib import loader
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmi_nerf_vox.so")
-ABI_VERSION = 1
+ABI_VERSION = 2
 MAX_RES, BLOCK, MAX_DIRS, MAX_STEPS = 512, 8, 256, 65536          # MI_VOX_MAX_RES / _BLOCK / _MAX_DIRS / _MAX_STEPS
+FMT_F32, FMT_F16 = 0, 1                                           # MI_VOX_FMT_F32 / _F16: the record formats of the compact grid
 
 
 class Grid(C.Structure):              # mi_vox_grid
@@ -39,6 +40,11 @@ SIGNATURES = {
     "mi_vox_project": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _P]),
     "mi_vox_build_skip": (_I, [_GRIDP, _P, _P, _P]),
     "mi_vox_render": (_I, [_GRIDP, _I, _P, _P, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P]),
+    "mi_vox_record_bytes": (_SZ, [_I, _I]),
+    "mi_vox_index_scratch_bytes": (_SZ, [_GRIDP]),
+    "mi_vox_index": (_I, [_GRIDP, _P, _P, _P, _P, _SZ, _P]),
+    "mi_vox_pack": (_I, [_GRIDP, _I, _I, _P, _P, _I64, _P, _P]),
+    "mi_vox_render_sparse": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P]),
 }
 
 lib, check, last_error = loader(globals(), "mi_vox")

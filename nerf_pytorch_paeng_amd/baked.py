@@ -3,6 +3,8 @@
     grid = baked.RadianceGrid(-1.2, 1.2, 256, B=9).bake(model)          # density + 9 spherical-harmonic colour coefficients per lattice point
     rgb, disp, acc, depth = grid.render(rays)                            # marching through the table: no network
     opts.baked = grid                                                    # harness.test / harness.render then render every pose from it
+    small = grid.compact("f16")                                          # records of the active points only (THE COMPACT GRID), fp32 or f16
+    small = baked.SparseRadianceGrid(-1.2, 1.2, 512, B=9, storage="f16").bake(model)    # ... baked without the dense record array
 
 The lattice is the one of mesh.density_lattice (include/mi_nerf_mesh.h): the grid's sigma plane is that lattice after a ReLU.  Colour is
 the network's post-sigmoid colour at the lattice point, seen from D fixed directions, projected by least squares onto B real spherical
@@ -186,15 +188,28 @@ class RadianceGrid:
         rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
         disp, acc, depth = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3)) if want_all else (None, None, None)
         seen = torch.empty(n, dtype=torch.int32, device=dev) if visited else None
-        g = self.c_grid()
         with ops._guard(dev):
-            _vox.check(_vox.lib().mi_vox_render(C.byref(g), self.B, dev_ptr(self.sigma, "sigma"), dev_ptr(self.coef, "coef", torch.float32, 16),
-                                                dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
-                                                dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
-                                                dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render")
+            self._launch_render(rays, n, cfg, rgb, disp, acc, depth, seen, dev)
         out = (rgb, disp, acc, depth) if want_all else (rgb,)
         out = out + (seen,) if visited else out
         return out if len(out) > 1 else out[0]
+
+    def _launch_render(self, rays, n, cfg, rgb, disp, acc, depth, seen, dev) -> None:
+        g = self.c_grid()
+        _vox.check(_vox.lib().mi_vox_render(C.byref(g), self.B, dev_ptr(self.sigma, "sigma"), dev_ptr(self.coef, "coef", torch.float32, 16),
+                                            dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
+                                            dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
+                                            dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render")
+
+    def compact(self, storage: str = "fp32") -> "SparseRadianceGrid":
+        """The same grid as a SparseRadianceGrid: mi_vox_index, one read-back of the count, mi_vox_pack.  sigma and skip are copies."""
+        self._need()
+        out = SparseRadianceGrid(self.lo, self.hi, self.res, self.B, storage)
+        out.sigma, out.skip = self.sigma.clone(), self.skip.clone()
+        out.index()
+        out.table = out.empty_table(out.count)
+        out.pack(self.coef, out.table, out.count, slot=out.slot)
+        return out
 
     # ---- baking --------------------------------------------------------------------------------------
     def bake(self, model_or_packed, network: str = "fine", D: int = 32, sigma_min: float = 0.0, precision=None,
@@ -224,6 +239,142 @@ class RadianceGrid:
         if tuple(sigma.shape) != grid.points or tuple(coef.shape) != grid.points + (grid.record_floats,) or tuple(skip.shape) != grid.skip_shape:
             raise MiNerfError(f"{path}: the arrays do not fit the grid ({tuple(sigma.shape)}, {tuple(coef.shape)}, {tuple(skip.shape)})")
         grid.sigma, grid.coef, grid.skip = sigma.float(), coef.float(), skip.to(torch.uint8)
+        return grid.to(device) if device is not None else grid
+
+
+STORAGES = {"fp32": (_vox.FMT_F32, torch.float32), "f16": (_vox.FMT_F16, torch.float16)}
+
+
+class SparseRadianceGrid(RadianceGrid):
+    """THE COMPACT GRID of the header: ``sigma`` and ``skip`` as in a RadianceGrid, ``slot`` int32 [P_z, P_y, P_x] (the record number of an
+    active point, -1 elsewhere), ``table`` [count, R] float32 (``storage="fp32"``) or float16 (``"f16"``), ``count`` the number of active
+    points.  ``coef`` stays None: there is no dense record array.  Renders bit for bit what the dense grid with the same records renders."""
+
+    def __init__(self, lo, hi, res, B: int = 9, storage: str = "fp32"):
+        if storage not in STORAGES:
+            raise MiNerfError(f"storage={storage!r}: 'fp32' or 'f16'")
+        super().__init__(lo, hi, res, B)
+        self.storage = storage
+        self.slot: Optional[torch.Tensor] = None
+        self.table: Optional[torch.Tensor] = None
+        self.count = 0
+
+    @property
+    def fmt(self) -> int:
+        return STORAGES[self.storage][0]
+
+    @property
+    def record_bytes(self) -> int:
+        return int(_vox.lib().mi_vox_record_bytes(self.B, self.fmt))
+
+    @property
+    def nbytes(self) -> int:
+        """The real bytes: sigma, slot, skip and ``count`` records."""
+        n = self.points[0] * self.points[1] * self.points[2]
+        return 8 * n + self.count * self.record_bytes + self.skip_shape[0] * self.skip_shape[1] * self.skip_shape[2]
+
+    def empty_table(self, count: int, device=None) -> torch.Tensor:
+        return torch.empty(count, self.record_floats, dtype=STORAGES[self.storage][1], device=self.sigma.device if device is None else device)
+
+    def allocate(self, device) -> "SparseRadianceGrid":
+        """An empty scene on ``device``: no active point, no record."""
+        device = torch.device(device)
+        self.sigma = torch.zeros(self.points, dtype=torch.float32, device=device)
+        self.slot = torch.full(self.points, -1, dtype=torch.int32, device=device)
+        self.skip = torch.zeros(self.skip_shape, dtype=torch.uint8, device=device)
+        self.count, self.table = 0, self.empty_table(0, device)
+        return self
+
+    def to(self, device) -> "SparseRadianceGrid":
+        self._need()
+        self.sigma, self.slot, self.table, self.skip = (t.to(device) for t in (self.sigma, self.slot, self.table, self.skip))
+        return self
+
+    def _need(self) -> None:
+        if self.sigma is None or self.slot is None or self.table is None or self.skip is None:
+            raise MiNerfError("the grid holds nothing yet: bake(), bake_field(), RadianceGrid.compact(), allocate() or load() first")
+
+    def project(self, *args, **kwargs):
+        raise MiNerfError("a SparseRadianceGrid has no dense record array to project into: bake_field(..., storage='sparse') fills its table")
+
+    # ---- the library's entries -----------------------------------------------------------------------
+    def index(self) -> "SparseRadianceGrid":
+        """mi_vox_index: ``slot`` and ``count`` from ``sigma`` (the count is read back once)."""
+        if self.sigma is None:
+            raise MiNerfError("index() needs sigma")
+        dev = self.sigma.device
+        g = self.c_grid()
+        need = int(_vox.lib().mi_vox_index_scratch_bytes(C.byref(g)))
+        self.slot = torch.empty(self.points, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_index(C.byref(g), dev_ptr(self.sigma, "sigma"), dev_ptr(self.slot, "slot", torch.int32), dev_ptr(count, "count", torch.int64, 8),
+                                               dev_ptr(scratch, "scratch", torch.uint8, 16), need, stream_ptr(dev)), "mi_vox_index")
+        self.count = int(count.item())
+        return self
+
+    def pack(self, src: torch.Tensor, table: torch.Tensor, count: int, slot: Optional[torch.Tensor] = None) -> None:
+        """mi_vox_pack into ``table`` (a view of the table's rows from an even record number on): from a dense coef array with ``slot``, or
+        from ``count`` fp32 records one to one without."""
+        dev = table.device
+        g = self.c_grid()
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_pack(C.byref(g), self.B, self.fmt, dev_ptr(src, "src", torch.float32, 16) if count else None,
+                                              dev_ptr(slot, "slot", torch.int32), int(count),
+                                              dev_ptr(table, "table", STORAGES[self.storage][1], 16) if count else None, stream_ptr(dev)), "mi_vox_pack")
+
+    def _launch_render(self, rays, n, cfg, rgb, disp, acc, depth, seen, dev) -> None:
+        g = self.c_grid()
+        _vox.check(_vox.lib().mi_vox_render_sparse(C.byref(g), self.B, self.fmt, dev_ptr(self.sigma, "sigma"), dev_ptr(self.slot, "slot", torch.int32),
+                                                   dev_ptr(self.table, "table", STORAGES[self.storage][1], 16) if self.count else None, self.count,
+                                                   dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
+                                                   dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
+                                                   dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render_sparse")
+
+    def compact(self, storage: str = "fp32") -> "SparseRadianceGrid":
+        raise MiNerfError("the grid is compact already")
+
+    def to_dense(self) -> RadianceGrid:
+        """A RadianceGrid with the same records (binary16 widened exactly); inactive points hold zero records.  Torch ops: works on any device."""
+        self._need()
+        out = RadianceGrid(self.lo, self.hi, self.res, self.B)
+        out.sigma, out.skip = self.sigma.clone(), self.skip.clone()
+        out.coef = torch.zeros(*self.points, self.record_floats, dtype=torch.float32, device=self.sigma.device)
+        where = (self.slot >= 0) & (self.slot < self.count)
+        out.coef[where] = self.table[self.slot[where].long()].float()
+        return out
+
+    # ---- baking --------------------------------------------------------------------------------------
+    def bake(self, model_or_packed, network: str = "fine", D: int = 32, sigma_min: float = 0.0, precision=None,
+             slab_points: int = SLAB_POINTS, shell: str = "field") -> "SparseRadianceGrid":
+        """RadianceGrid.bake without a dense record array: see ``bake_field(..., storage=...)``."""
+        from . import mesh
+        from .weights import packed_for
+        packed = packed_for(model_or_packed)
+        dev, net, blob = mesh._blob(packed, network, mesh.check_precision(None))
+        density = mesh.density_lattice(packed, self.lo, self.hi, self.res, network=network, precision=precision)
+        return bake_field(lambda rays, z: ops.mlp_rays(net, blob, rays, z), self.lo, self.hi, self.res, B=self.B, D=D, sigma_min=sigma_min,
+                          slab_points=slab_points, device=dev, density=density, grid=self, shell=shell,
+                          storage="sparse16" if self.storage == "f16" else "sparse")
+
+    # ---- persistence ---------------------------------------------------------------------------------
+    def save(self, path: str) -> None:
+        """npz: lo, hi, res, B, storage and the four arrays."""
+        self._need()
+        np.savez_compressed(path, lo=np.asarray(self.lo, np.float32), hi=np.asarray(self.hi, np.float32), res=np.asarray(self.res, np.int32),
+                            B=np.asarray(self.B, np.int32), storage=np.asarray(self.storage), sigma=self.sigma.cpu().numpy(), slot=self.slot.cpu().numpy(),
+                            table=self.table.cpu().numpy(), skip=self.skip.cpu().numpy())
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "SparseRadianceGrid":
+        with np.load(path, allow_pickle=False) as f:
+            grid = cls(f["lo"].tolist(), f["hi"].tolist(), f["res"].tolist(), int(f["B"]), str(f["storage"]))
+            sigma, slot, table, skip = (torch.from_numpy(np.ascontiguousarray(f[k])) for k in ("sigma", "slot", "table", "skip"))
+        if (tuple(sigma.shape) != grid.points or tuple(slot.shape) != grid.points or table.dim() != 2 or table.shape[1] != grid.record_floats
+                or tuple(skip.shape) != grid.skip_shape or table.dtype != STORAGES[grid.storage][1]):
+            raise MiNerfError(f"{path}: the arrays do not fit the grid ({tuple(sigma.shape)}, {tuple(slot.shape)}, {tuple(table.shape)} {table.dtype}, {tuple(skip.shape)})")
+        grid.sigma, grid.slot, grid.table, grid.skip, grid.count = sigma.float(), slot.to(torch.int32), table, skip.to(torch.uint8), int(table.shape[0])
         return grid.to(device) if device is not None else grid
 
 
@@ -257,7 +408,7 @@ def lattice_positions(lo, hi, res, index: torch.Tensor) -> torch.Tensor:
 
 def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi, res, B: int = 9, D: int = 32, sigma_min: float = 0.0,
                slab_points: int = SLAB_POINTS, device="cuda:0", density: Optional[torch.Tensor] = None,
-               grid: Optional[RadianceGrid] = None, shell: str = "field") -> RadianceGrid:
+               grid: Optional[RadianceGrid] = None, shell: str = "field", storage: str = "dense") -> RadianceGrid:
     """Bake any field ``fn(rays [n,6], z [n,S]) -> raw [n,S,4]`` (a network's fused entry, ``SolidScene.field``) into a RadianceGrid.
       1. sigma: ``density`` [P_z, P_y, P_x] (raw, before the ReLU) when given, else fn over the lattice rows of mesh.lattice_rows; values
          <= sigma_min (and NaN) become 0.
@@ -269,9 +420,22 @@ def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi,
     surface interpolates with).  "field" (default): the field's own colour there, as at every active point -- right for a network, whose
     colour branch is continuous across its surfaces.  "neighbours": the mean of the records of the point's neighbours (of the 26) that
     have density -- for a field whose colour outside its solids means nothing (``SolidScene.field``: frames come out washed with that
-    colour otherwise, docs/design/22_radiance_grid.md)."""
+    colour otherwise, docs/design/22_radiance_grid.md).
+    ``storage``: "dense" (default) | "sparse" | "sparse16" -- the last two give a SparseRadianceGrid (fp32 / binary16 records) and never
+    allocate a dense record array: after sigma, mi_vox_index numbers the active points, the table of that many records is allocated, and
+    step 3 projects slab by slab into the table with record numbers as mi_vox_project's index list (for binary16 into a slab-sized fp32
+    buffer that mi_vox_pack converts into the table).  The result equals the dense bake's ``compact()`` bit for bit.  shell="neighbours"
+    works on the dense table only."""
     from . import mesh
-    grid = RadianceGrid(lo, hi, res, B) if grid is None else grid
+    if storage not in ("dense", "sparse", "sparse16"):
+        raise MiNerfError(f"storage={storage!r}: 'dense', 'sparse' or 'sparse16'")
+    sparse = storage != "dense"
+    if sparse and shell == "neighbours":
+        raise MiNerfError("shell='neighbours' fills the shell on the dense table: bake dense, then compact()")
+    if grid is None:
+        grid = SparseRadianceGrid(lo, hi, res, B, "f16" if storage == "sparse16" else "fp32") if sparse else RadianceGrid(lo, hi, res, B)
+    if isinstance(grid, SparseRadianceGrid) != sparse or (sparse and grid.storage != ("f16" if storage == "sparse16" else "fp32")):
+        raise MiNerfError(f"storage={storage!r} does not fit the grid handed in ({type(grid).__name__})")
     dev = torch.device(device)
     if slab_points < 1:
         raise MiNerfError(f"slab_points={slab_points}: at least one point per slab")
@@ -289,6 +453,8 @@ def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi,
         if tuple(density.shape) != grid.points:
             raise MiNerfError(f"density must be {grid.points}, got {tuple(density.shape)}")
         sigma = torch.where(density > float(sigma_min), density, torch.zeros_like(density)).clamp_(min=0.0, max=torch.finfo(torch.float32).max)
+        if sparse:
+            return _bake_sparse(fn, grid, sigma.contiguous(), proj, omega, D, slab_points)
         grid.allocate(dev)
         grid.sigma.copy_(sigma)
         active = torch.nn.functional.max_pool3d((sigma > 0).to(torch.float32)[None, None], 3, stride=1, padding=1)[0, 0] > 0
@@ -303,4 +469,34 @@ def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi,
         if shell == "neighbours":
             fill_shell(grid)
         grid.build_skip()
+    return grid
+
+
+def _bake_sparse(fn, grid: "SparseRadianceGrid", sigma: torch.Tensor, proj: torch.Tensor, omega: torch.Tensor, D: int, slab_points: int) -> "SparseRadianceGrid":
+    """Steps 2 to 4 of bake_field into a compact grid (under no_grad): sigma | mi_vox_index | the table | slabs of records | skip."""
+    dev = sigma.device
+    grid.sigma = sigma
+    grid.skip = torch.zeros(grid.skip_shape, dtype=torch.uint8, device=dev)
+    grid.index()
+    grid.table = grid.empty_table(grid.count)
+    index = torch.nonzero(grid.slot.reshape(-1) >= 0).reshape(-1)          # flat lattice indices in record order
+    slab = slab_points + (slab_points & 1)                                   # slabs start at even record numbers: 16-byte aligned at 8 bytes a record
+    half = grid.storage == "f16"
+    buf = torch.empty(min(slab, grid.count), grid.record_floats, dtype=torch.float32, device=dev) if half else None
+    c_grid = grid.c_grid()
+    for a in range(0, grid.count, slab):
+        idx = index[a:a + slab].contiguous()
+        x = lattice_positions(grid.lo, grid.hi, grid.res, idx)
+        m = idx.numel()
+        rays = torch.cat([x[:, None, :].expand(m, D, 3), omega[None].expand(m, D, 3)], -1).reshape(m * D, 6).contiguous()
+        raw = fn(rays, torch.zeros(m * D, 1, dtype=torch.float32, device=dev)).reshape(m, D, 4)
+        # record numbers as the index list: straight into the fp32 table, or into the buffer from record 0
+        record = torch.arange(0 if half else a, m if half else a + m, dtype=torch.int64, device=dev)
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_project(C.byref(c_grid), grid.B, D, dev_ptr(raw, "raw", torch.float32, 16), dev_ptr(proj, "proj"),
+                                                 dev_ptr(record, "index", torch.int64, 8), m, None,
+                                                 dev_ptr(buf if half else grid.table, "coef", torch.float32, 16), stream_ptr(dev)), "mi_vox_project")
+        if half:
+            grid.pack(buf, grid.table[a:a + m], m)
+    grid.build_skip()
     return grid

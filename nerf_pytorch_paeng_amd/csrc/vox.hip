@@ -6,7 +6,7 @@
 //                          sigmoid of the D colours (increasing j), one record written with 16-byte stores, padding as zero.
 //   skip_kernel            one wave per block of 8^3 cells: the lanes sweep the points of the block extended by one cell, a ballot decides
 //                          the byte, lane 0 stores it.
-//   render_kernel<B>       a GROUP OF 8 LANES PER RAY, 32 rays per workgroup.  Every lane of a group carries the same ray state (origin,
+//   render_kernel<B, ST>   a GROUP OF 8 LANES PER RAY, 32 rays per workgroup.  Every lane of a group carries the same ray state (origin,
 //                          interval counter, transmittance, sums): all control flow is uniform within a group, so the eight lanes are
 //                          always active together.  Lane e owns corner e of the sample's cell: it reads that corner's sigma (4 bytes; the
 //                          eight lanes read 4 pairs of neighbours), and only when the group's sigma_s > 0 its record with 16-byte loads --
@@ -15,6 +15,13 @@
 //                          other half-row): no LDS, no bpermute.  A wave instruction whose 64 lanes read 64 unrelated rows runs ~17x below
 //                          the rate of contiguous segments; here a wave's 64 lanes are 8 rays of neighbouring pixels in neighbouring cells.
 //                          The skip byte and the sigma plane are read before any coefficient: in a baked scene most samples end there.
+//                          ST names the storage: DENSE (mi_vox_render), SPARSE32 and SPARSE16 (mi_vox_render_sparse).  A sparse lane reads
+//                          its corner's slot once sigma_s > 0, then one record of the table: dwordx4 loads for fp32, one 8-byte load (B = 1) or
+//                          16-byte loads (B = 4, 9) for binary16, widened with v_cvt_f32_f16.  Active x neighbours have consecutive slots,
+//                          so the records of a pair of lanes are still adjacent.
+//   index_*_kernel         mi_vox_index: the active flag of 1024 points per workgroup into the slot plane and their count (ballots, wave
+//                          sums through LDS) | one block scans the counts | flags become record numbers.  Deterministic: no atomic.
+//   pack_kernel<F16>       one thread per 16-byte piece of an fp32 record: copied, or converted to four binary16 values, to table[slot].
 //
 // No atomic, no host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
 #include <hip/hip_runtime.h>
@@ -126,7 +133,123 @@ __global__ __launch_bounds__(64) void skip_kernel(const Lattice g, const float* 
 }
 
 // ------------------------------------------------------------------------------------------------
-// mi_vox_render
+// mi_vox_index: flag + count | exclusive scan of the counts | emit
+// ------------------------------------------------------------------------------------------------
+constexpr int IDX_ROWS = 4;                              // a workgroup owns IDX_ROWS rows of THREADS consecutive points
+constexpr int IDX_CHUNK = THREADS * IDX_ROWS;
+constexpr int WAVES = THREADS / 64;
+
+// the active flag of every point goes into the slot plane (1 / 0), the chunk's count into counts[blockIdx.x]
+__global__ __launch_bounds__(THREADS) void index_flag_kernel(const Lattice g, const float* __restrict__ sigma, int* __restrict__ slot,
+                                                             unsigned* __restrict__ counts, long long N) {
+    __shared__ unsigned lds[WAVES];
+    const long long base = (long long)blockIdx.x * IDX_CHUNK;
+    unsigned cnt = 0;                                                      // of this wave, the same in every lane
+    for (int r = 0; r < IDX_ROWS; ++r) {
+        const long long i = base + r * THREADS + threadIdx.x;
+        bool act = false;
+        if (i < N) {
+            const int x = (int)(i % g.P[0]), y = (int)((i / g.P[0]) % g.P[1]), z = (int)(i / ((long long)g.P[0] * g.P[1]));
+            for (int z1 = max(z - 1, 0); z1 <= min(z + 1, g.P[2] - 1); ++z1)
+                for (int y1 = max(y - 1, 0); y1 <= min(y + 1, g.P[1] - 1); ++y1)
+                    for (int x1 = max(x - 1, 0); x1 <= min(x + 1, g.P[0] - 1); ++x1)
+                        act |= sigma[((long long)z1 * g.P[1] + y1) * g.P[0] + x1] > 0.0f;
+            slot[i] = act ? 1 : 0;
+        }
+        cnt += (unsigned)__popcll(__ballot(act));
+    }
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+// one block: the chunk counts -> their exclusive prefix sums in place; *total = M
+__global__ __launch_bounds__(1024) void index_scan_kernel(unsigned* __restrict__ counts, int nb, long long* __restrict__ total) {
+    __shared__ unsigned lds[1024 / 64 + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned carry = 0;
+    for (int c = 0; c < nb; c += 1024) {
+        const int i = c + (int)threadIdx.x;
+        const unsigned v = i < nb ? counts[i] : 0u;
+        unsigned x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned t = __shfl_up(x, d, 64);
+            if (lane >= d) x += t;
+        }
+        if (lane == 63) lds[wave] = x;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned run = 0;
+            for (int w = 0; w < 1024 / 64; ++w) {
+                const unsigned s = lds[w];
+                lds[w] = run;
+                run += s;
+            }
+            lds[1024 / 64] = run;
+        }
+        __syncthreads();
+        if (i < nb) counts[i] = carry + (x - v + lds[wave]);
+        carry += lds[1024 / 64];
+        __syncthreads();                                                   // lds is rewritten by the next round
+    }
+    if (threadIdx.x == 0) *total = (long long)carry;
+}
+
+// flags -> slots: the chunk's first record number from the scan, ranks within a row from a ballot, rows in order
+__global__ __launch_bounds__(THREADS) void index_emit_kernel(int* __restrict__ slot, const unsigned* __restrict__ counts, long long N) {
+    __shared__ unsigned lds[WAVES];
+    const long long base = (long long)blockIdx.x * IDX_CHUNK;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned run = counts[blockIdx.x];
+    for (int r = 0; r < IDX_ROWS; ++r) {
+        const long long i = base + r * THREADS + threadIdx.x;
+        const bool act = i < N && slot[i] != 0;
+        const unsigned long long m = __ballot(act);
+        if (lane == 0) lds[wave] = (unsigned)__popcll(m);
+        __syncthreads();
+        unsigned before = 0, row = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const unsigned s = lds[w];
+            if (w < wave) before += s;
+            row += s;
+        }
+        if (i < N) slot[i] = act ? (int)(run + before + (unsigned)__popcll(m & ((1ull << lane) - 1ull))) : -1;
+        run += row;
+        __syncthreads();                                                   // lds is rewritten by the next row
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// mi_vox_pack: one thread per 16-byte piece of an fp32 record
+// ------------------------------------------------------------------------------------------------
+typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+
+template <bool F16>
+__global__ __launch_bounds__(THREADS) void pack_kernel(const float4* __restrict__ src, const int* __restrict__ slot, long long records, long long M,
+                                                       int R4, void* __restrict__ table) {
+    const long long t = (long long)blockIdx.x * THREADS + threadIdx.x;
+    const long long rec = t / R4;
+    const int q = (int)(t % R4);
+    if (rec >= records) return;
+    long long to = rec;
+    if (slot) {
+        to = slot[rec];
+        if (to < 0 || to >= M) return;
+    }
+    const float4 v = src[rec * R4 + q];
+    if constexpr (F16) {
+        // the conversion rounds to nearest even and gives +-inf beyond the binary16 range
+        const half4_t h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+        reinterpret_cast<uint2*>(table)[to * R4 + q] = __builtin_bit_cast(uint2, h);
+    } else {
+        reinterpret_cast<float4*>(table)[to * R4 + q] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// mi_vox_render, mi_vox_render_sparse
 // ------------------------------------------------------------------------------------------------
 // the sum over a group's eight lanes, in the header's order: x neighbours, y neighbours, then the two halves.  Every lane ends with the
 // same bits (an addition commutes).  quad_perm [1,0,3,2] and [2,3,0,1] exchange within a quad; after them a quad's four lanes agree, so
@@ -140,10 +263,25 @@ __device__ __forceinline__ float group_sum(float v) {
     return v + dpp_half_mirror(v);
 }
 
+// where a render instantiation finds corner e's record
+constexpr int DENSE = 0;                                 // coef[flat(corner)], fp32
+constexpr int SPARSE32 = 1;                              // table[slot[corner]], fp32
+constexpr int SPARSE16 = 2;                              // table[slot[corner]], binary16
+
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+// two binary16 values of one 32-bit word, widened exactly
+__device__ __forceinline__ void widen2(unsigned u, float& lo, float& hi) {
+    const half2_t h = __builtin_bit_cast(half2_t, u);
+    lo = (float)h.x;
+    hi = (float)h.y;
+}
+
 struct RenderArgs {
     Lattice g;
     const float* sigma;
-    const float4* coef;
+    const float4* coef;                                  // the dense coef array, or the table of a compact grid (either format)
+    const int* slot;                                     // compact grids only
+    long long M;
     const uint8_t* skip;
     const float* rays;
     long long n;
@@ -155,10 +293,12 @@ struct RenderArgs {
     unsigned* visited;
 };
 
-template <int B>
+template <int B, int ST>
 __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
-    constexpr int R4 = record_floats(B) / 4;               // 16-byte pieces of a record
+    constexpr int R4 = record_floats(B) / 4;               // 16-byte pieces of an fp32 record
     constexpr int V4 = (3 * B + 3) / 4;                    // the pieces that hold coefficients
+    constexpr int H4 = (3 * B + 7) / 8;                    // ... of a binary16 record (B > 1; the B = 1 record is one 8-byte piece)
+    constexpr int KC = ST == SPARSE16 && B > 1 ? 8 * H4 : 4 * V4;
     const int e = threadIdx.x & (GROUP - 1);               // this lane's corner
     const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 3);
     if (ray >= a.n) return;                                // a whole group leaves together
@@ -247,12 +387,46 @@ __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
             const float alpha = 1.0f - expf(-(sigma_s * delta));
             const float wt = T * alpha;
             if (sigma_s > 0.0f) {
-                const float4* rec = a.coef + at * R4;
-                float kc[V4 * 4];
+                float kc[KC];
+                if constexpr (ST == DENSE) {
+                    const float4* rec = a.coef + at * R4;
 #pragma unroll
-                for (int q = 0; q < V4; ++q) {
-                    const float4 v = rec[q];
-                    kc[4 * q] = v.x; kc[4 * q + 1] = v.y; kc[4 * q + 2] = v.z; kc[4 * q + 3] = v.w;
+                    for (int q = 0; q < V4; ++q) {
+                        const float4 v = rec[q];
+                        kc[4 * q] = v.x; kc[4 * q + 1] = v.y; kc[4 * q + 2] = v.z; kc[4 * q + 3] = v.w;
+                    }
+                } else {
+                    // The slot is read here, after the sigma_s > 0 decision.  Written beside the sigma load it lands here all the same: the
+                    // compiler sinks a load into the one branch that uses it (docs/design/22_radiance_grid.md, 22.9).
+                    // A slot outside [0, M) is a zero record and no load (the one branch that is not uniform in a group: it closes
+                    // before the next DPP sum).
+#pragma unroll
+                    for (int i = 0; i < KC; ++i) kc[i] = 0.0f;
+                    const int sl = a.slot[at];
+                    if (sl >= 0 && (long long)sl < a.M) {
+                        if constexpr (ST == SPARSE32) {
+                            const float4* rec = a.coef + (long long)sl * R4;
+#pragma unroll
+                            for (int q = 0; q < V4; ++q) {
+                                const float4 v = rec[q];
+                                kc[4 * q] = v.x; kc[4 * q + 1] = v.y; kc[4 * q + 2] = v.z; kc[4 * q + 3] = v.w;
+                            }
+                        } else if constexpr (B == 1) {
+                            const uint2 v = reinterpret_cast<const uint2*>(a.coef)[sl];              // the whole 8-byte record
+                            widen2(v.x, kc[0], kc[1]);
+                            widen2(v.y, kc[2], kc[3]);
+                        } else {
+                            const uint4* rec = reinterpret_cast<const uint4*>(a.coef) + (long long)sl * (R4 / 2);
+#pragma unroll
+                            for (int q = 0; q < H4; ++q) {
+                                const uint4 v = rec[q];
+                                widen2(v.x, kc[8 * q], kc[8 * q + 1]);
+                                widen2(v.y, kc[8 * q + 2], kc[8 * q + 3]);
+                                widen2(v.z, kc[8 * q + 4], kc[8 * q + 5]);
+                                widen2(v.w, kc[8 * q + 6], kc[8 * q + 7]);
+                            }
+                        }
+                    }
                 }
                 float col[3];
 #pragma unroll
@@ -322,6 +496,67 @@ static int64_t max_steps_of(const mi_vox_grid* grid, float step) {
     return q >= 9.0e18 ? INT64_MAX : (int64_t)q + 1;
 }
 
+__host__ __device__ constexpr int record_bytes(int B, int fmt) {
+    return fmt == MI_VOX_FMT_F32 ? 4 * record_floats(B) : fmt == MI_VOX_FMT_F16 ? 2 * record_floats(B) : 0;
+}
+
+static inline long long index_chunks(const Lattice& g) { return ((long long)g.P[0] * g.P[1] * g.P[2] + IDX_CHUNK - 1) / IDX_CHUNK; }
+static inline size_t index_scratch_bytes(const Lattice& g) { return ((size_t)index_chunks(g) * sizeof(unsigned) + 15) & ~(size_t)15; }
+
+template <int ST>
+static void launch_render(int B, dim3 blocks, hipStream_t st, const RenderArgs& a) {
+    if (B == 1) hipLaunchKernelGGL((render_kernel<1, ST>), blocks, dim3(THREADS), 0, st, a);
+    else if (B == 4) hipLaunchKernelGGL((render_kernel<4, ST>), blocks, dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL((render_kernel<9, ST>), blocks, dim3(THREADS), 0, st, a);
+}
+
+// mi_vox_render (slot_dev NULL, fmt and M unused) and mi_vox_render_sparse: one set of checks, one kernel body
+static int render(const char* who, bool sparse, const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const void* coef_dev,
+                  const int32_t* slot_dev, int64_t M, const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg,
+                  float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream) {
+    RenderArgs a{};
+    if (int rc = check_grid(who, grid, &a.g)) return rc;
+    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
+    if (sparse) {
+        VOX_CHECK_ARG(fmt == MI_VOX_FMT_F32 || fmt == MI_VOX_FMT_F16, "%s: fmt=%d: MI_VOX_FMT_F32 (0) or MI_VOX_FMT_F16 (1)", who, fmt);
+        VOX_CHECK_ARG(M >= 0 && M <= (int64_t)a.g.P[0] * a.g.P[1] * a.g.P[2], "%s: M=%lld: 0 .. the lattice's points", who, (long long)M);
+    }
+    VOX_CHECK_ARG(cfg != nullptr, "%s: cfg is NULL", who);
+    VOX_CHECK_ARG(isfinite(cfg->step) && cfg->step > 0.0f, "%s: step=%g must be a positive finite number", who, (double)cfg->step);
+    VOX_CHECK_ARG(cfg->t_near < cfg->t_far, "%s: t_near=%g must lie below t_far=%g", who, (double)cfg->t_near, (double)cfg->t_far);
+    VOX_CHECK_ARG(cfg->T_min >= 0.0f && cfg->T_min < 1.0f, "%s: T_min=%g: 0 <= T_min < 1", who, (double)cfg->T_min);
+    VOX_CHECK_ARG(isfinite(cfg->bg[0]) && isfinite(cfg->bg[1]) && isfinite(cfg->bg[2]), "%s: the background must be finite", who);
+    VOX_CHECK_ARG(cfg->use_skip == 0 || cfg->use_skip == 1, "%s: use_skip=%d must be 0 or 1", who, cfg->use_skip);
+    const int64_t steps = max_steps_of(grid, cfg->step);
+    VOX_CHECK_ARG(steps <= MI_VOX_MAX_STEPS, "%s: step=%g gives up to %lld samples per ray, more than %d", who, (double)cfg->step, (long long)steps,
+                  MI_VOX_MAX_STEPS);
+    VOX_CHECK_ARG(n >= 0 && n <= ((int64_t)1 << 31) * RAYS_PER_BLOCK - 1, "%s: n=%lld out of range", who, (long long)n);
+    if (n == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty ray set may be NULL
+    if (sparse) {
+        VOX_CHECK_ARG(sigma_dev && slot_dev && rays_dev && rgb_dev && (coef_dev || M == 0), "%s: NULL pointer", who);
+        VOX_CHECK_ARG(aligned(coef_dev, 16) && aligned(slot_dev, 4), "%s: the table must be 16-byte aligned, slot 4-byte aligned", who);
+    } else {
+        VOX_CHECK_ARG(sigma_dev && coef_dev && rays_dev && rgb_dev, "%s: NULL pointer", who);
+        VOX_CHECK_ARG(aligned(coef_dev, 16), "%s: coef must be 16-byte aligned", who);
+    }
+    VOX_CHECK_ARG(skip_dev || !cfg->use_skip, "%s: use_skip needs the skip plane", who);
+    VOX_CHECK_ARG(aligned(sigma_dev, 4) && aligned(rays_dev, 4) && aligned(rgb_dev, 4) && aligned(disp_dev, 4) && aligned(acc_dev, 4) &&
+                      aligned(depth_dev, 4) && aligned(visited_dev, 4),
+                  "%s: a float or uint32 array is not 4-byte aligned", who);
+    a.sigma = sigma_dev; a.coef = reinterpret_cast<const float4*>(coef_dev); a.slot = slot_dev; a.M = M; a.skip = skip_dev; a.rays = rays_dev; a.n = n;
+    a.step = cfg->step; a.t_near = cfg->t_near; a.t_far = cfg->t_far; a.T_min = cfg->T_min;
+    a.bg[0] = cfg->bg[0]; a.bg[1] = cfg->bg[1]; a.bg[2] = cfg->bg[2];
+    a.use_skip = cfg->use_skip; a.max_steps = (int)steps;
+    a.rgb = rgb_dev; a.disp = disp_dev; a.acc = acc_dev; a.depth = depth_dev; a.visited = visited_dev;
+    const dim3 blocks((unsigned)((n + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK));
+    hipStream_t st = (hipStream_t)stream;
+    if (!sparse) launch_render<DENSE>(B, blocks, st, a);
+    else if (fmt == MI_VOX_FMT_F32) launch_render<SPARSE32>(B, blocks, st, a);
+    else launch_render<SPARSE16>(B, blocks, st, a);
+    VOX_LAUNCH_CHECK("render_kernel");
+    return MI_VOX_OK;
+}
+
 }  // namespace mivox
 
 using namespace mivox;
@@ -387,38 +622,67 @@ int mi_vox_build_skip(const mi_vox_grid* grid, const float* sigma_dev, uint8_t* 
 int mi_vox_render(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev, const float* rays_dev,
                   int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev,
                   uint32_t* visited_dev, void* stream) {
-    const char* who = "mi_vox_render";
-    RenderArgs a{};
-    if (int rc = check_grid(who, grid, &a.g)) return rc;
-    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
-    VOX_CHECK_ARG(cfg != nullptr, "%s: cfg is NULL", who);
-    VOX_CHECK_ARG(isfinite(cfg->step) && cfg->step > 0.0f, "%s: step=%g must be a positive finite number", who, (double)cfg->step);
-    VOX_CHECK_ARG(cfg->t_near < cfg->t_far, "%s: t_near=%g must lie below t_far=%g", who, (double)cfg->t_near, (double)cfg->t_far);
-    VOX_CHECK_ARG(cfg->T_min >= 0.0f && cfg->T_min < 1.0f, "%s: T_min=%g: 0 <= T_min < 1", who, (double)cfg->T_min);
-    VOX_CHECK_ARG(isfinite(cfg->bg[0]) && isfinite(cfg->bg[1]) && isfinite(cfg->bg[2]), "%s: the background must be finite", who);
-    VOX_CHECK_ARG(cfg->use_skip == 0 || cfg->use_skip == 1, "%s: use_skip=%d must be 0 or 1", who, cfg->use_skip);
-    const int64_t steps = max_steps_of(grid, cfg->step);
-    VOX_CHECK_ARG(steps <= MI_VOX_MAX_STEPS, "%s: step=%g gives up to %lld samples per ray, more than %d", who, (double)cfg->step, (long long)steps,
-                  MI_VOX_MAX_STEPS);
-    VOX_CHECK_ARG(n >= 0 && n <= ((int64_t)1 << 31) * RAYS_PER_BLOCK - 1, "%s: n=%lld out of range", who, (long long)n);
-    if (n == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty ray set may be NULL
-    VOX_CHECK_ARG(sigma_dev && coef_dev && rays_dev && rgb_dev, "%s: NULL pointer", who);
-    VOX_CHECK_ARG(skip_dev || !cfg->use_skip, "%s: use_skip needs the skip plane", who);
-    VOX_CHECK_ARG(aligned(coef_dev, 16), "%s: coef must be 16-byte aligned", who);
-    VOX_CHECK_ARG(aligned(sigma_dev, 4) && aligned(rays_dev, 4) && aligned(rgb_dev, 4) && aligned(disp_dev, 4) && aligned(acc_dev, 4) &&
-                      aligned(depth_dev, 4) && aligned(visited_dev, 4),
-                  "%s: a float or uint32 array is not 4-byte aligned", who);
-    a.sigma = sigma_dev; a.coef = reinterpret_cast<const float4*>(coef_dev); a.skip = skip_dev; a.rays = rays_dev; a.n = n;
-    a.step = cfg->step; a.t_near = cfg->t_near; a.t_far = cfg->t_far; a.T_min = cfg->T_min;
-    a.bg[0] = cfg->bg[0]; a.bg[1] = cfg->bg[1]; a.bg[2] = cfg->bg[2];
-    a.use_skip = cfg->use_skip; a.max_steps = (int)steps;
-    a.rgb = rgb_dev; a.disp = disp_dev; a.acc = acc_dev; a.depth = depth_dev; a.visited = visited_dev;
-    const dim3 blocks((unsigned)((n + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK));
+    return render("mi_vox_render", false, grid, B, MI_VOX_FMT_F32, sigma_dev, coef_dev, nullptr, 0, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev, acc_dev,
+                  depth_dev, visited_dev, stream);
+}
+
+int mi_vox_render_sparse(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev, int64_t M,
+                         const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev,
+                         float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream) {
+    return render("mi_vox_render_sparse", true, grid, B, fmt, sigma_dev, table_dev, slot_dev, M, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev, acc_dev,
+                  depth_dev, visited_dev, stream);
+}
+
+size_t mi_vox_record_bytes(int B, int fmt) { return (size_t)record_bytes(B, fmt); }
+
+size_t mi_vox_index_scratch_bytes(const mi_vox_grid* grid) {
+    Lattice g;
+    if (check_grid("mi_vox_index_scratch_bytes", grid, &g)) return 0;
+    return index_scratch_bytes(g);
+}
+
+int mi_vox_index(const mi_vox_grid* grid, const float* sigma_dev, int32_t* slot_dev, int64_t* count_dev, void* scratch_dev, size_t scratch_bytes,
+                 void* stream) {
+    const char* who = "mi_vox_index";
+    Lattice g;
+    if (int rc = check_grid(who, grid, &g)) return rc;
+    VOX_CHECK_ARG(sigma_dev && slot_dev && count_dev && scratch_dev, "%s: NULL pointer", who);
+    const size_t need = index_scratch_bytes(g);
+    VOX_CHECK_ARG(scratch_bytes >= need, "%s: scratch too small: %zu < %zu (mi_vox_index_scratch_bytes)", who, scratch_bytes, need);
+    VOX_CHECK_ARG(aligned(sigma_dev, 4) && aligned(slot_dev, 4) && aligned(count_dev, 8) && aligned(scratch_dev, 16),
+                  "%s: sigma, slot (4 bytes), count (8 bytes) or scratch (16 bytes) is misaligned", who);
+    const long long N = (long long)g.P[0] * g.P[1] * g.P[2];
+    const int nb = (int)index_chunks(g);
+    unsigned* counts = reinterpret_cast<unsigned*>(scratch_dev);
     hipStream_t st = (hipStream_t)stream;
-    if (B == 1) hipLaunchKernelGGL(render_kernel<1>, blocks, dim3(THREADS), 0, st, a);
-    else if (B == 4) hipLaunchKernelGGL(render_kernel<4>, blocks, dim3(THREADS), 0, st, a);
-    else hipLaunchKernelGGL(render_kernel<9>, blocks, dim3(THREADS), 0, st, a);
-    VOX_LAUNCH_CHECK("render_kernel");
+    hipLaunchKernelGGL(index_flag_kernel, dim3((unsigned)nb), dim3(THREADS), 0, st, g, sigma_dev, slot_dev, counts, N);
+    VOX_LAUNCH_CHECK("index_flag_kernel");
+    hipLaunchKernelGGL(index_scan_kernel, dim3(1), dim3(1024), 0, st, counts, nb, reinterpret_cast<long long*>(count_dev));
+    VOX_LAUNCH_CHECK("index_scan_kernel");
+    hipLaunchKernelGGL(index_emit_kernel, dim3((unsigned)nb), dim3(THREADS), 0, st, slot_dev, counts, N);
+    VOX_LAUNCH_CHECK("index_emit_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_pack(const mi_vox_grid* grid, int B, int fmt, const float* src_dev, const int32_t* slot_dev, int64_t M, void* table_dev, void* stream) {
+    const char* who = "mi_vox_pack";
+    Lattice g;
+    if (int rc = check_grid(who, grid, &g)) return rc;
+    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
+    VOX_CHECK_ARG(fmt == MI_VOX_FMT_F32 || fmt == MI_VOX_FMT_F16, "%s: fmt=%d: MI_VOX_FMT_F32 (0) or MI_VOX_FMT_F16 (1)", who, fmt);
+    const long long N = (long long)g.P[0] * g.P[1] * g.P[2];
+    VOX_CHECK_ARG(M >= 0 && M <= N, "%s: M=%lld: 0 .. the lattice's points", who, (long long)M);
+    if (M == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty table may be NULL
+    VOX_CHECK_ARG(src_dev && table_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(src_dev, 16) && aligned(table_dev, 16) && aligned(slot_dev, 4), "%s: src and table must be 16-byte aligned, slot 4-byte aligned", who);
+    const int R4 = record_floats(B) / 4;
+    const long long records = slot_dev ? N : (long long)M;
+    const dim3 blocks((unsigned)((records * R4 + THREADS - 1) / THREADS));
+    hipStream_t st = (hipStream_t)stream;
+    const float4* src4 = reinterpret_cast<const float4*>(src_dev);
+    if (fmt == MI_VOX_FMT_F16) hipLaunchKernelGGL(pack_kernel<true>, blocks, dim3(THREADS), 0, st, src4, slot_dev, records, (long long)M, R4, table_dev);
+    else hipLaunchKernelGGL(pack_kernel<false>, blocks, dim3(THREADS), 0, st, src4, slot_dev, records, (long long)M, R4, table_dev);
+    VOX_LAUNCH_CHECK("pack_kernel");
     return MI_VOX_OK;
 }
 
