@@ -3,14 +3,15 @@ standing in for the dataset loaders (no dataset ships with either repository).  
 reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap the imports back and the same script drives the reference.
 
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
-                                             [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10]]
+                                             [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10] [--mesh-view]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
                                              [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
 +-``--mesh-box`` is turned into a triangle mesh at the level ``--mesh-iso`` (mesh.extract: marching tetrahedra on the device), coloured by the
-network and written as a binary PLY.  No counterpart in the reference.  ``--train-occupancy WARMUP:EVERY``: WARMUP full steps, then an
+network and written as a binary PLY; with ``--mesh-view`` the video poses are then rasterised from the mesh (Mesh.render, the network left out) into
+``render_mesh`` and the PSNR of each frame against the network's frame of the same pose is printed.  No counterpart in the reference.  ``--train-occupancy WARMUP:EVERY``: WARMUP full steps, then an
 occupancy grid is baked from the model (128^3 cells; ``--scene solid``: the box +-1.5 with everything outside it skipped, otherwise a box that
 holds every sample) and the remaining steps skip the samples it marks empty (occupancy_train.py), re-baking every EVERY steps (0: never).
 ``--geometry ACC:DEPTH:DIST``: the weights of the opacity, depth and distortion losses (geometry.py; e.g. 0.1:0:0.01); ACC and DEPTH are
@@ -49,6 +50,7 @@ def main(argv=None):
     ap.add_argument("--mesh-res", type=int, default=128, help="lattice cells per axis (1..512)")
     ap.add_argument("--mesh-iso", type=float, default=10.0, help="raw density of the surface")
     ap.add_argument("--mesh-box", type=float, default=1.5, help="the lattice spans +-this on every axis")
+    ap.add_argument("--mesh-view", action="store_true", help="with --mesh: rasterise the video poses from the mesh too (Mesh.render) and compare with the network's frames")
     ap.add_argument("--train-occupancy", default=None, metavar="WARMUP:EVERY", help="train with an occupancy grid baked after WARMUP full steps, re-baked every EVERY steps")
     ap.add_argument("--geometry", default=None, metavar="ACC:DEPTH:DIST", help="weights of the opacity, depth and distortion losses (ACC, DEPTH: --scene solid only)")
     ap.add_argument("--fused-adam", action="store_true", help="optim.FusedAdam instead of torch.optim.Adam")
@@ -60,6 +62,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.warmup is not None and not 0 <= a.warmup < a.steps:
         ap.error("--warmup takes a number of steps below --steps")
+    if a.mesh_view and not a.mesh:
+        ap.error("--mesh-view renders the mesh that --mesh PATH extracts: give both")
     bake_res = bake_B = None
     bake_storage = "dense"
     if a.bake is not None:
@@ -198,6 +202,15 @@ def main(argv=None):
         m.save_ply(a.mesh)
         print(f"mesh: {m.verts.shape[0]} vertices, {m.tris.shape[0]} triangles at density {a.mesh_iso:g} on a {a.mesh_res}^3 lattice of +-{a.mesh_box:g}; "
               f"area {m.area():.3f}, enclosed volume {m.volume():.4f}; {a.mesh}")
+        if a.mesh_view:
+            opts.mesh_view = m                                                                   # the same poses, from the mesh alone
+            t_view = time.perf_counter()
+            rgbs_m, _ = harness.render(a.steps, posenc, None, K, None, (H, W), opts, save_dir=os.path.join(a.out, "render_mesh"))
+            t_view = time.perf_counter() - t_view
+            opts.mesh_view = None
+            mse = np.mean((rgbs_m.astype(np.float64) - rgbs.astype(np.float64)) ** 2, axis=(1, 2, 3)) / 255.0 ** 2
+            print(f"mesh view: {rgbs_m.shape[0]} frames from the mesh in {t_view * 1e3:.1f} ms (the network: {t_net * 1e3:.1f} ms, PNG writing included in both); "
+                  f"PSNR of the mesh's frames against the network's {['%.2f' % (-10.0 * np.log10(max(v, 1e-12))) for v in mse]} dB; {a.out}/render_mesh")
     return res
 
 

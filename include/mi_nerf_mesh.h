@@ -1,5 +1,5 @@
 /*
- * mi_nerf_mesh.h -- C ABI of libmi_nerf_mesh.so: triangle meshes from a density lattice on the MI355X (gfx950).
+ * mi_nerf_mesh.h -- C ABI of libmi_nerf_mesh.so: triangle meshes from a density lattice on the MI355X (gfx950), and views of them.
  *
  * A library of its own ON TOP of the path: include/mi_nerf.h stays what it is, nothing here is declared there, and libmi_nerf_mesh.so
  * exports no mi_nerf_*, mi_occ_*, mi_iqa_* or mi_scene_* symbol.  It links against libmi_nerf.so (rpath $ORIGIN) and calls ONLY
@@ -39,6 +39,39 @@
  * NORMALS (optional).  g(j), the gradient of f at a lattice point: (f[j + 1] - f[j - 1]) / (2.f * step_i) per axis, one-sided
  * (f[1] - f[0]) / step_i and (f[P - 1] - f[P - 2]) / step_i at the lattice boundary.  At a vertex g_i = g_i(a) + t * (g_i(b) - g_i(a)),
  * len = sqrtf((g_x g_x + g_y g_y) + g_z g_z), and the normal is -g_i / len, or (0, 0, 0) when len is 0 or not finite.
+ *
+ * THE VIEW: a rasteriser for the meshes above (mi_mesh_project, mi_mesh_raster and mi_mesh_shade are its public statement).  All fp32
+ * arithmetic is rounded once per operation (no contraction); coverage is integer arithmetic and has no rounding at all.
+ *   Camera.     The pinhole camera of make_o_d: H rows, W columns, fx, fy, cx, cy and the pose c2w [3,4] = (R | t), row-major.  For a
+ *               vertex v:   d_k = v_k - t_k;   p_i = (R_0i d_0 + R_1i d_1) + R_2i d_2   (p = R^T d: three products, two sums, in this order)
+ *                   z  = -p_z                        the parameter t of the pixel's ray x = o + t d: the project's `depth`
+ *                   sx = cx + (fx * p_x) / z         column
+ *                   sy = cy - (fy * p_y) / z         row (downwards)
+ *               Pixel (i, j) -- column i, row j, element j W + i of every output -- has its centre at screen position (i, j): the ray
+ *               make_o_d gives pixel (i, j) passes through exactly that point.
+ *   Snap.       X = rint(256 sx), Y = rint(256 sy) as int32 (24.8 fixed point, ties to even).
+ *   Validity.   A vertex is valid iff z > near, z is finite, |256 sx| <= 2^22 and |256 sy| <= 2^22 (the guard band; a NaN fails every
+ *               test).  An invalid vertex is stored as z = 0, X = Y = INT32_MIN.  mi_mesh_raster and mi_mesh_shade take any arrays and
+ *               hold a vertex valid iff 0 < z < inf, |X| <= 2^22 and |Y| <= 2^22.  THERE IS NO NEAR-PLANE CLIPPING: a triangle with an
+ *               invalid vertex, or with a vertex number outside [0, V), is not drawn (and nothing is read out of bounds for it).
+ *   Coverage.   orient(a, b, p) = (X_b - X_a)(Y_p - Y_a) - (Y_b - Y_a)(X_p - X_a) on int64.  A2 = orient(v0, v1, v2), the doubled signed area.
+ *               A2 == 0: not drawn.  A triangle is FRONT iff A2 < 0: rows grow downwards, so that is counter-clockwise on the screen,
+ *               which is how mi_mesh_emit's winding (normals towards lower density) looks from outside.  cull 0 draws both, 1 drops
+ *               back faces (A2 > 0), 2 drops front faces.  With s = sign(A2) and P = (256 i, 256 j):
+ *                   e_0 = s orient(v1, v2, P), e_1 = s orient(v2, v0, P), e_2 = s orient(v0, v1, P), a2 = s A2 = e_0 + e_1 + e_2 > 0
+ *               The edge of e_k runs from a to b with (dx, dy) = s (X_b - X_a, Y_b - Y_a); it is a TOP-LEFT edge iff dy < 0, or dy == 0
+ *               and dx > 0.  Pixel (i, j) is covered iff every e_k > 0, or e_k == 0 on a top-left edge.  Two triangles that share an
+ *               edge cover each pixel centre on it exactly once.  No anti-aliasing.  |e_k| < 2^48 for H, W <= MI_MESH_VIEW_MAX_DIM.
+ *   Depth.      Perspective-correct: b_k = (float)e_k / (float)a2 (int64 -> fp32 rounded to nearest even), w_k = b_k / z_k,
+ *               inv = (w_0 + w_1) + w_2, depth = 1.f / inv.
+ *   Visibility. The triangle with the smallest depth wins the pixel (fp32 comparison; depth > 0); ties go to the smaller triangle
+ *               number.  The result does not depend on the order in which triangles are processed: every output is the same bit for
+ *               bit from run to run.
+ *   Shade.      From the winner's number alone: e_k, b_k, w_k and depth as above, then per channel
+ *                   c = ((w_0 c_0 + w_1 c_1) + w_2 c_2) * depth;   c < 0 -> 0, c > 1 -> 1 (a NaN stays a NaN)
+ *               with the per-vertex colours c_k.  Normals: n the same expression of the per-vertex normals (not clamped),
+ *               len = sqrtf((n_x n_x + n_y n_y) + n_z n_z), output n_i / len, or (0, 0, 0) when len is 0 or not finite.  disp = 1.f / depth.
+ * Not in THE VIEW: anti-aliasing, near-plane clipping, textures and lighting, gradients, NDC scenes, triangles beyond the guard band.
  */
 #ifndef MI_NERF_MESH_H
 #define MI_NERF_MESH_H
@@ -52,7 +85,7 @@
 extern "C" {
 #endif
 
-#define MI_MESH_ABI_VERSION 1
+#define MI_MESH_ABI_VERSION 2
 
 /* status codes (the values of mi_nerf.h) */
 #define MI_MESH_OK 0
@@ -62,6 +95,10 @@ extern "C" {
 #define MI_MESH_MAX_RES 512             /* largest res[i] */
 #define MI_MESH_MIN_SLAB_POINTS 1024    /* mi_mesh_density: the smallest slab holds at least this many lattice points (or the whole lattice) */
 #define MI_MESH_SCAN_TILE 1024          /* elements of one block of the prefix sums */
+#define MI_MESH_VIEW_MAX_DIM 16384      /* largest H and W of a view: 256 W <= 2^22, the guard band */
+#define MI_MESH_VIEW_GUARD 4194304      /* 2^22: the guard band of the snapped coordinates */
+#define MI_MESH_VIEW_LARGE_BOX 32       /* pixels in a triangle's clipped bounding box above which a whole wave walks it (mesh_view.hip: measured) */
+#define MI_MESH_VIEW_QUEUE 65536        /* large triangles the queue holds; the ones beyond it are walked by their own lane */
 
 int mi_mesh_abi_version(void);
 /* Thread-local text of the last error on this thread ("" if none). */
@@ -107,6 +144,46 @@ int mi_mesh_count(const mi_mesh_grid* grid, const float* f_dev, float iso, void*
                   void* stream);
 int mi_mesh_emit(const mi_mesh_grid* grid, const float* f_dev, float iso, const void* scratch_dev, size_t scratch_bytes, uint64_t n_verts,
                  uint64_t n_tris, float* verts_dev, int32_t* tris_dev, float* normals_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * THE VIEW.  Three entries, one per stage, so that each can be tested on the inputs of the next; none synchronises the host.  Every
+ * pointer but `cam` and `bg` is a device pointer, 4-byte aligned (scratch: 256).  H and W: 1..MI_MESH_VIEW_MAX_DIM (0 is refused);
+ * V and T: 0..2^31 - 1; V == 0 takes NULL vertex arrays, T == 0 a NULL tris.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mi_mesh_camera {
+    int32_t H, W;
+    float fx, fy, cx, cy;     /* finite; fx and fy not 0 */
+    float c2w[12];            /* [3,4] row-major, finite */
+} mi_mesh_camera;
+
+/* One thread per vertex: verts [V,3] -> X, Y int32 [V] and z float [V] (Camera, Snap, Validity).  near > 0.  V == 0 launches nothing. */
+int mi_mesh_project(const mi_mesh_camera* cam, float near, const float* verts_dev, int64_t V, int32_t* X_dev, int32_t* Y_dev, float* z_dev,
+                    void* stream);
+
+/* The visibility pass (Coverage, Depth, Visibility): tri_out int32 [H,W] = the winner's number or -1, depth_out float [H,W] = its depth or 0;
+ * either may be NULL, not both.  One 64-bit word per pixel, depth bits << 32 | triangle number (a positive float's bits order as the float
+ * does), cleared to all ones and lowered by a 64-bit unsigned atomic minimum; a last kernel resolves the words into the outputs.  One lane
+ * takes one triangle and walks its clipped bounding box; a triangle whose box holds more than large_box pixels is queued, and a second
+ * kernel walks it with a whole wave.  large_box == 0 takes MI_MESH_VIEW_LARGE_BOX, the measured choice; any other value (> 0) exists for
+ * measurements and changes no output.
+ *     mi_mesh_raster_scratch_bytes = a256(8 H W) + a256(24 + 4 MI_MESH_VIEW_QUEUE)
+ *         uint64 word[H W]
+ *         uint32 counters[6]   0: large triangles met   1: triangles drawn by a lane   2, 3: atomic updates issued (low, high word)
+ *                              4, 5: the updates among them that lowered their word
+ *         int32  queue[MI_MESH_VIEW_QUEUE]
+ * The counters are there to be read back by whoever measures.  T == 0 or V == 0: clear and resolve only. */
+size_t mi_mesh_raster_scratch_bytes(int H, int W);   /* 0 + error text if H or W is refused */
+int mi_mesh_raster(int H, int W, int cull, int large_box, const int32_t* X_dev, const int32_t* Y_dev, const float* z_dev, int64_t V,
+                   const int32_t* tris_dev, int64_t T, void* scratch_dev, size_t scratch_bytes, int32_t* tri_out_dev, float* depth_out_dev,
+                   void* stream);
+
+/* One thread per pixel (Shade), from tri_in int32 [H,W]: a pixel is covered iff 0 <= tri_in < T, the triangle's vertex numbers are in
+ * [0, V), its vertices valid and its A2 != 0 (coverage itself is NOT tested again).  colors [V,3] is required when rgb_dev is given, normals [V,3] when
+ * normal_dev is given, bg is 3 floats on the host.  Outputs, any of them NULL but not all:
+ *     rgb [H,W,3]   c | bg        disp [H,W]   1 / depth | 0        acc [H,W]   1 | 0        depth [H,W]   depth | 0        normal [H,W,3]   n | 0 */
+int mi_mesh_shade(int H, int W, const int32_t* X_dev, const int32_t* Y_dev, const float* z_dev, int64_t V, const int32_t* tris_dev, int64_t T,
+                  const int32_t* tri_in_dev, const float* colors_dev, const float* normals_dev, const float* bg, float* rgb_dev, float* disp_dev,
+                  float* acc_dev, float* depth_dev, float* normal_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@
 
 LIBRARIES has one record per library: its name ("" is libmi_nerf.so itself), its sources, its extra link arguments, and whether libmi_nerf.so
 is built first because the library links against it (rpath $ORIGIN).  _build() builds any record; the build_*_library names bind to it.
+occ and mesh link against libmi_nerf.so; mesh is two translation units (mesh.hip: extraction, which calls the fused network entries;
+mesh_view.hip: the rasteriser, which calls nothing of libmi_nerf.so); the other libraries link against none of the project's.
 
 What lands where:
   nerf_pytorch_paeng_amd/libmi_nerf[_NAME].so (+ .stamp)   the shipped libraries: the only artefacts inside the package, git-ignored, copied with the tree
@@ -49,7 +51,7 @@ LIBRARIES = {
     "iqa": (["iqa.hip"], [], False),
     "occ": (["occ.hip"], LINK_NERF, True),
     "scene": (["scene.hip"], [], False),
-    "mesh": (["mesh.hip"], LINK_NERF, True),
+    "mesh": (["mesh.hip", "mesh_view.hip"], LINK_NERF, True),
     "geo": (["geo.hip"], [], False),
     "pose": (["pose.hip"], [], False),
     "optim": (["optim.hip"], [], False),

@@ -19,7 +19,7 @@
 namespace mimesh {
 
 // ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
-ABI_ERROR_STATE(static, MI_MESH_EHIP)
+ABI_ERROR_STATE(, MI_MESH_EHIP)          // external linkage: mesh_view.hip declares the two functions and writes the same buffer
 ABI_NERF_FAIL(MI_MESH_EINVAL, MI_MESH_EHIP)
 #define MESH_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::mimesh, MI_MESH_EINVAL, cond, __VA_ARGS__)
 #define MESH_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::mimesh, name)

@@ -233,7 +233,9 @@ def _frozen(model, opts):
     per call otherwise).  Split precision: the blobs are built here and the device packer's out-of-range count is read once -- a checkpoint
     with a weight beyond the f16 range raises instead of rendering from a clipped network."""
     from .weights import packed_for
-    if getattr(opts, "baked", None) is not None:                                          # frames come from the grid: the network is not packed
+    if getattr(opts, "baked", None) is not None and getattr(opts, "mesh_view", None) is not None:
+        raise MiNerfError("opts.baked and opts.mesh_view are both set: each renders every frame without the network; set one")
+    if getattr(opts, "baked", None) is not None or getattr(opts, "mesh_view", None) is not None:   # frames come from the grid / the mesh: the network is not packed
         return None
     packed = packed_for(model)
     if ops.precision(**_precision(opts)).reads_f16s:
@@ -243,15 +245,28 @@ def _frozen(model, opts):
 
 
 def _device_of(model, opts):
-    """Where test() / render() work: the baked grid's device when opts.baked is set (``model`` may then be None), else the model's."""
+    """Where test() / render() work: the baked grid's device when opts.baked is set, the mesh's when opts.mesh_view is (``model`` may then be
+    None), else the model's."""
     grid = getattr(opts, "baked", None)
     if grid is not None:
         return grid.device
+    view = getattr(opts, "mesh_view", None)
+    if view is not None:
+        return view.verts.device
     return next(model.parameters()).device if isinstance(model, torch.nn.Module) else model.device
 
 
 def _render_pose(model, posenc, K, pose, hw, opts):
     img_h, img_w = hw
+    # opts.mesh_view (not a flag of the reference's config.py; absent = None): a mesh.Mesh with colours that test() / render() rasterise every pose
+    # from (Mesh.render: THE VIEW of include/mi_nerf_mesh.h), the network left out; opts.mesh_view_near (absent = 1e-3), opts.mesh_view_cull
+    # (absent = 0) and opts.mesh_view_bg (absent = white) are its arguments.  Together with opts.baked it is refused (_frozen).
+    view = getattr(opts, "mesh_view", None)
+    if view is not None:
+        from .mesh import Camera
+        frame = view.render(Camera(img_h, img_w, K, pose[:3, :4]), near=float(getattr(opts, "mesh_view_near", 1e-3)),
+                            cull=int(getattr(opts, "mesh_view_cull", 0)), bg=getattr(opts, "mesh_view_bg", (1.0, 1.0, 1.0)))
+        return frame.rgb.reshape(-1, 3), frame.disp.reshape(-1)
     rays_o, rays_d = make_o_d(img_w, img_h, K, pose[:3, :4])
     # opts.baked (not a flag of the reference's config.py; absent = None): a baked.RadianceGrid that test() / render() render every pose from, the
     # network left out; opts.baked_step (absent = None: half the smallest cell edge) and opts.baked_T_min (absent = 0) are its march's step and

@@ -4,6 +4,8 @@
     m = mesh.extract(f, -1.2, 1.2, iso=10.0)                           # marching tetrahedra: welded vertices, int32 triangles, normals
     m.colorize(model).save_ply("scene.ply")
 
+    frame = m.render(mesh.Camera(H, W, K, pose))                       # THE VIEW: rgb, disp, acc, depth, tri of the mesh from a pinhole camera
+
 ``extract`` takes a field from anywhere -- a network, ``SolidScene.field`` on the lattice rows, a formula -- and follows THE RULE of the
 header: where the surface stays off the lattice boundary the mesh is a closed oriented manifold with normals towards lower density; a
 surface that reaches the boundary is left open there.  ``extract`` reads the two counts back once (the one host synchronisation of the
@@ -102,6 +104,30 @@ def density_lattice(model_or_packed, lo, hi, res, network: str = "fine", precisi
     return f
 
 
+class Camera:
+    """The pinhole camera of ``make_o_d`` for ``Mesh.render``: ``H`` rows, ``W`` columns, the harness's ``K`` ([[fx, 0, cx], [0, fy, cy], ...]) and a
+    camera-to-world ``pose`` [3,4] or [4,4] (a tensor on any device, or host numbers).  The values are read to the host once, here, like
+    ops.make_o_d does per call; a pose that lives on a HIP device ties the camera to that device."""
+
+    def __init__(self, H: int, W: int, K, pose):
+        k = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
+        self.device = pose.device if isinstance(pose, torch.Tensor) and pose.is_cuda else None
+        p = np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose, dtype=np.float32)
+        if p.shape not in ((3, 4), (4, 4)):
+            raise MiNerfError(f"pose must be [3,4] or [4,4], got {list(p.shape)}")
+        self.H, self.W = int(H), int(W)
+        self.c = _mesh.Camera(self.H, self.W, float(np.float32(k[0][0])), float(np.float32(k[1][1])), float(np.float32(k[0][2])),
+                              float(np.float32(k[1][2])), (C.c_float * 12)(*p[:3, :4].reshape(-1).tolist()))
+
+
+class Frame:
+    """What ``Mesh.render`` returns: ``rgb`` [H,W,3], ``disp``, ``acc``, ``depth`` [H,W] float, ``tri`` [H,W] int32 (-1 where nothing is drawn) and
+    ``normal`` [H,W,3] or None, all on the mesh's device."""
+
+    def __init__(self, rgb, disp, acc, depth, tri, normal=None):
+        self.rgb, self.disp, self.acc, self.depth, self.tri, self.normal = rgb, disp, acc, depth, tri, normal
+
+
 class Mesh:
     """An indexed triangle mesh on the device: ``verts`` float [V,3], ``tris`` int32 [T,3], ``normals`` float [V,3] or None (unit, towards
     lower density; zero where the field is flat), ``colors`` float [V,3] in [0,1] or None (``colorize``)."""
@@ -146,6 +172,65 @@ class Mesh:
         """Signed volume by the divergence theorem (fp64): positive for a closed mesh whose normals point outwards."""
         a, b, c = self._corners()
         return float((a * torch.linalg.cross(b, c)).sum() / 6.0)
+
+    def _view_args(self, camera: Camera):
+        if not isinstance(camera, Camera):
+            raise MiNerfError(f"camera must be a mesh.Camera, got {type(camera).__name__}")
+        dev = self.verts.device
+        if dev.type != "cuda":
+            raise MiNerfError(f"the mesh must live on a HIP device (got {dev}); this path has no CPU fallback")
+        if camera.device is not None and camera.device != dev:
+            raise MiNerfError(f"the mesh lives on {dev}, the camera's pose on {camera.device}")
+        for name, t in (("tris", self.tris), ("colors", self.colors), ("normals", self.normals)):
+            if t is not None and t.device != dev:
+                raise MiNerfError(f"the mesh's {name} live on {t.device}, its verts on {dev}")
+        return dev, int(self.verts.shape[0]), int(self.tris.shape[0])
+
+    def project(self, camera: Camera, near: float = 1e-3) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(X, Y int32 [V], z float [V]) of mi_mesh_project: 24.8 fixed-point screen coordinates and depths; an invalid vertex (behind ``near``,
+        not finite, beyond the guard band) is X = Y = INT32_MIN, z = 0."""
+        dev, V, _ = self._view_args(camera)
+        X = torch.empty(V, dtype=torch.int32, device=dev)
+        Y = torch.empty(V, dtype=torch.int32, device=dev)
+        z = torch.empty(V, dtype=torch.float32, device=dev)
+        with ops._guard(dev):
+            _mesh.check(_mesh.lib().mi_mesh_project(C.byref(camera.c), float(near), dev_ptr(as_f32_dev(self.verts), "verts") if V else None, V,
+                                                    dev_ptr(X, "X", torch.int32) if V else None, dev_ptr(Y, "Y", torch.int32) if V else None,
+                                                    dev_ptr(z, "z") if V else None, stream_ptr(dev)), "mi_mesh_project")
+        return X, Y, z
+
+    def render(self, camera: Camera, near: float = 1e-3, cull: int = 0, bg=(1.0, 1.0, 1.0), normals: bool = False) -> "Frame":
+        """THE VIEW of include/mi_nerf_mesh.h: project, raster, shade, queued on the current stream without a host synchronisation.  ``cull``: 0 draws
+        both windings, 1 drops back faces, 2 front faces (``extract``'s winding is front from outside).  Needs ``colors`` (``colorize``, or any
+        [V,3] tensor); ``normals=True`` also shades the per-vertex normals.  A mesh without triangles renders ``bg``."""
+        if self.colors is None:
+            raise MiNerfError("Mesh.render needs per-vertex colours: call colorize(model) first, or set mesh.colors to a [V,3] tensor")
+        if normals and self.normals is None:
+            raise MiNerfError("Mesh.render(normals=True) needs per-vertex normals (extract(..., normals=True))")
+        dev, V, T = self._view_args(camera)
+        if tuple(self.colors.shape) != (V, 3):
+            raise MiNerfError(f"colors must be [{V},3], got {list(self.colors.shape)}")
+        H, W = camera.H, camera.W
+        L = _mesh.lib()
+        nbytes = int(L.mi_mesh_raster_scratch_bytes(H, W))
+        if nbytes == 0:
+            raise MiNerfError(f"mi_mesh_raster refused: {_mesh.last_error()}")
+        X, Y, z = self.project(camera, near)
+        i32 = lambda t, name: dev_ptr(t, name, torch.int32)
+        with ops._guard(dev):
+            st = stream_ptr(dev)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            tri = torch.empty(H, W, dtype=torch.int32, device=dev)
+            out = {k: torch.empty(H, W, *tail, dtype=torch.float32, device=dev) for k, tail in (("rgb", (3,)), ("disp", ()), ("acc", ()), ("depth", ()))}
+            nrm = torch.empty(H, W, 3, dtype=torch.float32, device=dev) if normals else None
+            tris = self.tris.contiguous()
+            mesh_args = (i32(X, "X") if V else None, i32(Y, "Y") if V else None, dev_ptr(z, "z") if V else None, V, i32(tris, "tris") if T else None, T)
+            _mesh.check(L.mi_mesh_raster(H, W, int(cull), 0, *mesh_args, dev_ptr(scratch, "scratch", torch.uint8, 256), nbytes, i32(tri, "tri"), None, st),
+                        "mi_mesh_raster")
+            _mesh.check(L.mi_mesh_shade(H, W, *mesh_args, i32(tri, "tri"), dev_ptr(as_f32_dev(self.colors), "colors") if V else None,
+                                        dev_ptr(as_f32_dev(self.normals), "normals") if (normals and V) else None, (C.c_float * 3)(*(float(b) for b in bg)),
+                                        dev_ptr(out["rgb"]), dev_ptr(out["disp"]), dev_ptr(out["acc"]), dev_ptr(out["depth"]), dev_ptr(nrm), st), "mi_mesh_shade")
+        return Frame(out["rgb"], out["disp"], out["acc"], out["depth"], tri, nrm)
 
     def save_ply(self, path: str) -> None:
         """Binary little-endian PLY: positions, normals when present, uchar colours when present, triangles as uchar-counted int lists."""
