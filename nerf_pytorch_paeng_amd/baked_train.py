@@ -1,0 +1,151 @@
+"""Training a radiance grid against images: the backward pass of the grid renderer (include/mi_nerf_voxgrad.h, libmi_nerf_voxgrad.so).
+
+    grid = baked.RadianceGrid(-1.2, 1.2, 128, B=9).bake(model)           # or .allocate(dev): an empty grid, trained from nothing (skip=False)
+    losses = baked_train.finetune(grid, rays, target, steps=300)         # Adam on sigma and coef against the images' rgb
+    rgb, disp, acc, depth = baked_train.render(grid, rays)               # one autograd node, for a loss of one's own
+
+The forward is ``grid.render`` (libmi_nerf_vox.so); the backward is mi_voxgrad_render_backward, which recomputes the march and ADDS
+dL/d sigma and dL/d coef by THE BACKWARD RULE of the header.  Its sums are fp32 hardware atomic adds: unlike every other entry of the
+package, the gradient is not bit-identical from run to run (docs/design/23_radiance_grid_training.md).  Dense fp32 grids only; there is no
+fallback: a missing library or a failed call raises ``MiNerfError``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional
+
+import torch
+
+from . import _voxgrad, ops
+from ._lib import MiNerfError, dev_ptr, stream_ptr
+from .baked import RadianceGrid, SparseRadianceGrid
+
+
+def _check(grid, rays) -> torch.device:
+    if isinstance(grid, SparseRadianceGrid):
+        raise MiNerfError("a SparseRadianceGrid has no dense record array to differentiate: fine-tune the dense grid, then compact()")
+    if not isinstance(grid, RadianceGrid):
+        raise MiNerfError(f"a baked.RadianceGrid expected, got {type(grid).__name__}")
+    grid._need()
+    dev = grid.sigma.device
+    if dev.type != "cuda":
+        raise MiNerfError(f"the grid must live on a HIP device (got {dev}); this path has no CPU fallback")
+    if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+        raise MiNerfError(f"rays [n,6] expected, got {tuple(rays.shape) if isinstance(rays, torch.Tensor) else type(rays).__name__}")
+    if rays.device != dev:
+        raise MiNerfError(f"rays live on {rays.device}, the grid on {dev}")
+    return dev
+
+
+def backward(grid: RadianceGrid, rays: torch.Tensor, g_rgb: torch.Tensor, g_acc: Optional[torch.Tensor] = None, g_depth: Optional[torch.Tensor] = None,
+             d_sigma: Optional[torch.Tensor] = None, d_coef: Optional[torch.Tensor] = None, step: Optional[float] = None, near: float = 0.0,
+             far: float = math.inf, T_min: float = 0.0, bg=(1.0, 1.0, 1.0), skip: bool = True, check: bool = False):
+    """mi_voxgrad_render_backward: ADDS the gradients of rays [n,6] under g_rgb [n,3] (and g_acc, g_depth [n]) into ``d_sigma`` / ``d_coef``
+    (zeros of the grid's shapes when not given) and returns them; ``check=True`` appends the forward the backward recomputed,
+    (rgb [n,3], acc [n], depth [n])."""
+    dev = _check(grid, rays)
+    n = rays.shape[0]
+    if tuple(g_rgb.shape) != (n, 3) or any(t is not None and tuple(t.shape) != (n,) for t in (g_acc, g_depth)):
+        raise MiNerfError(f"g_rgb [{n},3] and g_acc, g_depth [{n}] expected")
+    d_sigma = torch.zeros_like(grid.sigma) if d_sigma is None else d_sigma
+    d_coef = torch.zeros_like(grid.coef) if d_coef is None else d_coef
+    if d_sigma.shape != grid.sigma.shape or d_coef.shape != grid.coef.shape:
+        raise MiNerfError(f"d_sigma {tuple(grid.sigma.shape)} and d_coef {tuple(grid.coef.shape)} expected")
+    cfg = _voxgrad.RenderCfg(float(0.5 * grid.cell_edge() if step is None else step), float(near), float(far), float(T_min),
+                             (C.c_float * 3)(*(float(v) for v in bg)), int(bool(skip)))
+    g = _voxgrad.Grid((C.c_float * 3)(*grid.lo), (C.c_float * 3)(*grid.hi), (C.c_int32 * 3)(*grid.res))
+    rgb = torch.empty(n, 3, dtype=torch.float32, device=dev) if check else None
+    acc, depth = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2)) if check else (None, None)
+    with ops._guard(dev):
+        _voxgrad.check(_voxgrad.lib().mi_voxgrad_render_backward(
+            C.byref(g), grid.B, dev_ptr(grid.sigma.detach(), "sigma"), dev_ptr(grid.coef.detach(), "coef", torch.float32, 16),
+            dev_ptr(grid.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(g_rgb, "g_rgb"), dev_ptr(g_acc, "g_acc"),
+            dev_ptr(g_depth, "g_depth"), dev_ptr(d_sigma, "d_sigma"), dev_ptr(d_coef, "d_coef", torch.float32, 16), dev_ptr(rgb, "rgb_check"),
+            dev_ptr(acc, "acc_check"), dev_ptr(depth, "depth_check"), stream_ptr(dev)), "mi_voxgrad_render_backward")
+    return (d_sigma, d_coef, rgb, acc, depth) if check else (d_sigma, d_coef)
+
+
+class _Render(torch.autograd.Function):
+    """sigma and coef are the grid's own tensors, passed so that the node hangs on them."""
+
+    @staticmethod
+    def forward(ctx, sigma, coef, grid, rays, kw):
+        ctx.grid, ctx.rays, ctx.kw = grid, rays, kw
+        rgb, disp, acc, depth = grid.render(rays, **kw)
+        ctx.mark_non_differentiable(disp)
+        return rgb, disp, acc, depth
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb, _g_disp, g_acc, g_depth):
+        grid = ctx.grid
+        n = ctx.rays.shape[0]
+        g_rgb = torch.zeros(n, 3, dtype=torch.float32, device=ctx.rays.device) if g_rgb is None else g_rgb.contiguous()
+        g_acc, g_depth = (None if t is None else t.contiguous() for t in (g_acc, g_depth))
+        d_sigma, d_coef = backward(grid, ctx.rays, g_rgb, g_acc, g_depth, **ctx.kw)
+        return d_sigma, d_coef, None, None, None
+
+
+def render(grid: RadianceGrid, rays: torch.Tensor, step: Optional[float] = None, near: float = 0.0, far: float = math.inf, T_min: float = 0.0,
+           bg=(1.0, 1.0, 1.0), skip: bool = True):
+    """(rgb [n,3], disp [n], acc [n], depth [n]) as ``grid.render`` gives them, differentiable with respect to ``grid.sigma`` and
+    ``grid.coef`` where those require a gradient: one autograd node whose backward fills ``grid.sigma.grad`` / ``grid.coef.grad``.  ``disp``
+    is detached and the rays carry no gradient.  Without ``requires_grad`` on either tensor, or under ``no_grad``, it is ``grid.render``.
+    The node differentiates once: a second differentiation raises."""
+    _check(grid, rays)
+    kw = dict(step=step, near=near, far=far, T_min=T_min, bg=tuple(float(v) for v in bg), skip=bool(skip))
+    if not (torch.is_grad_enabled() and (grid.sigma.requires_grad or grid.coef.requires_grad)):
+        return grid.render(rays, **kw)
+    return _Render.apply(grid.sigma, grid.coef, grid, rays.detach().contiguous(), kw)
+
+
+def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps: int, batch: int = 4096, lr_sigma: float = 0.05, lr_coef: float = 0.005,
+             optimizer=torch.optim.Adam, rebuild_skip_every: int = 1, seed: int = 0, step: Optional[float] = None, near: float = 0.0,
+             far: float = math.inf, T_min: float = 0.0, bg=(1.0, 1.0, 1.0), skip: bool = True) -> torch.Tensor:
+    """``steps`` optimiser steps on ``grid.sigma`` (lr_sigma) and ``grid.coef`` (lr_coef) against target [N,3], the rgb of rays [N,6]: a
+    seeded batch of ``batch`` rays drawn on the device per step, the mean squared error on rgb, and ``sigma.clamp_(min=0)`` after every
+    step.  Returns the per-step losses [steps] as a device tensor: nothing synchronises with the host.
+
+    The skip plane describes the sigma that is rendered at every step: ``grid.build_skip()`` runs every ``rebuild_skip_every`` steps and at
+    the end, a step that follows a rebuild renders with the plane (``skip=True``), and the steps between two rebuilds render without it
+    (exact, slower).  With the plane, a sample in an empty block contributes no gradient (the header's rule per sample): density grows
+    outwards from where there is some, block margin by block margin.  ``skip=False`` never uses the plane -- the setting for a grid that
+    starts empty (``allocate()``), where the plane would hide every sample.
+
+    The default rates suit a baked grid: the colours move, the density barely does.  Adam steps every touched element by about its rate
+    whatever the gradient's size, so a large ``lr_sigma`` on small batches fills the empty space next to surfaces with noise (measured in
+    docs/design/23_radiance_grid_training.md, with the gain from larger batches); a grid trained from nothing wants a larger one."""
+    dev = _check(grid, rays)
+    N = rays.shape[0]
+    if not isinstance(target, torch.Tensor) or tuple(target.shape) != (N, 3) or target.device != dev:
+        raise MiNerfError(f"target [{N},3] on {dev} expected")
+    if steps < 0 or batch < 1 or rebuild_skip_every < 1:
+        raise MiNerfError(f"steps={steps} >= 0, batch={batch} >= 1 and rebuild_skip_every={rebuild_skip_every} >= 1 expected")
+    rays, target = rays.detach().float().contiguous(), target.detach().float()
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    was = (grid.sigma.requires_grad, grid.coef.requires_grad)
+    grid.sigma.requires_grad_(True)
+    grid.coef.requires_grad_(True)
+    opt = optimizer([dict(params=[grid.sigma], lr=lr_sigma), dict(params=[grid.coef], lr=lr_coef)])
+    losses = []
+    try:
+        for it in range(steps):
+            fresh = it % rebuild_skip_every == 0
+            if fresh and skip:
+                grid.build_skip()
+            idx = torch.randint(N, (min(batch, N),), generator=gen, device=dev)
+            rgb = render(grid, rays[idx], step=step, near=near, far=far, T_min=T_min, bg=bg, skip=skip and fresh)[0]
+            loss = torch.mean((rgb - target[idx]) ** 2)
+            opt.zero_grad(set_to_none=False)
+            loss.backward()
+            opt.step()
+            with torch.no_grad():
+                grid.sigma.clamp_(min=0.0)
+            losses.append(loss.detach())
+    finally:
+        grid.sigma.requires_grad_(was[0])
+        grid.coef.requires_grad_(was[1])
+        grid.sigma.grad = grid.coef.grad = None
+    grid.build_skip()
+    return torch.stack(losses) if losses else torch.zeros(0, dtype=torch.float32, device=dev)

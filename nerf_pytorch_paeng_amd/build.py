@@ -1,4 +1,4 @@
-"""Build the project's ten shared libraries with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libmi_nerf.so and the ten shared libraries beside it with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m nerf_pytorch_paeng_amd.build [--force]          the shipped libraries (clean build: ~1 min 20 s on 8 cores)
     python -m nerf_pytorch_paeng_amd.build --variant TAG -DFOO -DBAR=1     an A/B variant (tools/ab_probe.py)
@@ -8,13 +8,14 @@
 LIBRARIES has one record per library: its name ("" is libmi_nerf.so itself), its sources, its extra link arguments, and whether libmi_nerf.so
 is built first because the library links against it (rpath $ORIGIN).  _build() builds any record; the build_*_library names bind to it.
 occ and mesh link against libmi_nerf.so; mesh is two translation units (mesh.hip: extraction, which calls the fused network entries;
-mesh_view.hip: the rasteriser, which calls nothing of libmi_nerf.so); the other libraries link against none of the project's.
+mesh_view.hip: the rasteriser, which calls nothing of libmi_nerf.so); the other libraries (voxgrad, the radiance grid's
+backward pass, among them) link against none of the project's.
 
 What lands where:
   nerf_pytorch_paeng_amd/libmi_nerf[_NAME].so (+ .stamp)   the shipped libraries: the only artefacts inside the package, git-ignored, copied with the tree
         to a GPU box.  A stamp hashes the library's sources, EVERY header under csrc/ and include/, the flags and the link arguments; the library is
         up to date iff the stamp matches (no mtimes, no objects needed -- the GPU box gets neither).  Every header for every library: the one rule
-        that cannot miss a header reached through another (csrc/abi_error.h is in all ten); a one-file library is rebuilt a few seconds too often.
+        that cannot miss a header reached through another (csrc/abi_error.h is in all eleven); a one-file library is rebuilt a few seconds too often.
   build_scratch/obj/                                objects of the shipped libraries (cache; tests/test_packing_cpu.py disassembles them)
   build_scratch/obj_TAG/, build_scratch/libmi_nerf_TAG.so    variants of libmi_nerf.so.  build_scratch/ is git-ignored and is not copied: a variant is
         built where it is used (tools/ab_probe.py builds the ones it is asked for on the box).
@@ -45,7 +46,7 @@ FILE_FLAGS = {"mlp_bf16.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "mlp_f
               "mlp_f16s.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"],
               "mlp_f16s_stash.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "dgrad_f16s.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"]}
 LINK_NERF = ["-L" + HERE, "-lmi_nerf", "-Wl,-rpath,$ORIGIN"]
-# name -> (sources, extra link arguments, libmi_nerf.so is built first); iqa, scene, geo, pose, optim, lpips and vox link against no other library of the project
+# name -> (sources, extra link arguments, libmi_nerf.so is built first); iqa, scene, geo, pose, optim, lpips, vox and voxgrad link against no other library of the project
 LIBRARIES = {
     "": (SOURCES, [], False),
     "iqa": (["iqa.hip"], [], False),
@@ -57,6 +58,7 @@ LIBRARIES = {
     "optim": (["optim.hip"], [], False),
     "lpips": (["lpips.hip"], [], False),
     "vox": (["vox.hip"], [], False),
+    "voxgrad": (["voxgrad.hip"], [], False),
 }
 
 
@@ -156,6 +158,7 @@ def build_pose_library(force: bool = False, verbose: bool = False) -> str: retur
 def build_optim_library(force: bool = False, verbose: bool = False) -> str: return _build("optim", force, verbose)
 def build_lpips_library(force: bool = False, verbose: bool = False) -> str: return _build("lpips", force, verbose)
 def build_vox_library(force: bool = False, verbose: bool = False) -> str: return _build("vox", force, verbose)
+def build_voxgrad_library(force: bool = False, verbose: bool = False) -> str: return _build("voxgrad", force, verbose)
 
 
 def build_variant(tag: str, defines) -> str:

@@ -1,0 +1,209 @@
+"""Training a radiance grid, measured: the backward pass next to the forward on the same rays, its atomic traffic, and what fine-tuning
+does to the quality of a baked grid -- one process, interleaved, as medians.
+
+    python tools/voxgrad_probe.py [--res 128 256] [--reps 7] [--steps 300] [--out profiles/r20_voxgrad.txt]
+
+The scene is scenes.SolidScene.default() baked on the box +-1.2 with shell="neighbours".  Timing: per (res, B) and per ray set -- 4 096
+and 65 536 rays drawn at random from an 800 x 800 frame (a training batch), and the frame's 640 000 rays in pixel order -- the device
+time (HIP events) of mi_voxgrad_render_backward into arrays that already exist, and of RadianceGrid.render on the same rays; every
+repetition runs every variant once.  Both with the skip plane, T_min = 0, upstream gradients 2 (rgb - truth) / n.
+Atomic traffic: the adds are counted in numpy (fp32, the header's rule, on every 8th pixel of every 8th row, x 64) the way the kernel
+issues them: per ray and per run of consecutive visited samples in one cell, 8 adds into d_sigma, and 8 x 3 B into d_coef when a sample
+of the run carries weight (w_k > 0).  Adds whose value happens to be exactly 0 are counted all the same (a corner with weight 0, a colour
+outside the clamp, a zero basis value): an upper bound, close on this scene.
+Quality: ``baked_train.finetune`` on the rays of --views training views (400 x 400, on a spiral around the scene) and the PSNR to
+scene.render of two held-out 800 x 800 views before and after, with the steps, the wall time and the loss curve.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from nerf_pytorch_paeng_amd import baked, baked_train, scenes, synthetic                      # noqa: E402
+from nerf_pytorch_paeng_amd.rays import make_o_d                                               # noqa: E402
+
+BOX = 1.2
+ATOMIC_RATE = 1.3e12            # chip-wide fp32 atomic-add rate, bytes added per second (the microarchitecture guide's figure)
+
+
+def frame_rays(H, W, K, az, el, dev, radius=4.0):
+    pose = torch.from_numpy(np.asarray(synthetic.pose_spherical(az, el, radius), dtype=np.float32)).to(dev)
+    o, d = make_o_d(W, H, K, pose[:3, :4])
+    return torch.cat([o.reshape(-1, 3), d.reshape(-1, 3)], -1).contiguous()
+
+
+def count_adds(grid, rays, step, B):
+    """(visited samples, runs, runs with weight) over rays [n,6] (numpy fp32): the header's march in fp32 with the skip rule per sample."""
+    f32 = np.float32
+    sigma, skip = grid.sigma.cpu().numpy(), grid.skip.cpu().numpy()
+    lo, hi = np.asarray(grid.lo, f32), np.asarray(grid.hi, f32)
+    res = np.asarray(grid.res)
+    inv = res.astype(f32) / (hi - lo)
+    o, d = rays[:, :3], rays[:, 3:]
+    n = len(rays)
+    with np.errstate(all="ignore"):
+        L = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        ta, tb = (lo - o) / d, (hi - o) / d
+        t0 = np.fmax(f32(0), np.where(d != 0, np.fmin(ta, tb), -np.inf).max(1)).astype(f32)
+        t1 = np.where(d != 0, np.fmax(ta, tb), np.inf).min(1).astype(f32)
+        live = (t1 > t0) & (((o >= lo) & (o <= hi)) | (d != 0)).all(1)
+        dt = f32(step) / L
+    cap = int(np.ceil(np.sqrt(((hi - lo).astype(np.float64) ** 2).sum()) / step)) + 1
+    T = np.ones(n, f32)
+    cell = np.full(n, -1, np.int64)
+    has_w = np.zeros(n, bool)
+    visited = runs = runs_w = 0
+    for k in range(cap):
+        ak = t0 + f32(k) * dt
+        live &= ak < t1
+        r = np.nonzero(live)[0]
+        if r.size == 0:
+            break
+        bk = np.fmin(t0[r] + f32(k + 1) * dt[r], t1[r])
+        mk = f32(0.5) * (ak[r] + bk)
+        c, f = [], []
+        for i in range(3):
+            g = ((o[r, i] + mk * d[r, i]) - lo[i]) * inv[i]
+            ci = np.clip(np.floor(g).astype(np.int64), 0, res[i] - 1)
+            c.append(ci)
+            f.append(np.clip(g - ci.astype(f32), 0, 1))
+        keep = skip[c[2] >> 3, c[1] >> 3, c[0] >> 3] != 0
+        r, bk, akr = r[keep], bk[keep], ak[r][keep]
+        c, f = [ci[keep] for ci in c], [fi[keep] for fi in f]
+        if r.size == 0:
+            continue
+        s = np.zeros(r.size, f32)
+        for e in range(8):
+            ex, ey, ez = e & 1, (e >> 1) & 1, e >> 2
+            w = (f[0] if ex else 1 - f[0]) * (f[1] if ey else 1 - f[1]) * (f[2] if ez else 1 - f[2])
+            s += w * sigma[c[2] + ez, c[1] + ey, c[0] + ex]
+        alpha = f32(1) - np.exp(-(s * ((bk - akr) * L[r])))
+        wt = T[r] * alpha
+        T[r] = T[r] * (f32(1) - alpha)
+        here = (c[2] * (res[1] + 1) + c[1]) * (res[0] + 1) + c[0]
+        new = here != cell[r]
+        closed = new & (cell[r] >= 0)
+        runs += int(closed.sum())
+        runs_w += int((closed & has_w[r]).sum())
+        has_w[r] = np.where(new, wt > 0, has_w[r] | (wt > 0))
+        cell[r] = here
+        visited += r.size
+    open_ = cell >= 0
+    runs += int(open_.sum())
+    runs_w += int((open_ & has_w).sum())
+    return visited, runs, runs_w
+
+
+def psnr(a, b):
+    return float(-10.0 * torch.log10(torch.mean((a - b) ** 2)))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, nargs="+", default=[128, 256])
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--views", type=int, default=20)
+    ap.add_argument("--batch", type=int, nargs="+", default=[4096, 32768])
+    ap.add_argument("--out", default=os.path.join("profiles", "r20_voxgrad.txt"))
+    a = ap.parse_args(argv)
+    dev = torch.device("cuda:0")
+    scene = scenes.SolidScene.default()
+    K, H, W = synthetic.lego_camera()
+    frame = frame_rays(H, W, K, 30.0, -30.0, dev)
+    n_frame = frame.shape[0]
+    perm = torch.randperm(n_frame, generator=torch.Generator().manual_seed(0)).to(dev)
+    sets = {"4096 random": frame[perm[:4096]].contiguous(), "65536 random": frame[perm[:65536]].contiguous(), f"{n_frame} frame": frame}
+    truth = {k: scene.render(v, 2.0, 6.0, want_all=False) for k, v in sets.items()}
+    lines = [f"radiance-grid training probe: scenes.SolidScene.default() baked on the box +-{BOX:g} (shell='neighbours'), frame {H} x {W}, azimuth 30, elevation -30, "
+             f"radius 4; step = half a cell, skip plane on, T_min = 0; medians of {a.reps} interleaved repetitions after a warm-up"]
+
+    # ---- backward against forward ------------------------------------------------------------------
+    grids = {(res, B): baked.bake_field(scene.field, -BOX, BOX, res, B=B, D=32, device=dev, shell="neighbours") for res in a.res for B in (1, 9)}
+    grads = {k: (torch.zeros_like(g.sigma), torch.zeros_like(g.coef)) for k, g in grids.items()}
+    variants = [(res, B, s) for res in a.res for B in (1, 9) for s in sets]
+    t_b, t_f = {v: [] for v in variants}, {v: [] for v in variants}
+    ups = {}
+    with torch.no_grad():
+        for v in variants:
+            res, B, s = v
+            rgb = grids[(res, B)].render(sets[s], want_all=False)
+            ups[v] = (2.0 * (rgb - truth[s]) / rgb.shape[0]).contiguous()
+        for rep in range(a.reps + 1):                                 # the first pass warms up
+            for v in variants:
+                res, B, s = v
+                g = grids[(res, B)]
+                e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                e0.record()
+                g.render(sets[s], want_all=False)
+                e1.record()
+                baked_train.backward(g, sets[s], ups[v], None, None, *grads[(res, B)])
+                e2.record()
+                e2.synchronize()
+                if rep:
+                    t_f[v].append(e0.elapsed_time(e1))
+                    t_b[v].append(e1.elapsed_time(e2))
+    sub = frame.reshape(H, W, 6)[::8, ::8].reshape(-1, 6).cpu().numpy()
+    counts = {}
+    for res in a.res:
+        g = grids[(res, 1)]
+        counts[res] = tuple(64 * x for x in count_adds(g, sub, 0.5 * g.cell_edge(), 1))
+        vis, runs, runs_w = counts[res]
+        lines.append(f"res {res}^3, the frame, every 8th pixel of every 8th row counted in numpy, x 64: {vis} visited samples in {runs} runs of one cell "
+                     f"({vis / max(runs, 1):.2f} samples per run), {runs_w} runs carry weight")
+    lines.append("  res   B  rays               forward ms   backward ms   backward / forward   adds (frame)   added MB   added GB/s   share of the 1.3 TB/s atomic rate")
+    for v in variants:
+        res, B, s = v
+        f_ms, b_ms = float(np.median(t_f[v])), float(np.median(t_b[v]))
+        tail = ""
+        if s.endswith("frame"):
+            vis, runs, runs_w = counts[res]
+            adds = 8 * runs + 8 * 3 * B * runs_w
+            rate = adds * 4 / (b_ms * 1e-3)
+            tail = f"   {adds:12d}   {adds * 4 / 1e6:8.1f}   {rate / 1e9:9.1f}   {rate / ATOMIC_RATE:6.3f}"
+        lines.append(f"  {res:3d}   {B}  {s:16s}  {f_ms:9.3f}    {b_ms:9.3f}      {b_ms / f_ms:9.2f}{tail}")
+    del grads
+
+    # ---- quality -----------------------------------------------------------------------------------
+    Kt, Ht, Wt = scenes.scaled_camera((400, 400)), 400, 400
+    train = torch.cat([frame_rays(Ht, Wt, Kt, 360.0 * i / a.views + 7.0, -15.0 - 30.0 * (i % 3), dev) for i in range(a.views)]).contiguous()
+    target = scene.render(train, 2.0, 6.0, want_all=False)
+    held = [frame_rays(H, W, K, az, el, dev) for az, el in ((30.0, -30.0), (200.0, -50.0))]
+    held_truth = [scene.render(r, 2.0, 6.0, want_all=False) for r in held]
+    lines.append(f"fine-tuning: {a.views} training views of {Ht} x {Wt} ({train.shape[0]} rays), baked_train.finetune defaults (Adam, lr_sigma 0.05, lr_coef 0.005, "
+                 f"skip plane rebuilt every step) at batch {a.batch}, {a.steps} steps each from the same bake; PSNR to scene.render of two held-out {H} x {W} views (azimuth 30 / 200)")
+    for res in a.res:
+        for B in (1, 9):
+            g = grids.pop((res, B))
+            sigma0, coef0 = g.sigma.clone(), g.coef.clone()
+            with torch.no_grad():
+                before = [psnr(g.render(r, want_all=False), t) for r, t in zip(held, held_truth)]
+            for batch in a.batch:
+                g.sigma.copy_(sigma0)
+                g.coef.copy_(coef0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                losses = baked_train.finetune(g, train, target, a.steps, batch=batch)
+                torch.cuda.synchronize()
+                wall = time.perf_counter() - t0
+                with torch.no_grad():
+                    after = [psnr(g.render(r, want_all=False), t) for r, t in zip(held, held_truth)]
+                ls = losses.cpu().numpy()
+                curve = ", ".join(f"{float(ls[i:i + max(a.steps // 10, 1)].mean()):.5f}" for i in range(0, a.steps, max(a.steps // 10, 1)))
+                lines.append(f"  res {res}^3 B={B} batch {batch}: held-out PSNR {before[0]:.2f} / {before[1]:.2f} dB -> {after[0]:.2f} / {after[1]:.2f} dB; {a.steps} steps in "
+                             f"{wall:.2f} s ({1e3 * wall / max(a.steps, 1):.2f} ms per step, optimiser included); batch loss, means of tenths of the run: {curve}")
+            del g, sigma0, coef0
+            torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
