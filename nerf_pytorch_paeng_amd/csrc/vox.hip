@@ -1,6 +1,7 @@
 // vox.hip -- libmi_nerf_vox.so (include/mi_nerf_vox.h): a radiance grid (density plus spherical-harmonic colour per lattice point), the
 // projection of a network's answers onto it, its empty-space plane, and the renderer that marches rays through it with no network.  A
-// library of its own: it shares abi_error.h with the others at compile time and nothing at link time.
+// library of its own: it shares abi_error.h with the others, and vox_rule.h (the rule's building blocks in device code, the grid and march
+// checks) with voxgrad.hip, at compile time and nothing at link time.
 //
 //   project_kernel<B>      one thread per lattice point of the index list: fmaxf of the density, 3 B dot products of proj rows with the
 //                          sigmoid of the D colours (increasing j), one record written with 16-byte stores, padding as zero.
@@ -29,6 +30,8 @@
 #include <stdint.h>
 #include "../../include/mi_nerf_vox.h"
 #include "abi_error.h"
+#define VOX_RULE_NAMESPACE mivox
+#include "vox_rule.h"
 
 namespace mivox {
 
@@ -37,39 +40,7 @@ ABI_ERROR_STATE(static, MI_VOX_EHIP)
 #define VOX_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::mivox, MI_VOX_EINVAL, cond, __VA_ARGS__)
 #define VOX_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::mivox, name)
 
-constexpr int THREADS = 256;
-constexpr int GROUP = 8;                                 // lanes per ray: the corners of a cell
-constexpr int RAYS_PER_BLOCK = THREADS / GROUP;
-constexpr int BLK = MI_VOX_BLOCK;
-constexpr float EPS32 = 5.9604645e-8f;                   // 2^-24
-
-__host__ __device__ constexpr int record_floats(int B) { return B == 1 ? 4 : B == 4 ? 16 : B == 9 ? 32 : 0; }
-
-// the grid as the kernels see it
-struct Lattice {
-    float lo[3], hi[3], inv[3];
-    int res[3];
-    int P[3];                                            // points per axis
-    int nb[3];                                           // blocks per axis
-};
-
-// the basis of the header at a unit vector
-template <int B>
-__device__ __forceinline__ void sh_basis(float x, float y, float z, float (&Y)[B]) {
-    Y[0] = 0.28209479f;
-    if constexpr (B >= 4) {
-        Y[1] = -0.48860251f * y;
-        Y[2] = 0.48860251f * z;
-        Y[3] = -0.48860251f * x;
-    }
-    if constexpr (B >= 9) {
-        Y[4] = 1.0925484f * (x * y);
-        Y[5] = -1.0925484f * (y * z);
-        Y[6] = 0.31539157f * (((2.0f * z) * z - x * x) - y * y);
-        Y[7] = -1.0925484f * (x * z);
-        Y[8] = 0.54627422f * (x * x - y * y);
-    }
-}
+static_assert(BLK == MI_VOX_BLOCK, "vox_rule.h and mi_nerf_vox.h disagree on the block edge");
 
 // ------------------------------------------------------------------------------------------------
 // mi_vox_project
@@ -251,31 +222,6 @@ __global__ __launch_bounds__(THREADS) void pack_kernel(const float4* __restrict_
 // ------------------------------------------------------------------------------------------------
 // mi_vox_render, mi_vox_render_sparse
 // ------------------------------------------------------------------------------------------------
-// the sum over a group's eight lanes, in the header's order: x neighbours, y neighbours, then the two halves.  Every lane ends with the
-// same bits (an addition commutes).  quad_perm [1,0,3,2] and [2,3,0,1] exchange within a quad; after them a quad's four lanes agree, so
-// the mirror of the half-row (lane i <-> 7 - i) hands each lane the other quad's sum.
-__device__ __forceinline__ float dpp_quad_x(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)); }
-__device__ __forceinline__ float dpp_quad_y(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)); }
-__device__ __forceinline__ float dpp_half_mirror(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)); }
-__device__ __forceinline__ float group_sum(float v) {
-    v = v + dpp_quad_x(v);
-    v = v + dpp_quad_y(v);
-    return v + dpp_half_mirror(v);
-}
-
-// where a render instantiation finds corner e's record
-constexpr int DENSE = 0;                                 // coef[flat(corner)], fp32
-constexpr int SPARSE32 = 1;                              // table[slot[corner]], fp32
-constexpr int SPARSE16 = 2;                              // table[slot[corner]], binary16
-
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-// two binary16 values of one 32-bit word, widened exactly
-__device__ __forceinline__ void widen2(unsigned u, float& lo, float& hi) {
-    const half2_t h = __builtin_bit_cast(half2_t, u);
-    lo = (float)h.x;
-    hi = (float)h.y;
-}
-
 struct RenderArgs {
     Lattice g;
     const float* sigma;
@@ -295,10 +241,6 @@ struct RenderArgs {
 
 template <int B, int ST>
 __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
-    constexpr int R4 = record_floats(B) / 4;               // 16-byte pieces of an fp32 record
-    constexpr int V4 = (3 * B + 3) / 4;                    // the pieces that hold coefficients
-    constexpr int H4 = (3 * B + 7) / 8;                    // ... of a binary16 record (B > 1; the B = 1 record is one 8-byte piece)
-    constexpr int KC = ST == SPARSE16 && B > 1 ? 8 * H4 : 4 * V4;
     const int e = threadIdx.x & (GROUP - 1);               // this lane's corner
     const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 3);
     if (ray >= a.n) return;                                // a whole group leaves together
@@ -387,47 +329,8 @@ __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
             const float alpha = 1.0f - expf(-(sigma_s * delta));
             const float wt = T * alpha;
             if (sigma_s > 0.0f) {
-                float kc[KC];
-                if constexpr (ST == DENSE) {
-                    const float4* rec = a.coef + at * R4;
-#pragma unroll
-                    for (int q = 0; q < V4; ++q) {
-                        const float4 v = rec[q];
-                        kc[4 * q] = v.x; kc[4 * q + 1] = v.y; kc[4 * q + 2] = v.z; kc[4 * q + 3] = v.w;
-                    }
-                } else {
-                    // The slot is read here, after the sigma_s > 0 decision.  Written beside the sigma load it lands here all the same: the
-                    // compiler sinks a load into the one branch that uses it (docs/design/22_radiance_grid.md, 22.9).
-                    // A slot outside [0, M) is a zero record and no load (the one branch that is not uniform in a group: it closes
-                    // before the next DPP sum).
-#pragma unroll
-                    for (int i = 0; i < KC; ++i) kc[i] = 0.0f;
-                    const int sl = a.slot[at];
-                    if (sl >= 0 && (long long)sl < a.M) {
-                        if constexpr (ST == SPARSE32) {
-                            const float4* rec = a.coef + (long long)sl * R4;
-#pragma unroll
-                            for (int q = 0; q < V4; ++q) {
-                                const float4 v = rec[q];
-                                kc[4 * q] = v.x; kc[4 * q + 1] = v.y; kc[4 * q + 2] = v.z; kc[4 * q + 3] = v.w;
-                            }
-                        } else if constexpr (B == 1) {
-                            const uint2 v = reinterpret_cast<const uint2*>(a.coef)[sl];              // the whole 8-byte record
-                            widen2(v.x, kc[0], kc[1]);
-                            widen2(v.y, kc[2], kc[3]);
-                        } else {
-                            const uint4* rec = reinterpret_cast<const uint4*>(a.coef) + (long long)sl * (R4 / 2);
-#pragma unroll
-                            for (int q = 0; q < H4; ++q) {
-                                const uint4 v = rec[q];
-                                widen2(v.x, kc[8 * q], kc[8 * q + 1]);
-                                widen2(v.y, kc[8 * q + 2], kc[8 * q + 3]);
-                                widen2(v.z, kc[8 * q + 4], kc[8 * q + 5]);
-                                widen2(v.w, kc[8 * q + 6], kc[8 * q + 7]);
-                            }
-                        }
-                    }
-                }
+                float kc[record_regs<B, ST>()];
+                fetch_record<B, ST>(a.coef, a.slot, a.M, at, kc);
                 float col[3];
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) {
@@ -467,33 +370,11 @@ __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
 // ------------------------------------------------------------------------------------------------
 // host side: checks, launches
 // ------------------------------------------------------------------------------------------------
-static inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-static int check_grid(const char* who, const mi_vox_grid* grid, Lattice* out) {
-    VOX_CHECK_ARG(grid != nullptr, "%s: grid is NULL", who);
-    Lattice g{};
-    for (int i = 0; i < 3; ++i) {
-        const float lo = grid->lo[i], hi = grid->hi[i];
-        const int res = grid->res[i];
-        VOX_CHECK_ARG(res >= 1 && res <= MI_VOX_MAX_RES, "%s: res[%d]=%d: 1 .. %d", who, i, res, MI_VOX_MAX_RES);
-        VOX_CHECK_ARG(isfinite(lo) && isfinite(hi) && lo < hi, "%s: axis %d: lo=%g, hi=%g must be finite with lo < hi", who, i, (double)lo, (double)hi);
-        const float step = (hi - lo) / (float)res, inv = (float)res / (hi - lo);
-        VOX_CHECK_ARG(isfinite(step) && step > 0.0f && isfinite(inv) && inv > 0.0f, "%s: axis %d: the step %g of [%g, %g] / %d is not a positive finite float",
-                      who, i, (double)step, (double)lo, (double)hi, res);
-        g.lo[i] = lo; g.hi[i] = hi; g.inv[i] = inv; g.res[i] = res; g.P[i] = res + 1; g.nb[i] = (res + BLK - 1) / BLK;
-    }
-    if (out) *out = g;
-    return MI_VOX_OK;
-}
-
-static int64_t max_steps_of(const mi_vox_grid* grid, float step) {
-    double s = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        const double e = (double)grid->hi[i] - (double)grid->lo[i];
-        s += e * e;
-    }
-    const double q = ceil(sqrt(s) / (double)step);
-    return q >= 9.0e18 ? INT64_MAX : (int64_t)q + 1;
+// vox_rule.h's checks under this library's status values
+static int check_grid(const char* who, const mi_vox_grid* grid, Lattice* out) { return grid_ok(set_error, MI_VOX_MAX_RES, who, grid, out) ? MI_VOX_OK : MI_VOX_EINVAL; }
+static int check_basis(const char* who, int B) { return basis_ok(set_error, who, B) ? MI_VOX_OK : MI_VOX_EINVAL; }
+static int check_march(const char* who, const mi_vox_grid* grid, const mi_vox_render_cfg* cfg, int64_t n, int64_t* steps) {
+    return march_ok(set_error, MI_VOX_MAX_STEPS, who, grid, cfg, n, steps) ? MI_VOX_OK : MI_VOX_EINVAL;
 }
 
 __host__ __device__ constexpr int record_bytes(int B, int fmt) {
@@ -516,21 +397,13 @@ static int render(const char* who, bool sparse, const mi_vox_grid* grid, int B, 
                   float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream) {
     RenderArgs a{};
     if (int rc = check_grid(who, grid, &a.g)) return rc;
-    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
+    if (int rc = check_basis(who, B)) return rc;
     if (sparse) {
         VOX_CHECK_ARG(fmt == MI_VOX_FMT_F32 || fmt == MI_VOX_FMT_F16, "%s: fmt=%d: MI_VOX_FMT_F32 (0) or MI_VOX_FMT_F16 (1)", who, fmt);
         VOX_CHECK_ARG(M >= 0 && M <= (int64_t)a.g.P[0] * a.g.P[1] * a.g.P[2], "%s: M=%lld: 0 .. the lattice's points", who, (long long)M);
     }
-    VOX_CHECK_ARG(cfg != nullptr, "%s: cfg is NULL", who);
-    VOX_CHECK_ARG(isfinite(cfg->step) && cfg->step > 0.0f, "%s: step=%g must be a positive finite number", who, (double)cfg->step);
-    VOX_CHECK_ARG(cfg->t_near < cfg->t_far, "%s: t_near=%g must lie below t_far=%g", who, (double)cfg->t_near, (double)cfg->t_far);
-    VOX_CHECK_ARG(cfg->T_min >= 0.0f && cfg->T_min < 1.0f, "%s: T_min=%g: 0 <= T_min < 1", who, (double)cfg->T_min);
-    VOX_CHECK_ARG(isfinite(cfg->bg[0]) && isfinite(cfg->bg[1]) && isfinite(cfg->bg[2]), "%s: the background must be finite", who);
-    VOX_CHECK_ARG(cfg->use_skip == 0 || cfg->use_skip == 1, "%s: use_skip=%d must be 0 or 1", who, cfg->use_skip);
-    const int64_t steps = max_steps_of(grid, cfg->step);
-    VOX_CHECK_ARG(steps <= MI_VOX_MAX_STEPS, "%s: step=%g gives up to %lld samples per ray, more than %d", who, (double)cfg->step, (long long)steps,
-                  MI_VOX_MAX_STEPS);
-    VOX_CHECK_ARG(n >= 0 && n <= ((int64_t)1 << 31) * RAYS_PER_BLOCK - 1, "%s: n=%lld out of range", who, (long long)n);
+    int64_t steps;
+    if (int rc = check_march(who, grid, cfg, n, &steps)) return rc;
     if (n == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty ray set may be NULL
     if (sparse) {
         VOX_CHECK_ARG(sigma_dev && slot_dev && rays_dev && rgb_dev && (coef_dev || M == 0), "%s: NULL pointer", who);
@@ -588,7 +461,7 @@ int mi_vox_project(const mi_vox_grid* grid, int B, int D, const float* raw_dev, 
     const char* who = "mi_vox_project";
     Lattice g;
     if (int rc = check_grid(who, grid, &g)) return rc;
-    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
+    if (int rc = check_basis(who, B)) return rc;
     VOX_CHECK_ARG(D >= B && D <= MI_VOX_MAX_DIRS, "%s: D=%d: B=%d .. %d directions", who, D, B, MI_VOX_MAX_DIRS);
     VOX_CHECK_ARG(M >= 0 && M <= ((int64_t)1 << 31) * THREADS - 1, "%s: M=%lld out of range", who, (long long)M);
     if (M == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty list may be NULL
@@ -668,7 +541,7 @@ int mi_vox_pack(const mi_vox_grid* grid, int B, int fmt, const float* src_dev, c
     const char* who = "mi_vox_pack";
     Lattice g;
     if (int rc = check_grid(who, grid, &g)) return rc;
-    VOX_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
+    if (int rc = check_basis(who, B)) return rc;
     VOX_CHECK_ARG(fmt == MI_VOX_FMT_F32 || fmt == MI_VOX_FMT_F16, "%s: fmt=%d: MI_VOX_FMT_F32 (0) or MI_VOX_FMT_F16 (1)", who, fmt);
     const long long N = (long long)g.P[0] * g.P[1] * g.P[2];
     VOX_CHECK_ARG(M >= 0 && M <= N, "%s: M=%lld: 0 .. the lattice's points", who, (long long)M);

@@ -1,5 +1,6 @@
 // voxgrad.hip -- libmi_nerf_voxgrad.so (include/mi_nerf_voxgrad.h): the backward pass of the radiance-grid renderer.  A library of its
-// own: it shares abi_error.h with the others at compile time and nothing at link time.
+// own: it shares abi_error.h with the others, and vox_rule.h (the rule's building blocks in device code, the grid and march checks) with
+// vox.hip, at compile time and nothing at link time.
 //
 //   backward_kernel<B>     the forward's shape: a GROUP OF 8 LANES PER RAY, 32 rays per workgroup, lane e owns corner e of the sample's
 //                          cell, sums over the group with DPP row operations, no LDS.  All control flow but the adds themselves is uniform
@@ -23,6 +24,8 @@
 #include <stdint.h>
 #include "../../include/mi_nerf_voxgrad.h"
 #include "abi_error.h"
+#define VOX_RULE_NAMESPACE mivoxgrad
+#include "vox_rule.h"
 
 namespace mivoxgrad {
 
@@ -31,49 +34,7 @@ ABI_ERROR_STATE(static, MI_VOXGRAD_EHIP)
 #define VG_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::mivoxgrad, MI_VOXGRAD_EINVAL, cond, __VA_ARGS__)
 #define VG_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::mivoxgrad, name)
 
-constexpr int THREADS = 256;
-constexpr int GROUP = 8;                                 // lanes per ray: the corners of a cell
-constexpr int RAYS_PER_BLOCK = THREADS / GROUP;
-constexpr int BLK = MI_VOXGRAD_BLOCK;
-constexpr float EPS32 = 5.9604645e-8f;                   // 2^-24
-
-__host__ __device__ constexpr int record_floats(int B) { return B == 1 ? 4 : B == 4 ? 16 : B == 9 ? 32 : 0; }
-
-// the grid as the kernel sees it
-struct Lattice {
-    float lo[3], hi[3], inv[3];
-    int res[3];
-    int P[3];                                            // points per axis
-    int nb[3];                                           // blocks per axis
-};
-
-// the basis of include/mi_nerf_vox.h at a unit vector
-template <int B>
-__device__ __forceinline__ void sh_basis(float x, float y, float z, float (&Y)[B]) {
-    Y[0] = 0.28209479f;
-    if constexpr (B >= 4) {
-        Y[1] = -0.48860251f * y;
-        Y[2] = 0.48860251f * z;
-        Y[3] = -0.48860251f * x;
-    }
-    if constexpr (B >= 9) {
-        Y[4] = 1.0925484f * (x * y);
-        Y[5] = -1.0925484f * (y * z);
-        Y[6] = 0.31539157f * (((2.0f * z) * z - x * x) - y * y);
-        Y[7] = -1.0925484f * (x * z);
-        Y[8] = 0.54627422f * (x * x - y * y);
-    }
-}
-
-// the sum over a group's eight lanes in the rule's order: x neighbours, y neighbours, then the two halves; every lane ends with the same bits
-__device__ __forceinline__ float dpp_quad_x(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)); }
-__device__ __forceinline__ float dpp_quad_y(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)); }
-__device__ __forceinline__ float dpp_half_mirror(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)); }
-__device__ __forceinline__ float group_sum(float v) {
-    v = v + dpp_quad_x(v);
-    v = v + dpp_quad_y(v);
-    return v + dpp_half_mirror(v);
-}
+static_assert(BLK == MI_VOXGRAD_BLOCK, "vox_rule.h and mi_nerf_voxgrad.h disagree on the block edge");
 
 struct BackArgs {
     Lattice g;
@@ -116,15 +77,8 @@ __device__ __forceinline__ bool interval(const Lattice& g, const float (&o)[3], 
 // lane e's share w_e * q_e[ch] of the pre-clamp colour: the basis applied to its corner's record, in increasing b
 template <int B>
 __device__ __forceinline__ void corner_colour(const float4* __restrict__ coef, long long at, const float (&Y)[B], float w, float (&wq)[3]) {
-    constexpr int R4 = record_floats(B) / 4;
-    constexpr int V4 = (3 * B + 3) / 4;                    // the 16-byte pieces that hold coefficients
-    float kc[4 * V4];
-    const float4* rec = coef + at * R4;
-#pragma unroll
-    for (int q = 0; q < V4; ++q) {
-        const float4 v = rec[q];
-        kc[4 * q] = v.x; kc[4 * q + 1] = v.y; kc[4 * q + 2] = v.z; kc[4 * q + 3] = v.w;
-    }
+    float kc[record_regs<B, DENSE>()];
+    fetch_record<B, DENSE>(coef, nullptr, 0, at, kc);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
         float q = kc[ch] * Y[0];
@@ -303,33 +257,13 @@ __global__ __launch_bounds__(THREADS) void backward_kernel(const BackArgs a) {
 // ------------------------------------------------------------------------------------------------
 // host side: checks, launch
 // ------------------------------------------------------------------------------------------------
-static inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
+// vox_rule.h's checks under this library's status values
 static int check_grid(const char* who, const mi_voxgrad_grid* grid, Lattice* out) {
-    VG_CHECK_ARG(grid != nullptr, "%s: grid is NULL", who);
-    Lattice g{};
-    for (int i = 0; i < 3; ++i) {
-        const float lo = grid->lo[i], hi = grid->hi[i];
-        const int res = grid->res[i];
-        VG_CHECK_ARG(res >= 1 && res <= MI_VOXGRAD_MAX_RES, "%s: res[%d]=%d: 1 .. %d", who, i, res, MI_VOXGRAD_MAX_RES);
-        VG_CHECK_ARG(isfinite(lo) && isfinite(hi) && lo < hi, "%s: axis %d: lo=%g, hi=%g must be finite with lo < hi", who, i, (double)lo, (double)hi);
-        const float step = (hi - lo) / (float)res, inv = (float)res / (hi - lo);
-        VG_CHECK_ARG(isfinite(step) && step > 0.0f && isfinite(inv) && inv > 0.0f, "%s: axis %d: the step %g of [%g, %g] / %d is not a positive finite float",
-                     who, i, (double)step, (double)lo, (double)hi, res);
-        g.lo[i] = lo; g.hi[i] = hi; g.inv[i] = inv; g.res[i] = res; g.P[i] = res + 1; g.nb[i] = (res + BLK - 1) / BLK;
-    }
-    *out = g;
-    return MI_VOXGRAD_OK;
+    return grid_ok(set_error, MI_VOXGRAD_MAX_RES, who, grid, out) ? MI_VOXGRAD_OK : MI_VOXGRAD_EINVAL;
 }
-
-static int64_t max_steps_of(const mi_voxgrad_grid* grid, float step) {
-    double s = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        const double e = (double)grid->hi[i] - (double)grid->lo[i];
-        s += e * e;
-    }
-    const double q = ceil(sqrt(s) / (double)step);
-    return q >= 9.0e18 ? INT64_MAX : (int64_t)q + 1;
+static int check_basis(const char* who, int B) { return basis_ok(set_error, who, B) ? MI_VOXGRAD_OK : MI_VOXGRAD_EINVAL; }
+static int check_march(const char* who, const mi_voxgrad_grid* grid, const mi_voxgrad_render_cfg* cfg, int64_t n, int64_t* steps) {
+    return march_ok(set_error, MI_VOXGRAD_MAX_STEPS, who, grid, cfg, n, steps) ? MI_VOXGRAD_OK : MI_VOXGRAD_EINVAL;
 }
 
 }  // namespace mivoxgrad
@@ -348,17 +282,9 @@ int mi_voxgrad_render_backward(const mi_voxgrad_grid* grid, int B, const float* 
     const char* who = "mi_voxgrad_render_backward";
     BackArgs a{};
     if (int rc = check_grid(who, grid, &a.g)) return rc;
-    VG_CHECK_ARG(record_floats(B) != 0, "%s: B=%d: 1, 4 or 9 basis functions", who, B);
-    VG_CHECK_ARG(cfg != nullptr, "%s: cfg is NULL", who);
-    VG_CHECK_ARG(isfinite(cfg->step) && cfg->step > 0.0f, "%s: step=%g must be a positive finite number", who, (double)cfg->step);
-    VG_CHECK_ARG(cfg->t_near < cfg->t_far, "%s: t_near=%g must lie below t_far=%g", who, (double)cfg->t_near, (double)cfg->t_far);
-    VG_CHECK_ARG(cfg->T_min >= 0.0f && cfg->T_min < 1.0f, "%s: T_min=%g: 0 <= T_min < 1", who, (double)cfg->T_min);
-    VG_CHECK_ARG(isfinite(cfg->bg[0]) && isfinite(cfg->bg[1]) && isfinite(cfg->bg[2]), "%s: the background must be finite", who);
-    VG_CHECK_ARG(cfg->use_skip == 0 || cfg->use_skip == 1, "%s: use_skip=%d must be 0 or 1", who, cfg->use_skip);
-    const int64_t steps = max_steps_of(grid, cfg->step);
-    VG_CHECK_ARG(steps <= MI_VOXGRAD_MAX_STEPS, "%s: step=%g gives up to %lld samples per ray, more than %d", who, (double)cfg->step, (long long)steps,
-                 MI_VOXGRAD_MAX_STEPS);
-    VG_CHECK_ARG(n >= 0 && n <= ((int64_t)1 << 31) * RAYS_PER_BLOCK - 1, "%s: n=%lld out of range", who, (long long)n);
+    if (int rc = check_basis(who, B)) return rc;
+    int64_t steps;
+    if (int rc = check_march(who, grid, cfg, n, &steps)) return rc;
     if (n == 0) return MI_VOXGRAD_OK;                                  // no work: the arrays of an empty ray set may be NULL
     VG_CHECK_ARG(sigma_dev && coef_dev && rays_dev && g_rgb_dev && d_sigma_dev && d_coef_dev, "%s: NULL pointer", who);
     VG_CHECK_ARG(aligned(coef_dev, 16) && aligned(d_coef_dev, 16), "%s: coef and d_coef must be 16-byte aligned", who);

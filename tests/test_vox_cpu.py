@@ -72,10 +72,11 @@ def test_the_library_stands_alone_and_is_in_the_build_table(vox):
 
 
 def test_the_source_holds_no_preprocessor_conditional_no_ablation_macro_and_no_atomic():
-    """tests/test_packing_cpu.py allows 14 conditionals in csrc/ and counts 13; this source adds none."""
-    src = open(os.path.join(ROOT, "nerf_pytorch_paeng_amd", "csrc", "vox.hip")).read()
-    assert not re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b", src, re.M) and "MN_" not in src
-    assert not re.findall(r"\batomic[A-Z]|__atomic_|\basm\b", src)
+    """tests/test_packing_cpu.py allows 14 conditionals in csrc/ and counts 13; this source and the header that holds the rule add none."""
+    for name in ("vox.hip", "vox_rule.h"):
+        src = open(os.path.join(ROOT, "nerf_pytorch_paeng_amd", "csrc", name)).read()
+        assert not re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b", src, re.M) and "MN_" not in src, name
+        assert not re.findall(r"\batomic[A-Z]|__atomic_|\basm\b", src), name
 
 
 def test_header_compiles_as_c99_and_the_library_links_and_answers(tmp_path, vox):

@@ -78,10 +78,13 @@ def test_the_library_stands_alone_and_is_in_the_build_table(voxgrad):
 
 
 def test_the_source_holds_no_preprocessor_conditional_no_ablation_macro_and_no_inline_assembly():
-    src = open(os.path.join(ROOT, "nerf_pytorch_paeng_amd", "csrc", "voxgrad.hip")).read()
-    assert not re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b", src, re.M) and "MN_" not in src
-    assert not re.findall(r"\basm\b", src)
+    csrc = os.path.join(ROOT, "nerf_pytorch_paeng_amd", "csrc")
+    src, rule = open(os.path.join(csrc, "voxgrad.hip")).read(), open(os.path.join(csrc, "vox_rule.h")).read()
+    for name, text in (("voxgrad.hip", src), ("vox_rule.h", rule)):
+        assert not re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b", text, re.M) and "MN_" not in text, name
+        assert not re.findall(r"\basm\b", text), name
     assert '#include "../../include/mi_nerf_voxgrad.h"' in src and "mi_nerf_vox.h\"" not in src     # it includes its own header alone
+    assert '#include "vox_rule.h"' in src and not re.findall(r"#\s*include\s*[\"<][^\"<>]*mi_nerf\w*\.h", rule)   # the shared rule knows no public header
 
 
 def test_header_compiles_as_c99_and_the_library_links_and_answers(tmp_path, voxgrad):

@@ -98,6 +98,58 @@ def _interp(w, q):
     return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]))
 
 
+def slab(lo, hi, o, d, t_near, t_far):
+    """Step 1 of the rule for a ray set, in the arithmetic of the arrays passed: (L, t0, t1, miss), each [n]."""
+    dtype = o.dtype.type
+    n = o.shape[0]
+    with np.errstate(all="ignore"):
+        L = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        miss = ~(np.isfinite(o).all(1) & np.isfinite(L)) | (L == 0)
+        entry, exit_ = np.full(n, -np.inf, dtype), np.full(n, np.inf, dtype)
+        for i in range(3):
+            nz = d[:, i] != 0
+            ta, tb = (lo[i] - o[:, i]) / d[:, i], (hi[i] - o[:, i]) / d[:, i]
+            entry = np.where(nz, np.fmax(entry, np.fmin(ta, tb)), entry)
+            exit_ = np.where(nz, np.fmin(exit_, np.fmax(ta, tb)), exit_)
+            miss |= ~nz & ~((lo[i] <= o[:, i]) & (o[:, i] <= hi[i]))
+        t0, t1 = np.fmax(t_near, entry), np.fmin(t_far, exit_)
+        miss |= ~(t1 > t0)
+    return L, t0, t1, miss
+
+
+def samples(k, live, lo, inv, res, o, d, t0, t1, dt):
+    """Interval k of the rays still live: (live, r, ak, bk, mk, c, f) -- the rays whose interval k exists (a_k < t1) as a mask and as
+    indices r, and per such ray the interval's ends and midpoint, the cell c = [c_x, c_y, c_z] and the fractions f of the midpoint."""
+    dtype = o.dtype.type
+    with np.errstate(all="ignore"):
+        ak_all = t0 + dtype(k) * dt
+        live = live & (ak_all < t1)
+    r = np.nonzero(live)[0]
+    ak = ak_all[r]
+    bk = np.fmin(t0[r] + dtype(k + 1) * dt[r], t1[r])
+    mk = dtype(0.5) * (ak + bk)
+    c, f = [], []
+    for i in range(3):
+        p = o[r, i] + mk * d[r, i]
+        g = (p - lo[i]) * inv[i]
+        ci = np.clip(np.floor(g).astype(np.int64), 0, res[i] - 1)
+        c.append(ci)
+        f.append(np.fmin(np.fmax(g - ci.astype(dtype), dtype(0)), dtype(1)))
+    return live, r, ak, bk, mk, c, f
+
+
+def corners(c, f):
+    """The eight corners of the samples' cells, e = e_x + 2 e_y + 4 e_z: weights w[e] and index triples at[e] = (z, y, x)."""
+    one = f[0].dtype.type(1)
+    w, at = [], []
+    for e in range(8):
+        ex, ey, ez = e & 1, (e >> 1) & 1, e >> 2
+        wx, wy, wz = (f[0] if ex else one - f[0]), (f[1] if ey else one - f[1]), (f[2] if ez else one - f[2])
+        w.append((wx * wy) * wz)
+        at.append((c[2] + ez, c[1] + ey, c[0] + ex))
+    return w, at
+
+
 def render(lo, hi, res, B, sigma, coef, rays, step, t_near, t_far, T_min=0.0, bg=(1.0, 1.0, 1.0), dtype=np.float64):
     """THE RENDER RULE of the header without skipping (skipping changes no output but `visited`).  Returns a dict: rgb [n,3], disp, acc,
     depth [n], and samples [n], the number of samples the ray evaluated (`visited` with use_skip = 0)."""
@@ -113,50 +165,22 @@ def render(lo, hi, res, B, sigma, coef, rays, step, t_near, t_far, T_min=0.0, bg
     cap = max_steps(lo, hi, step)
     n = rays.shape[0]
     o, d = rays[:, :3], rays[:, 3:]
+    L, t0, t1, miss = slab(lo, hi, o, d, t_near, t_far)
     with np.errstate(all="ignore"):
-        L = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
-        miss = ~(np.isfinite(o).all(1) & np.isfinite(L)) | (L == 0)
-        entry, exit_ = np.full(n, -np.inf, dtype), np.full(n, np.inf, dtype)
-        for i in range(3):
-            nz = d[:, i] != 0
-            ta, tb = (lo[i] - o[:, i]) / d[:, i], (hi[i] - o[:, i]) / d[:, i]
-            entry = np.where(nz, np.fmax(entry, np.fmin(ta, tb)), entry)
-            exit_ = np.where(nz, np.fmin(exit_, np.fmax(ta, tb)), exit_)
-            miss |= ~nz & ~((lo[i] <= o[:, i]) & (o[:, i] <= hi[i]))
-        t0, t1 = np.fmax(t_near, entry), np.fmin(t_far, exit_)
-        miss |= ~(t1 > t0)
         dt = step / L
         Y = sh_basis(d / L[:, None], B, dtype)
     rgb, acc, depth = np.zeros((n, 3), dtype), np.zeros(n, dtype), np.zeros(n, dtype)
     T = np.ones(n, dtype)
-    samples = np.zeros(n, np.int64)
+    visited = np.zeros(n, np.int64)
     live = ~miss
-    half, one, zero = dtype(0.5), dtype(1), dtype(0)
+    one, zero = dtype(1), dtype(0)
     for k in range(cap):
-        with np.errstate(all="ignore"):
-            ak_all = t0 + dtype(k) * dt
-            live = live & (ak_all < t1)
-        r = np.nonzero(live)[0]
+        live, r, ak, bk, mk, c, f = samples(k, live, lo, inv, res, o, d, t0, t1, dt)
         if r.size == 0:
             break
-        ak = ak_all[r]
-        bk = np.fmin(t0[r] + dtype(k + 1) * dt[r], t1[r])
-        mk = half * (ak + bk)
         delta = (bk - ak) * L[r]
-        c, f = [], []
-        for i in range(3):
-            p = o[r, i] + mk * d[r, i]
-            g = (p - lo[i]) * inv[i]
-            ci = np.clip(np.floor(g).astype(np.int64), 0, res[i] - 1)
-            c.append(ci)
-            f.append(np.fmin(np.fmax(g - ci.astype(dtype), zero), one))
-        w, s_e, at = [], [], []
-        for e in range(8):
-            ex, ey, ez = e & 1, (e >> 1) & 1, e >> 2
-            wx, wy, wz = (f[0] if ex else one - f[0]), (f[1] if ey else one - f[1]), (f[2] if ez else one - f[2])
-            w.append((wx * wy) * wz)
-            at.append((c[2] + ez, c[1] + ey, c[0] + ex))
-            s_e.append(sigma[at[e]])
+        w, at = corners(c, f)
+        s_e = [sigma[a] for a in at]
         sigma_s = _interp(w, s_e)
         alpha = one - np.exp(-(sigma_s * delta))
         wt = T[r] * alpha
@@ -177,7 +201,7 @@ def render(lo, hi, res, B, sigma, coef, rays, step, t_near, t_far, T_min=0.0, bg
         acc[r] = acc[r] + wt
         depth[r] = depth[r] + wt * mk
         T[r] = T[r] * (one - alpha)
-        samples[r] += 1
+        visited[r] += 1
         live[r] = ~(T[r] < T_min)
     rgb = rgb + (one - acc)[:, None] * bg[None, :]
     with np.errstate(all="ignore"):
@@ -186,4 +210,4 @@ def render(lo, hi, res, B, sigma, coef, rays, step, t_near, t_far, T_min=0.0, bg
         disp = one / m
         disp = np.where(np.isnan(disp), zero, disp)
         disp = np.where(disp > dtype(5), dtype(5), disp)
-    return {"rgb": rgb, "disp": disp, "acc": acc, "depth": depth, "samples": samples}
+    return {"rgb": rgb, "disp": disp, "acc": acc, "depth": depth, "samples": visited}

@@ -45,18 +45,8 @@ def backward(lo, hi, res, B, sigma, coef, rays, step, t_near, t_far, G, ga=None,
     step, t_near, t_far, T_min = dtype(f32(step)), dtype(f32(t_near)), dtype(f32(t_far)), dtype(f32(T_min))
     cap = VR.max_steps(lo, hi, step)
     o, d = rays[:, :3], rays[:, 3:]
+    L, t0, t1, miss = VR.slab(lo, hi, o, d, t_near, t_far)
     with np.errstate(all="ignore"):
-        L = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
-        miss = ~(np.isfinite(o).all(1) & np.isfinite(L)) | (L == 0)
-        entry, exit_ = np.full(n, -np.inf, dtype), np.full(n, np.inf, dtype)
-        for i in range(3):
-            nz = d[:, i] != 0
-            ta, tb = (lo[i] - o[:, i]) / d[:, i], (hi[i] - o[:, i]) / d[:, i]
-            entry = np.where(nz, np.fmax(entry, np.fmin(ta, tb)), entry)
-            exit_ = np.where(nz, np.fmin(exit_, np.fmax(ta, tb)), exit_)
-            miss |= ~nz & ~((lo[i] <= o[:, i]) & (o[:, i] <= hi[i]))
-        t0, t1 = np.fmax(t_near, entry), np.fmin(t_far, exit_)
-        miss |= ~(t1 > t0)
         dt = step / L
         Y = VR.sh_basis(d / L[:, None], B, dtype)
     gap = ga - ((G[:, 0] * bg[0] + G[:, 1] * bg[1]) + G[:, 2] * bg[2])            # the effective gradient of acc
@@ -65,27 +55,14 @@ def backward(lo, hi, res, B, sigma, coef, rays, step, t_near, t_far, G, ga=None,
     S = np.zeros(n, dtype)
     samples = np.zeros(n, np.int64)
     live = ~miss
-    half, one, zero = dtype(0.5), dtype(1), dtype(0)
+    one, zero = dtype(1), dtype(0)
     qdist_w = qdist_all = np.inf
     kept = []                                                                    # what the second pass needs of every sample
     # ---- the forward, and S ---------------------------------------------------------------------------
     for k in range(cap):
-        with np.errstate(all="ignore"):
-            ak_all = t0 + dtype(k) * dt
-            live = live & (ak_all < t1)
-        r = np.nonzero(live)[0]
+        live, r, ak, bk, mk, c, f = VR.samples(k, live, lo, inv, res, o, d, t0, t1, dt)
         if r.size == 0:
             break
-        ak = ak_all[r]
-        bk = np.fmin(t0[r] + dtype(k + 1) * dt[r], t1[r])
-        mk = half * (ak + bk)
-        c, f = [], []
-        for i in range(3):
-            p = o[r, i] + mk * d[r, i]
-            g = (p - lo[i]) * inv[i]
-            ci = np.clip(np.floor(g).astype(np.int64), 0, res[i] - 1)
-            c.append(ci)
-            f.append(np.fmin(np.fmax(g - ci.astype(dtype), zero), one))
         if skip is not None:                                                     # a sample whose cell's block byte is 0 contributes nothing
             keep = np.asarray(skip)[c[2] >> 3, c[1] >> 3, c[0] >> 3] != 0
             r, ak, bk, mk = r[keep], ak[keep], bk[keep], mk[keep]
@@ -93,12 +70,7 @@ def backward(lo, hi, res, B, sigma, coef, rays, step, t_near, t_far, G, ga=None,
             if r.size == 0:
                 continue
         delta = (bk - ak) * L[r]
-        w, at = [], []
-        for e in range(8):
-            ex, ey, ez = e & 1, (e >> 1) & 1, e >> 2
-            wx, wy, wz = (f[0] if ex else one - f[0]), (f[1] if ey else one - f[1]), (f[2] if ez else one - f[2])
-            w.append((wx * wy) * wz)
-            at.append((c[2] + ez, c[1] + ey, c[0] + ex))
+        w, at = VR.corners(c, f)
         sigma_s = VR._interp(w, [sigma[a] for a in at])
         alpha = one - np.exp(-(sigma_s * delta))
         wt = T[r] * alpha
