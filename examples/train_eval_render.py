@@ -5,7 +5,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10] [--mesh-view]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
-                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS]]
+                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY]]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -22,7 +22,9 @@ none of the three the run is what it was.  ``--bake RES[:B[:dense|sparse|sparse1
 density and B = 1, 4 or 9 spherical-harmonic colour coefficients, default 9, on a (RES + 1)^3 lattice of the box +-``--mesh-box``), the video poses
 are rendered from the grid as well, with no network, and the PSNR of the grid's frames against the network's and both times are printed.
 ``--bake-finetune STEPS`` (dense storage): the baked grid is then fine-tuned on the training views' rays for STEPS steps
-(baked_train.finetune: the backward pass of the grid renderer) and its PSNR on the test views is printed before and after.
+(baked_train.finetune: the backward pass of the grid renderer) and its PSNR on the test views is printed before and after;
+``--bake-reg TV_SIGMA:TV_COEF:SPARSITY`` adds the lattice regularisers to those steps (total variation of the density plane and of the
+records, Cauchy sparsity of the density; e.g. 0.01:0.01:0.01) and is refused without ``--bake-finetune``.
 """
 import argparse
 import os
@@ -62,6 +64,8 @@ def main(argv=None):
                     help="bake the fine network into a radiance grid and render the video from it too; STORAGE: dense (default), sparse or sparse16 (records of active points only, fp32 or f16)")
     ap.add_argument("--lpips", default=None, metavar="VGG_PTH:LIN_PTH", help="also report LPIPS: a torchvision vgg16 state dict and the lpips package's linear layers, two files for torch.load")
     ap.add_argument("--bake-finetune", type=int, default=0, metavar="STEPS", help="after --bake (dense), fine-tune the grid on the training views for STEPS steps")
+    ap.add_argument("--bake-reg", default=None, metavar="TV_SIGMA:TV_COEF:SPARSITY",
+                    help="with --bake-finetune: weights of the total variation of the density plane and of the records and of the density's sparsity prior")
     a = ap.parse_args(argv)
     if a.warmup is not None and not 0 <= a.warmup < a.steps:
         ap.error("--warmup takes a number of steps below --steps")
@@ -71,6 +75,17 @@ def main(argv=None):
     bake_storage = "dense"
     if a.bake_finetune and (a.bake is None or len(a.bake.split(":")) > 2 and a.bake.split(":")[2] != "dense"):
         ap.error("--bake-finetune needs --bake with dense storage (fine-tune dense, then compact)")
+    bake_reg = {}
+    if a.bake_reg is not None:
+        if not a.bake_finetune:
+            ap.error("--bake-reg weighs the regularisers of --bake-finetune STEPS: give both")
+        try:
+            w_tvs, w_tvc, w_sp = (float(v) for v in a.bake_reg.split(":"))
+        except ValueError:
+            ap.error("--bake-reg takes TV_SIGMA:TV_COEF:SPARSITY, three numbers")
+        if not all(np.isfinite(w) and w >= 0 for w in (w_tvs, w_tvc, w_sp)):
+            ap.error("--bake-reg takes three non-negative numbers")
+        bake_reg = {"tv_sigma": w_tvs, "tv_coef": w_tvc, "sparsity": w_sp}
     if a.bake is not None:
         fields = a.bake.split(":")
         try:
@@ -212,9 +227,12 @@ def main(argv=None):
 
             before = grid_psnr()
             t_ft = time.perf_counter()
-            losses = baked_train.finetune(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), a.bake_finetune)
+            losses = baked_train.finetune(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), a.bake_finetune, **bake_reg)
             torch.cuda.synchronize()
             t_ft = time.perf_counter() - t_ft
+            if bake_reg:
+                print(f"bake-reg: {bake_reg}; TV(sigma) {float(baked_train.lattice_tv(grid)):.4g}, TV(coef) {float(baked_train.lattice_tv(grid, 'coef')):.4g}, "
+                      f"SP {float(baked_train.lattice_sparsity(grid)):.4g} after the steps")
             print(f"bake-finetune: {a.bake_finetune} steps in {t_ft:.2f} s, batch loss {float(losses[0]):.5f} -> {float(losses[-1]):.5f}; the grid's PSNR on the test "
                   f"views {['%.2f' % p for p in before]} -> {['%.2f' % p for p in grid_psnr()]} dB")
     if a.mesh:

@@ -3,10 +3,14 @@
     grid = baked.RadianceGrid(-1.2, 1.2, 128, B=9).bake(model)           # or .allocate(dev): an empty grid, trained from nothing (skip=False)
     losses = baked_train.finetune(grid, rays, target, steps=300)         # Adam on sigma and coef against the images' rgb
     rgb, disp, acc, depth = baked_train.render(grid, rays)               # one autograd node, for a loss of one's own
+    tv = baked_train.lattice_tv(grid, "sigma", mask=True, scale=1e-4)    # the priors a grid trained from nothing wants: total variation and
+    sp = baked_train.lattice_sparsity(grid, scale=1e-4)                  # Cauchy sparsity, value returned, gradient ADDED into .grad
 
 The forward is ``grid.render`` (libmi_nerf_vox.so); the backward is mi_voxgrad_render_backward, which recomputes the march and ADDS
 dL/d sigma and dL/d coef by THE BACKWARD RULE of the header.  Its sums are fp32 hardware atomic adds: unlike every other entry of the
-package, the gradient is not bit-identical from run to run (docs/design/23_radiance_grid_training.md).  Dense fp32 grids only; there is no
+package, the gradient is not bit-identical from run to run (docs/design/23_radiance_grid_training.md).  The regularisers are THE LATTICE
+REGULARISERS of include/mi_nerf_geo.h (libmi_nerf_geo.so): gathers without an atomic, bit-identical from run to run
+(docs/design/24_lattice_regularisers.md).  Dense fp32 grids only; there is no
 fallback: a missing library or a failed call raises ``MiNerfError``.
 """
 from __future__ import annotations
@@ -17,12 +21,12 @@ from typing import Optional
 
 import torch
 
-from . import _voxgrad, ops
+from . import _geo, _voxgrad, ops
 from ._lib import MiNerfError, dev_ptr, stream_ptr
 from .baked import RadianceGrid, SparseRadianceGrid
 
 
-def _check(grid, rays) -> torch.device:
+def _check_grid(grid) -> torch.device:
     if isinstance(grid, SparseRadianceGrid):
         raise MiNerfError("a SparseRadianceGrid has no dense record array to differentiate: fine-tune the dense grid, then compact()")
     if not isinstance(grid, RadianceGrid):
@@ -31,6 +35,11 @@ def _check(grid, rays) -> torch.device:
     dev = grid.sigma.device
     if dev.type != "cuda":
         raise MiNerfError(f"the grid must live on a HIP device (got {dev}); this path has no CPU fallback")
+    return dev
+
+
+def _check(grid, rays) -> torch.device:
+    dev = _check_grid(grid)
     if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
         raise MiNerfError(f"rays [n,6] expected, got {tuple(rays.shape) if isinstance(rays, torch.Tensor) else type(rays).__name__}")
     if rays.device != dev:
@@ -100,9 +109,77 @@ def render(grid: RadianceGrid, rays: torch.Tensor, step: Optional[float] = None,
     return _Render.apply(grid.sigma, grid.coef, grid, rays.detach().contiguous(), kw)
 
 
+# ---------------------------------------------------------------------------------------------------
+# THE LATTICE REGULARISERS (include/mi_nerf_geo.h)
+# ---------------------------------------------------------------------------------------------------
+def _lattice(grid: RadianceGrid, kind: str, which: str, eps: float, mask, scale: Optional[float], out: Optional[torch.Tensor], value: bool):
+    """One call of mi_geo_lattice_tv / mi_geo_lattice_sparsity on ``grid.sigma`` or ``grid.coef``: the gradient is added when ``scale`` is
+    given, the value is formed (and returned) when ``value``."""
+    dev = _check_grid(grid)
+    if which not in ("sigma", "coef") or (kind == "sparsity" and which != "sigma"):
+        raise MiNerfError(f"which={which!r}: 'sigma' or 'coef' expected (the sparsity prior is on sigma alone)")
+    v = (grid.sigma if which == "sigma" else grid.coef).detach()
+    R, Cn = (1, 1) if which == "sigma" else (grid.record_floats, 3 * grid.B)
+    align = 4 if R == 1 else 16
+    if mask is True:
+        mask = grid.skip
+    elif mask is False:
+        mask = None
+    if mask is not None and (not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(grid.skip_shape) or mask.device != dev):
+        raise MiNerfError(f"mask: None, True (the grid's skip plane) or a uint8 tensor {tuple(grid.skip_shape)} on {dev} expected")
+    grad = None
+    if scale is not None:
+        owner = grid.sigma if which == "sigma" else grid.coef
+        if out is None:
+            if owner.grad is None:
+                owner.grad = torch.zeros_like(owner)
+            out = owner.grad
+        if not isinstance(out, torch.Tensor) or out.shape != v.shape:
+            raise MiNerfError(f"out {tuple(v.shape)} expected, got {tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__}")
+        grad = out
+    elif out is not None:
+        raise MiNerfError("out is given without a scale: nothing would be added to it")
+    P = (C.c_int32 * 3)(*grid.points)
+    L = _geo.lib()
+    val = scratch = None
+    nbytes = 0
+    if value:
+        nbytes = int(L.mi_geo_lattice_scratch_bytes(P, R, Cn))
+        if nbytes == 0:
+            raise MiNerfError(f"the lattice {grid.points} x {R} is refused by mi_geo_lattice_scratch_bytes")
+        val = torch.empty((), dtype=torch.float64, device=dev)
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    sc = 0.0 if scale is None else float(scale)
+    with ops._guard(dev):
+        if kind == "tv":
+            _geo.check(L.mi_geo_lattice_tv(P, R, Cn, dev_ptr(v, which, torch.float32, align), dev_ptr(mask, "mask", torch.uint8, 1), float(eps), sc,
+                                           dev_ptr(grad, "out", torch.float32, align), dev_ptr(val, "value", torch.float64, 8),
+                                           dev_ptr(scratch, "scratch", torch.float64, 8), nbytes, stream_ptr(dev)), "mi_geo_lattice_tv")
+        else:
+            _geo.check(L.mi_geo_lattice_sparsity(P, dev_ptr(v, which), dev_ptr(mask, "mask", torch.uint8, 1), sc, dev_ptr(grad, "out"),
+                                                 dev_ptr(val, "value", torch.float64, 8), dev_ptr(scratch, "scratch", torch.float64, 8), nbytes,
+                                                 stream_ptr(dev)), "mi_geo_lattice_sparsity")
+    return val
+
+
+def lattice_tv(grid: RadianceGrid, which: str = "sigma", eps: float = 1e-8, mask=None, scale: Optional[float] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mi_geo_lattice_tv on ``grid.sigma`` (``which="sigma"``) or on the 3 B counted floats of ``grid.coef`` (``"coef"``): the total
+    variation as a 0-dim float64 device tensor.  With ``scale`` the gradient times ``scale`` is ADDED into ``out`` (default: the tensor's
+    ``.grad``, created as zeros if absent).  ``mask``: None (every point counts), True (``grid.skip``) or a uint8 tensor of its shape."""
+    return _lattice(grid, "tv", which, eps, mask, scale, out, True)
+
+
+def lattice_sparsity(grid: RadianceGrid, mask=None, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mi_geo_lattice_sparsity on ``grid.sigma``: sum of log1p(2 sigma^2) over the counted points, as a 0-dim float64 device tensor; with
+    ``scale`` the gradient times ``scale`` is ADDED into ``out`` (default ``grid.sigma.grad``).  ``mask`` as for ``lattice_tv``."""
+    return _lattice(grid, "sparsity", "sigma", 0.0, mask, scale, out, True)
+
+
 def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps: int, batch: int = 4096, lr_sigma: float = 0.05, lr_coef: float = 0.005,
              optimizer=torch.optim.Adam, rebuild_skip_every: int = 1, seed: int = 0, step: Optional[float] = None, near: float = 0.0,
-             far: float = math.inf, T_min: float = 0.0, bg=(1.0, 1.0, 1.0), skip: bool = True) -> torch.Tensor:
+             far: float = math.inf, T_min: float = 0.0, bg=(1.0, 1.0, 1.0), skip: bool = True, tv_sigma: float = 0.0, tv_coef: float = 0.0,
+             sparsity: float = 0.0, tv_eps: float = 1e-8) -> torch.Tensor:
     """``steps`` optimiser steps on ``grid.sigma`` (lr_sigma) and ``grid.coef`` (lr_coef) against target [N,3], the rgb of rays [N,6]: a
     seeded batch of ``batch`` rays drawn on the device per step, the mean squared error on rgb, and ``sigma.clamp_(min=0)`` after every
     step.  Returns the per-step losses [steps] as a device tensor: nothing synchronises with the host.
@@ -115,13 +192,22 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
 
     The default rates suit a baked grid: the colours move, the density barely does.  Adam steps every touched element by about its rate
     whatever the gradient's size, so a large ``lr_sigma`` on small batches fills the empty space next to surfaces with noise (measured in
-    docs/design/23_radiance_grid_training.md, with the gain from larger batches); a grid trained from nothing wants a larger one."""
+    docs/design/23_radiance_grid_training.md, with the gain from larger batches); a grid trained from nothing wants a larger one.
+
+    ``tv_sigma``, ``tv_coef``, ``sparsity`` (>= 0) weigh THE LATTICE REGULARISERS: between ``loss.backward()`` and the optimiser's step the
+    gradients of ``tv_sigma TV(sigma) / N``, ``tv_coef TV(coef) / (N 3 B)`` and ``sparsity SP / N`` are added, N the number of lattice
+    points (known on the host: nothing synchronises), ``tv_eps`` the eps of the total variation.  Their mask is ``grid.skip`` on the steps that
+    render with the plane and none otherwise.  The returned losses stay the data loss; with all three weights 0 no regulariser is
+    called."""
+    if not all(isinstance(w, (int, float)) and math.isfinite(w) and w >= 0 for w in (tv_sigma, tv_coef, sparsity)):
+        raise MiNerfError(f"tv_sigma={tv_sigma}, tv_coef={tv_coef} and sparsity={sparsity} must be finite numbers >= 0")
     dev = _check(grid, rays)
     N = rays.shape[0]
     if not isinstance(target, torch.Tensor) or tuple(target.shape) != (N, 3) or target.device != dev:
         raise MiNerfError(f"target [{N},3] on {dev} expected")
     if steps < 0 or batch < 1 or rebuild_skip_every < 1:
         raise MiNerfError(f"steps={steps} >= 0, batch={batch} >= 1 and rebuild_skip_every={rebuild_skip_every} >= 1 expected")
+    n_points = grid.points[0] * grid.points[1] * grid.points[2]
     rays, target = rays.detach().float().contiguous(), target.detach().float()
     gen = torch.Generator(device=dev).manual_seed(int(seed))
     was = (grid.sigma.requires_grad, grid.coef.requires_grad)
@@ -139,6 +225,14 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
             loss = torch.mean((rgb - target[idx]) ** 2)
             opt.zero_grad(set_to_none=False)
             loss.backward()
+            if tv_sigma or tv_coef or sparsity:
+                plane = True if skip and fresh else None
+                if tv_sigma:
+                    _lattice(grid, "tv", "sigma", tv_eps, plane, tv_sigma / n_points, None, False)
+                if tv_coef:
+                    _lattice(grid, "tv", "coef", tv_eps, plane, tv_coef / (n_points * 3 * grid.B), None, False)
+                if sparsity:
+                    _lattice(grid, "sparsity", "sigma", 0.0, plane, sparsity / n_points, None, False)
             opt.step()
             with torch.no_grad():
                 grid.sigma.clamp_(min=0.0)

@@ -8,7 +8,8 @@
 LIBRARIES has one record per library: its name ("" is libmi_nerf.so itself), its sources, its extra link arguments, and whether libmi_nerf.so
 is built first because the library links against it (rpath $ORIGIN).  _build() builds any record; the build_*_library names bind to it.
 occ and mesh link against libmi_nerf.so; mesh is two translation units (mesh.hip: extraction, which calls the fused network entries;
-mesh_view.hip: the rasteriser, which calls nothing of libmi_nerf.so); the other libraries (voxgrad, the radiance grid's
+mesh_view.hip: the rasteriser, which calls nothing of libmi_nerf.so); geo is two as well (geo.hip: the compositing pair; lattice_reg.hip: the grid
+regularisers); the other libraries (voxgrad, the radiance grid's
 backward pass, among them) link against none of the project's.
 
 What lands where:
@@ -53,7 +54,7 @@ LIBRARIES = {
     "occ": (["occ.hip"], LINK_NERF, True),
     "scene": (["scene.hip"], [], False),
     "mesh": (["mesh.hip", "mesh_view.hip"], LINK_NERF, True),
-    "geo": (["geo.hip"], [], False),
+    "geo": (["geo.hip", "lattice_reg.hip"], [], False),
     "pose": (["pose.hip"], [], False),
     "optim": (["optim.hip"], [], False),
     "lpips": (["lpips.hip"], [], False),

@@ -25,8 +25,8 @@ using minerf::wave_excl_suffix_sum;
 using minerf::wave_excl_sum;
 using minerf::wave_sum;
 
-// ---- error plumbing (abi_error.h) ----------------------------------------------------------------------
-ABI_ERROR_STATE(static, MI_GEO_EHIP)
+// ---- error plumbing (abi_error.h): the library's one buffer; lattice_reg.hip reaches set_error / hip_fail, which the library does not export
+ABI_ERROR_STATE(__attribute__((visibility("hidden"))), MI_GEO_EHIP)
 #define GEO_CHECK_ARG(cond, ...) ABI_CHECK_ARG(::migeo, MI_GEO_EINVAL, cond, __VA_ARGS__)
 #define GEO_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::migeo, name)
 
