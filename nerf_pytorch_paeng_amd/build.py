@@ -16,7 +16,8 @@ What lands where:
   nerf_pytorch_paeng_amd/libmi_nerf[_NAME].so (+ .stamp)   the shipped libraries: the only artefacts inside the package, git-ignored, copied with the tree
         to a GPU box.  A stamp hashes the library's sources, EVERY header under csrc/ and include/, the flags and the link arguments; the library is
         up to date iff the stamp matches (no mtimes, no objects needed -- the GPU box gets neither).  Every header for every library: the one rule
-        that cannot miss a header reached through another (csrc/abi_error.h is in all eleven, csrc/vox_rule.h in vox and voxgrad); a one-file library is rebuilt a few seconds too often.
+        that cannot miss a header reached through another (csrc/abi_error.h is in all eleven, csrc/vox_rule.h in vox and voxgrad, csrc/block_scan.h in
+        mesh, occ, vox, iqa and libmi_nerf.so's frames.hip, csrc/row_slab.h in occ and mesh); a one-file library is rebuilt a few seconds too often.
   build_scratch/obj/                                objects of the shipped libraries (cache; tests/test_packing_cpu.py disassembles them)
   build_scratch/obj_TAG/, build_scratch/libmi_nerf_TAG.so    variants of libmi_nerf.so.  build_scratch/ is git-ignored and is not copied: a variant is
         built where it is used (tools/ab_probe.py builds the ones it is asked for on the box).

@@ -11,10 +11,18 @@
 // Each library keeps a buffer of its own.  A one-file library passes `static`: the buffer and both functions have internal linkage and the
 // library exports nothing but the names of its header.  libmi_nerf.so passes nothing: api.hip holds the one buffer, and its other
 // translation units reach set_error / hip_fail through the declarations in common.h.
+//
+// Being the one header every library includes, it also holds the two size helpers of every host side: align256 and blocks_for.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
+
+// a region of a scratch or workspace starts on a 256-byte boundary
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// blocks of `per_block` items that cover n
+static inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 #define ABI_ERROR_STATE(linkage, ehip)                                                \
     static thread_local char g_err[768] = "";                                         \

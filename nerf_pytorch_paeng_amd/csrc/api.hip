@@ -111,8 +111,6 @@ static int mlp_rays_family(Family family, const mi_nerf_net* net, const void* pa
     return (family == Family::F16 ? mlp_rays_f16 : mlp_rays_bf16)(net, packed, rays, z, n, S, raw, st, points_per_wave, strat, fine);
 }
 
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static int workspace_layout(const mi_nerf_render_cfg* cfg, int64_t n, mi_nerf_workspace_layout* L) {
     MN_CHECK_ARG(cfg && L, "NULL cfg/layout");
     MN_CHECK_ARG(n >= 0 && cfg->Sc >= 1 && cfg->Nf >= 0, "bad sizes n=%lld Sc=%d Nf=%d", (long long)n, cfg->Sc, cfg->Nf);

@@ -15,9 +15,6 @@ int hip_fail(hipError_t e, const char* what);
 #define MN_HIP(call) ABI_HIP(::minerf, call, #call)
 #define MN_LAUNCH_CHECK(name) ABI_LAUNCH_CHECK(::minerf, name)
 
-// blocks of `per_block` items that cover n
-static inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 // Per-DEVICE launch state (a process may drive several GPUs: the 160 KB dynamic-LDS opt-in is an attribute of the function ON a
 // device, and the CU count is a property of the device): small arrays indexed by the current device ordinal.
 // The entry points are re-entrant per stream and callable from several host threads: the only state the library keeps between calls are

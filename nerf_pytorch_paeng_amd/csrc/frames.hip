@@ -6,22 +6,12 @@
 //   permute_rows    np.random.shuffle(rays_rgb)   main.py:102, utils.py:47-52 (gather by a permutation)
 // All HBM-bound streaming kernels: one pass, coalesced, grid-stride; reductions are two-stage and deterministic.
 #include "common.h"
+#include "block_scan.h"
 
 namespace minerf {
 
 constexpr int RED_BLOCKS = 1024;
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += sh[i];
-    return s;                                   // valid on thread 0
-}
+using miblock::block_sum;                       // fp64, fixed order; valid on thread 0
 
 __global__ __launch_bounds__(256) void sqerr_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n,
                                                              double* __restrict__ partial) {

@@ -18,7 +18,6 @@
 
 namespace migeo {
 
-using minerf::blocks_for;
 using minerf::f32x4;
 using minerf::wave_excl_prod;
 using minerf::wave_excl_suffix_sum;

@@ -13,6 +13,7 @@
 #include <math.h>
 #include "../../include/mi_nerf_iqa.h"
 #include "abi_error.h"
+#include "block_scan.h"
 
 namespace miiqa {
 
@@ -54,17 +55,7 @@ struct Geom {
     int tiles_x, tiles_y;
 };
 
-// deterministic block sum in fp64 (frames.hip: block_sum), NT / 64 waves; valid on thread 0
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += sh[i];
-    return s;
-}
+using miblock::block_sum;                    // deterministic block sum in fp64, NT / 64 waves; valid on thread 0
 
 // one pooled pixel-channel of frame `img` (f == 1: the pixel itself); fixed summation order, fp64 sum, rounded to fp32 like a pooled image
 __device__ __forceinline__ float pooled_at(const float* __restrict__ img, const Geom& G, int pr, int px, int ch) {

@@ -2,10 +2,11 @@
 // each cell.  A library of its own: it links against libmi_nerf.so and reaches the networks through the three public fused entries only.
 //
 // mesh_rows_kernel     a slab of lattice rows along x as rays (origin on the box face, direction +x) with depths
-// mesh_density_kernel  channel 3 of raw [rows, P_x, 4] -> f
+// mesh_density_kernel  channel 3 of raw [rows, P_x, 4] -> f (the slab loop around the two: row_slab.h)
 // mesh_mark_kernel     one thread per lattice point: the crossed-edge mask (7 bits) and its popcount
 // mesh_cells_kernel    one thread per cell: the number of triangles of its six tetrahedra
 // scan_*_kernel        exclusive prefix sum of a uint32 array in place: block sums | one block over the block sums (+ the total) | apply
+//                      (the bodies of block_scan.h)
 // mesh_verts_kernel    one thread per lattice point: the vertices (and normals) of its crossed edges
 // mesh_tris_kernel     one thread per cell: its triangles, vertex numbers looked up through mask + vfirst
 //
@@ -15,6 +16,8 @@
 #include <math.h>
 #include "../../include/mi_nerf_mesh.h"
 #include "abi_error.h"
+#include "block_scan.h"
+#include "row_slab.h"
 
 namespace mimesh {
 
@@ -26,8 +29,7 @@ ABI_NERF_FAIL(MI_MESH_EINVAL, MI_MESH_EHIP)
 #define MESH_NERF(call) ABI_NERF(::mimesh, call, #call)
 
 constexpr int SCAN_TILE = MI_MESH_SCAN_TILE;          // 256 threads x 4 elements
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-static inline unsigned blocks_for(long long n, int per) { return (unsigned)((n + per - 1) / per); }
+static_assert(SCAN_TILE == miblock::SCAN_TILE, "block_scan.h and mi_nerf_mesh.h disagree on the scan's block");
 
 // ---- the lattice as the kernels see it ---------------------------------------------------------------
 struct Lattice {
@@ -201,81 +203,20 @@ __global__ __launch_bounds__(256) void mesh_cells_kernel(Lattice L, const float*
     tcount[c] = n;
 }
 
-// exclusive scan of one value per thread over a block of NT threads; *total = the block's sum.  lds: NT / 64 + 1 words.
-template <int NT>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* total, uint32_t* lds) {
-    constexpr int NW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(x, d, 64);
-        if (lane >= d) x += t;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int w = 0; w < NW; ++w) {
-            const uint32_t s = lds[w];
-            lds[w] = run;
-            run += s;
-        }
-        lds[NW] = run;
-    }
-    __syncthreads();
-    const uint32_t r = x - v + lds[wave];
-    *total = lds[NW];
-    __syncthreads();                                                     // lds is reused by the caller's next round
-    return r;
-}
-
+// the scan's three launches (block_scan.h), on uint32
 __global__ __launch_bounds__(256) void scan_reduce_kernel(const uint32_t* __restrict__ data, long long n, uint32_t* __restrict__ bsum) {
-    __shared__ uint32_t lds[4];
-    const long long base = (long long)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (base + k < n) s += data[base + k];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+    miblock::scan_reduce(data, n, bsum);
 }
 
 // one block: block sums -> their exclusive prefix sums in place, the grand total to *total (the totals stay below 2^32: at most 7 vertices
 // per point and 12 triangles per cell of a 513^3 lattice)
 __global__ __launch_bounds__(1024) void scan_sums_kernel(uint32_t* __restrict__ bsum, int nb, unsigned long long* __restrict__ total) {
-    __shared__ uint32_t lds[17];
-    uint32_t carry = 0;
-    for (int c = 0; c < nb; c += 1024) {
-        const int i = c + (int)threadIdx.x;
-        const uint32_t v = i < nb ? bsum[i] : 0u;
-        uint32_t sum;
-        const uint32_t ex = block_exclusive_scan<1024>(v, &sum, lds);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += sum;
-    }
+    const uint32_t carry = miblock::scan_sums(bsum, nb);
     if (threadIdx.x == 0) *total = carry;
 }
 
 __global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t* __restrict__ data, long long n, const uint32_t* __restrict__ bsum) {
-    __shared__ uint32_t lds[5];
-    const long long base = (long long)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
-    uint32_t v[4], s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = base + k < n ? data[base + k] : 0u;
-        s += v[k];
-    }
-    uint32_t sum;
-    uint32_t run = bsum[blockIdx.x] + block_exclusive_scan<256>(s, &sum, lds);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (base + k < n) data[base + k] = run;
-        run += v[k];
-    }
+    miblock::scan_apply(data, n, bsum);
 }
 
 // ---- emit --------------------------------------------------------------------------------------------
@@ -372,55 +313,31 @@ __global__ __launch_bounds__(256) void mesh_tris_kernel(Lattice L, const float* 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-static inline size_t slab_bytes(long long R, int Px) { return align256((size_t)R * 24) + align256((size_t)R * Px * 4) + align256((size_t)R * Px * 16); }
-static inline long long min_rows(const Lattice& L) {
-    const long long rows = (long long)L.P[1] * L.P[2];
-    const long long want = (MI_MESH_MIN_SLAB_POINTS + L.P[0] - 1) / L.P[0];
-    return want < rows ? want : rows;
-}
-
-typedef int (*mlp_rays_fn)(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, void*);
-static int mlp_entry(int mode, mlp_rays_fn* fn) {
-    switch (mode) {
-        case MI_NERF_MODE_F32:  *fn = mi_nerf_mlp_rays; return MI_MESH_OK;
-        case MI_NERF_MODE_F16S: *fn = mi_nerf_mlp_rays_f16s; return MI_MESH_OK;
-        case MI_NERF_MODE_BF16: *fn = mi_nerf_mlp_rays_bf16; return MI_MESH_OK;
-    }
-    set_error("mode %d: the density lattice runs MI_NERF_MODE_F32 (0), MI_NERF_MODE_BF16 (1) and MI_NERF_MODE_F16S (5)", mode);
-    return MI_MESH_EINVAL;
+// the lattice's rows along x through a network, slab by slab (row_slab.h): P_x points a row, P_y P_z rows
+static inline long long lattice_rows(const Lattice& L) { return (long long)L.P[1] * L.P[2]; }
+static inline size_t density_scratch_bytes(const Lattice& L) {
+    return rowslab::slab_bytes(rowslab::min_rows(lattice_rows(L), L.P[0], MI_MESH_MIN_SLAB_POINTS), L.P[0]);
 }
 
 static int density(const mi_mesh_grid* grid, const mi_nerf_net* net, const void* packed, int mode, float* f, void* scratch, size_t scratch_bytes,
                    hipStream_t st) {
     Lattice L;
     if (int rc = resolve_grid(grid, &L)) return rc;
-    mlp_rays_fn fn;
-    if (int rc = mlp_entry(mode, &fn)) return rc;
+    rowslab::mlp_rays_fn fn;
+    if (!rowslab::mlp_entry(set_error, "the density lattice", mode, &fn)) return MI_MESH_EINVAL;
     MESH_CHECK_ARG(net && packed && f && scratch, "NULL pointer (net, packed, f and scratch are required)");
-    MESH_CHECK_ARG(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
     const int Px = L.P[0];
-    const long long rows = (long long)L.P[1] * L.P[2];
-    const size_t need = slab_bytes(min_rows(L), Px);
-    MESH_CHECK_ARG(scratch_bytes >= need, "scratch too small: %zu < %zu (mi_mesh_density_scratch_bytes)", scratch_bytes, need);
-    // the largest slab the scratch holds (three regions, each rounded up to 256 bytes)
-    long long R = (long long)((scratch_bytes - 768) / ((size_t)24 + (size_t)Px * 20));
-    if (R < min_rows(L)) R = min_rows(L);                               // fits: scratch_bytes >= need
-    if (R > rows) R = rows;
-    const long long r_cap = ((1LL << 31) - 1) / Px;                     // a slab's R x P_x points stay below 2^31
-    if (R > r_cap) R = r_cap;
-    char* w = (char*)scratch;
-    float* rays = (float*)w;
-    float* z = (float*)(w + align256((size_t)R * 24));
-    float* raw = (float*)(w + align256((size_t)R * 24) + align256((size_t)R * Px * 4));
-    for (long long r0 = 0; r0 < rows; r0 += R) {
-        const long long nr = rows - r0 < R ? rows - r0 : R;
+    rowslab::Slab slab;
+    if (!rowslab::plan(set_error, "mi_mesh_density_scratch_bytes", Px, lattice_rows(L), MI_MESH_MIN_SLAB_POINTS, scratch, scratch_bytes, &slab)) return MI_MESH_EINVAL;
+    float *rays = slab.rays, *z = slab.z, *raw = slab.raw;
+    return rowslab::for_each(slab, [&](long long r0, long long nr) {
         hipLaunchKernelGGL(mesh_rows_kernel, dim3(blocks_for(nr * Px, 256)), dim3(256), 0, st, L, r0, nr, rays, z);
         MESH_LAUNCH_CHECK("mesh_rows_kernel");
         MESH_NERF(fn(net, packed, rays, z, nr, Px, raw, (void*)st));
         hipLaunchKernelGGL(mesh_density_kernel, dim3(blocks_for(nr * Px, 256)), dim3(256), 0, st, nr * Px, raw, f + r0 * Px);
         MESH_LAUNCH_CHECK("mesh_density_kernel");
-    }
-    return MI_MESH_OK;
+        return MI_MESH_OK;
+    });
 }
 
 struct Scratch {
@@ -511,7 +428,7 @@ const char* mi_mesh_last_error(void) { return g_err; }
 
 size_t mi_mesh_density_scratch_bytes(const mi_mesh_grid* grid) {
     Lattice L;
-    return resolve_grid(grid, &L) == MI_MESH_OK ? slab_bytes(min_rows(L), L.P[0]) : 0;
+    return resolve_grid(grid, &L) == MI_MESH_OK ? density_scratch_bytes(L) : 0;
 }
 
 int mi_mesh_density(const mi_mesh_grid* grid, const mi_nerf_net* net, const void* packed, int mode, float* f, void* scratch, size_t scratch_bytes,

@@ -37,8 +37,6 @@ namespace view {
 constexpr int GUARD = MI_MESH_VIEW_GUARD;
 constexpr int QUEUE = MI_MESH_VIEW_QUEUE;
 constexpr int LARGE_BLOCKS = 1024;                    // view_large_kernel: 4096 waves stride over the queue
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-static inline unsigned blocks_for(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 struct CamArgs {
     float fx, fy, cx, cy;

@@ -8,9 +8,10 @@
 //                      sample's value does not: each lane of the network kernels evaluates its own point)
 // occ_scatter_kernel   one thread per sample: raw[ray, sample] = tile value of a survivor, zeros otherwise (every element written)
 // occ_compact_*_kernel the same compaction WITHOUT an atomic (mi_occ_compact): count per ray | exclusive scan of the tile counts | emit, so
-//                      the tile order is a function of the input; cscan_*_kernel is the scan (block sums | one block over them | apply)
+//                      the tile order is a function of the input; cscan_*_kernel is the scan (block sums | one block over them | apply:
+//                      the bodies of block_scan.h on 64-bit words)
 // occ_gather_kernel    one thread per tile lane: the inverse of the scatter (d_raw of the training path), zeros on padding lanes
-// occ_bake_gen_kernel  sub-lattice rows along x as rays (origin on the box face, direction +x) with depths
+// occ_bake_gen_kernel  sub-lattice rows along x as rays (origin on the box face, direction +x) with depths (the slab loop: row_slab.h)
 // occ_bake_reduce_kernel   OR of (density > sigma_min) over a cell's samples of one row, atomically ORed into the cell's bit
 // occ_dilate_kernel    one thread per cell, neighbourhood OR, words assembled by ballot
 // occ_count_kernel     popcount of the grid's cells
@@ -18,6 +19,8 @@
 #include <math.h>
 #include "../../include/mi_nerf_occ.h"
 #include "abi_error.h"
+#include "block_scan.h"
+#include "row_slab.h"
 
 namespace miocc {
 
@@ -30,7 +33,6 @@ ABI_NERF_FAIL(MI_OCC_EINVAL, MI_OCC_EHIP)
 #define OCC_NERF(call) ABI_NERF(::miocc, call, #call)
 
 constexpr int TILE = MI_OCC_TILE;
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ---- the grid as the kernels see it ----------------------------------------------------------------
 struct GridDev {
@@ -88,54 +90,80 @@ __global__ __launch_bounds__(256) void occ_mark_kernel(GridDev G, const uint32_t
 }
 
 // ---- cull + compact --------------------------------------------------------------------------------
-// One wave = one ray (4 per workgroup; no workgroup barrier).  Pass 1 counts the survivors, lane 0 reserves ceil(count / 32) tiles, pass 2
-// repeats the lookups and writes.  counters[0] += tiles, counters[1] += survivors.
-__global__ __launch_bounds__(256) void occ_cull_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
-                                                       const float* __restrict__ z, long long n, int S, float* __restrict__ tile_rays,
-                                                       float* __restrict__ tile_z, int* __restrict__ tile_src, int* __restrict__ slot,
-                                                       unsigned* __restrict__ counters) {
-    const int lane = threadIdx.x & 63;
-    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ray >= n) return;
+// One wave = one ray (4 per workgroup; no workgroup barrier).  The per-ray compaction is spelled once, for the atomic path
+// (occ_cull_kernel) and the deterministic one (occ_compact_*_kernel): ray_survivors counts, ray_emit repeats the lookups and writes.
+struct WaveRay {
+    long long ray;
+    const float* rp;            // its six floats
+    const float* zr;            // its S depths
+    float o[3], d[3];
+    int lane;
+};
+
+__device__ __forceinline__ WaveRay wave_ray(const float* __restrict__ rays, const float* __restrict__ z, long long ray, int S) {
     const float* rp = rays + ray * 6;
-    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
-    const float* zr = z + ray * S;
+    return WaveRay{ray, rp, z + ray * S, {rp[0], rp[1], rp[2]}, {rp[3], rp[4], rp[5]}, (int)(threadIdx.x & 63)};
+}
+
+// the ray's survivor count, the same in every lane: 64 lookups a round, ballot + popcount
+__device__ __forceinline__ int ray_survivors(const GridDev& G, const uint32_t* __restrict__ bits, const WaveRay& w, int S) {
     int cnt = 0;
     for (int c = 0; c < S; c += 64) {
-        const int s = c + lane;
-        const bool occ = s < S && occ_lookup(G, bits, o, d, zr[s]);
+        const int s = c + w.lane;
+        const bool occ = s < S && occ_lookup(G, bits, w.o, w.d, w.zr[s]);
         cnt += __popcll(__ballot(occ));
     }
-    const int ntiles = (cnt + TILE - 1) / TILE;
-    unsigned base = 0;
-    if (lane == 0 && ntiles > 0) {
-        base = atomicAdd(&counters[0], (unsigned)ntiles);
-        atomicAdd(&counters[1], (unsigned)cnt);
-    }
-    base = __shfl(base, 0, 64);
+    return cnt;
+}
+
+// the ray's tiles from tile `base` on: slot of every sample, tile_z / tile_src of the survivors in order, the last tile padded with the
+// last survivor's depth, the ray copied once per tile.
+__device__ __forceinline__ void ray_emit(const GridDev& G, const uint32_t* __restrict__ bits, const WaveRay& w, int S, long long base,
+                                         float* __restrict__ tile_rays, float* __restrict__ tile_z, int* __restrict__ tile_src, int* __restrict__ slot) {
+    const int lane = w.lane;
     const int j0 = (int)base * TILE;                                  // first flat tile lane of this ray
     int run = 0;
     float last_z = 0.0f;
     for (int c = 0; c < S; c += 64) {
         const int s = c + lane;
-        const float zv = s < S ? zr[s] : 0.0f;
-        const bool occ = s < S && occ_lookup(G, bits, o, d, zv);
+        const float zv = s < S ? w.zr[s] : 0.0f;
+        const bool occ = s < S && occ_lookup(G, bits, w.o, w.d, zv);
         const unsigned long long m = __ballot(occ);
         const int j = j0 + run + __popcll(m & ((1ull << lane) - 1ull));
-        if (s < S) slot[ray * S + s] = occ ? j : -1;
+        if (s < S) slot[w.ray * S + s] = occ ? j : -1;
         if (occ) {
             tile_z[j] = zv;
-            tile_src[j] = (int)(ray * S + s);
+            tile_src[j] = (int)(w.ray * S + s);
         }
         run += __popcll(m);
         if (m) last_z = __shfl(zv, 63 - __clzll((long long)m), 64);
     }
-    const int pad = ntiles * TILE - cnt;                              // < 32
+    const int ntiles = (run + TILE - 1) / TILE;
+    const int pad = ntiles * TILE - run;                              // < 32
     if (lane < pad) {
-        tile_z[j0 + cnt + lane] = last_z;
-        tile_src[j0 + cnt + lane] = -1;
+        tile_z[j0 + run + lane] = last_z;
+        tile_src[j0 + run + lane] = -1;
     }
-    for (int i = lane; i < ntiles * 6; i += 64) tile_rays[(long long)base * 6 + i] = rp[i % 6];
+    for (int i = lane; i < ntiles * 6; i += 64) tile_rays[base * 6 + i] = w.rp[i % 6];
+}
+
+// count, lane 0 reserves ceil(count / 32) tiles (counters[0] += tiles, counters[1] += survivors), emit
+__global__ __launch_bounds__(256) void occ_cull_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
+                                                       const float* __restrict__ z, long long n, int S, float* __restrict__ tile_rays,
+                                                       float* __restrict__ tile_z, int* __restrict__ tile_src, int* __restrict__ slot,
+                                                       unsigned* __restrict__ counters) {
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n) return;
+    const WaveRay w = wave_ray(rays, z, ray, S);
+    const int cnt = ray_survivors(G, bits, w, S);
+    const int ntiles = (cnt + TILE - 1) / TILE;
+    unsigned base = 0;
+    if (w.lane == 0 && ntiles > 0) {
+        base = atomicAdd(&counters[0], (unsigned)ntiles);
+        atomicAdd(&counters[1], (unsigned)cnt);
+    }
+    base = __shfl(base, 0, 64);
+    ray_emit(G, bits, w, S, (long long)base, tile_rays, tile_z, tile_src, slot);
 }
 
 __global__ __launch_bounds__(256) void occ_scatter_kernel(const int* __restrict__ slot, const float4* __restrict__ tile_raw, long long n_pts,
@@ -149,80 +177,25 @@ __global__ __launch_bounds__(256) void occ_scatter_kernel(const int* __restrict_
 // ---- deterministic compaction ------------------------------------------------------------------------
 // count | exclusive scan | emit.  One 64-bit word per ray carries both counts through ONE scan: tiles t_r in the low half, survivors k_r in
 // the high half (sum t < 2^26 and sum k < 2^31 under the entry's size limit, so neither half carries into the other).
-constexpr int CSCAN_TILE = 1024;                                       // 256 threads x 4 rays
+constexpr int CSCAN_TILE = miblock::SCAN_TILE;                         // 256 threads x 4 rays
 
 __global__ __launch_bounds__(256) void occ_compact_count_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
                                                                 const float* __restrict__ z, long long n, int S, unsigned long long* __restrict__ per_ray) {
-    const int lane = threadIdx.x & 63;
     const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= n) return;
-    const float* rp = rays + ray * 6;
-    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
-    const float* zr = z + ray * S;
-    int cnt = 0;
-    for (int c = 0; c < S; c += 64) {
-        const int s = c + lane;
-        const bool occ = s < S && occ_lookup(G, bits, o, d, zr[s]);
-        cnt += __popcll(__ballot(occ));
-    }
-    if (lane == 0) per_ray[ray] = ((unsigned long long)cnt << 32) | (unsigned long long)((cnt + TILE - 1) / TILE);
+    const WaveRay w = wave_ray(rays, z, ray, S);
+    const int cnt = ray_survivors(G, bits, w, S);
+    if (w.lane == 0) per_ray[ray] = ((unsigned long long)cnt << 32) | (unsigned long long)((cnt + TILE - 1) / TILE);
 }
 
-// exclusive scan of one value per thread over a block of NT threads; *total = the block's sum.  lds: NT / 64 + 1 words.
-template <int NT>
-__device__ __forceinline__ unsigned long long cscan_block(unsigned long long v, unsigned long long* total, unsigned long long* lds) {
-    constexpr int NW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(x, d, 64);
-        if (lane >= d) x += t;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long run = 0;
-        for (int w = 0; w < NW; ++w) {
-            const unsigned long long s = lds[w];
-            lds[w] = run;
-            run += s;
-        }
-        lds[NW] = run;
-    }
-    __syncthreads();
-    const unsigned long long r = x - v + lds[wave];
-    *total = lds[NW];
-    __syncthreads();                                                   // lds is reused by the caller's next round
-    return r;
-}
-
+// the scan's three launches (block_scan.h), on the packed words
 __global__ __launch_bounds__(256) void cscan_reduce_kernel(const unsigned long long* __restrict__ data, long long n, unsigned long long* __restrict__ bsum) {
-    __shared__ unsigned long long lds[4];
-    const long long base = (long long)blockIdx.x * CSCAN_TILE + threadIdx.x * 4;
-    unsigned long long s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (base + k < n) s += data[base + k];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+    miblock::scan_reduce(data, n, bsum);
 }
 
 // one block: block sums -> their exclusive prefix sums in place; counts[0] = tiles, counts[1] = survivors of the whole batch
 __global__ __launch_bounds__(1024) void cscan_sums_kernel(unsigned long long* __restrict__ bsum, int nb, unsigned* __restrict__ counts) {
-    __shared__ unsigned long long lds[17];
-    unsigned long long carry = 0;
-    for (int c = 0; c < nb; c += 1024) {
-        const int i = c + (int)threadIdx.x;
-        const unsigned long long v = i < nb ? bsum[i] : 0ull;
-        unsigned long long sum;
-        const unsigned long long ex = cscan_block<1024>(v, &sum, lds);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += sum;
-    }
+    const unsigned long long carry = miblock::scan_sums(bsum, nb);
     if (threadIdx.x == 0) {
         counts[0] = (unsigned)(carry & 0xffffffffull);
         counts[1] = (unsigned)(carry >> 32);
@@ -230,59 +203,18 @@ __global__ __launch_bounds__(1024) void cscan_sums_kernel(unsigned long long* __
 }
 
 __global__ __launch_bounds__(256) void cscan_apply_kernel(unsigned long long* __restrict__ data, long long n, const unsigned long long* __restrict__ bsum) {
-    __shared__ unsigned long long lds[5];
-    const long long base = (long long)blockIdx.x * CSCAN_TILE + threadIdx.x * 4;
-    unsigned long long v[4], s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = base + k < n ? data[base + k] : 0ull;
-        s += v[k];
-    }
-    unsigned long long sum;
-    unsigned long long run = bsum[blockIdx.x] + cscan_block<256>(s, &sum, lds);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (base + k < n) data[base + k] = run;
-        run += v[k];
-    }
+    miblock::scan_apply(data, n, bsum);
 }
 
-// One wave = one ray, as occ_cull_kernel's second pass; the ray's first tile comes from the scan (low half of first[ray]).
+// the ray's first tile comes from the scan (low half of first[ray])
 __global__ __launch_bounds__(256) void occ_compact_emit_kernel(GridDev G, const uint32_t* __restrict__ bits, const float* __restrict__ rays,
                                                                const float* __restrict__ z, long long n, int S,
                                                                const unsigned long long* __restrict__ first, float* __restrict__ tile_rays,
                                                                float* __restrict__ tile_z, int* __restrict__ tile_src, int* __restrict__ slot) {
-    const int lane = threadIdx.x & 63;
     const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= n) return;
-    const float* rp = rays + ray * 6;
-    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
-    const float* zr = z + ray * S;
-    const long long base = (long long)(first[ray] & 0xffffffffull);
-    const int j0 = (int)base * TILE;                                  // first flat tile lane of this ray
-    int run = 0;
-    float last_z = 0.0f;
-    for (int c = 0; c < S; c += 64) {
-        const int s = c + lane;
-        const float zv = s < S ? zr[s] : 0.0f;
-        const bool occ = s < S && occ_lookup(G, bits, o, d, zv);
-        const unsigned long long m = __ballot(occ);
-        const int j = j0 + run + __popcll(m & ((1ull << lane) - 1ull));
-        if (s < S) slot[ray * S + s] = occ ? j : -1;
-        if (occ) {
-            tile_z[j] = zv;
-            tile_src[j] = (int)(ray * S + s);
-        }
-        run += __popcll(m);
-        if (m) last_z = __shfl(zv, 63 - __clzll((long long)m), 64);
-    }
-    const int ntiles = (run + TILE - 1) / TILE;
-    const int pad = ntiles * TILE - run;                              // < 32
-    if (lane < pad) {
-        tile_z[j0 + run + lane] = last_z;
-        tile_src[j0 + run + lane] = -1;
-    }
-    for (int i = lane; i < ntiles * 6; i += 64) tile_rays[base * 6 + i] = rp[i % 6];
+    const WaveRay w = wave_ray(rays, z, ray, S);
+    ray_emit(G, bits, w, S, (long long)(first[ray] & 0xffffffffull), tile_rays, tile_z, tile_src, slot);
 }
 
 __global__ __launch_bounds__(256) void occ_gather_kernel(const int* __restrict__ tile_src, const float4* __restrict__ src, long long n_lanes,
@@ -377,8 +309,6 @@ __global__ __launch_bounds__(256) void occ_count_kernel(GridDev G, const uint32_
 }
 
 // ---- host side -------------------------------------------------------------------------------------
-static inline unsigned blocks_for(long long n, int per) { return (unsigned)((n + per - 1) / per); }
-
 static int resolve_bake(const mi_occ_grid* grid, int sub, GridDev* G, BakeGeom* B) {
     if (int rc = resolve_grid(grid, G)) return rc;
     OCC_CHECK_ARG(sub >= 1 && sub <= MI_OCC_MAX_SUB, "sub=%d: 1..%d lattice points per cell and axis", sub, MI_OCC_MAX_SUB);
@@ -392,25 +322,12 @@ static int resolve_bake(const mi_occ_grid* grid, int sub, GridDev* G, BakeGeom* 
     return MI_OCC_OK;
 }
 
-// bytes of a slab of R rows: rays [R,6], z [R,S], raw [R,S,4]
-static inline size_t bake_slab_bytes(long long R, int S) {
-    return align256((size_t)R * 24) + align256((size_t)R * S * 4) + align256((size_t)R * S * 16);
-}
-static inline long long bake_min_rows(const BakeGeom& B) {
-    const long long want = ((1LL << 22) + B.S - 1) / B.S;
-    return want < B.rows ? want : B.rows;
-}
+// the sub-lattice's rows along x through a network, slab by slab (row_slab.h); the smallest slab holds 2^22 points
+constexpr long long BAKE_MIN_SLAB_POINTS = 1LL << 22;
+static inline size_t bake_scratch_bytes(const BakeGeom& B) { return rowslab::slab_bytes(rowslab::min_rows(B.rows, B.S, BAKE_MIN_SLAB_POINTS), B.S); }
 
-typedef int (*mlp_rays_fn)(const mi_nerf_net*, const void*, const float*, const float*, int64_t, int, float*, void*);
-static int mlp_entry(int mode, mlp_rays_fn* fn) {
-    switch (mode) {
-        case MI_NERF_MODE_F32:  *fn = mi_nerf_mlp_rays; return MI_OCC_OK;
-        case MI_NERF_MODE_F16S: *fn = mi_nerf_mlp_rays_f16s; return MI_OCC_OK;
-        case MI_NERF_MODE_BF16: *fn = mi_nerf_mlp_rays_bf16; return MI_OCC_OK;
-    }
-    set_error("mode %d: the occupancy path runs MI_NERF_MODE_F32 (0), MI_NERF_MODE_BF16 (1) and MI_NERF_MODE_F16S (5)", mode);
-    return MI_OCC_EINVAL;
-}
+using rowslab::mlp_rays_fn;
+static int mlp_entry(int mode, mlp_rays_fn* fn) { return rowslab::mlp_entry(set_error, "the occupancy path", mode, fn) ? MI_OCC_OK : MI_OCC_EINVAL; }
 
 static int bake(const mi_occ_grid* grid, uint32_t* bits, const mi_nerf_net* net, const void* packed, int mode, int sub, float sigma_min, int accumulate,
                 void* scratch, size_t scratch_bytes, hipStream_t st) {
@@ -421,29 +338,18 @@ static int bake(const mi_occ_grid* grid, uint32_t* bits, const mi_nerf_net* net,
     if (int rc = mlp_entry(mode, &fn)) return rc;
     OCC_CHECK_ARG(bits && net && packed && scratch, "NULL pointer (bits, net, packed and scratch are required)");
     OCC_CHECK_ARG(!isnan(sigma_min), "sigma_min is NaN");
-    OCC_CHECK_ARG(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
-    const size_t need = bake_slab_bytes(bake_min_rows(B), B.S);
-    OCC_CHECK_ARG(scratch_bytes >= need, "scratch too small: %zu < %zu (mi_occ_bake_scratch_bytes)", scratch_bytes, need);
-    // the largest slab the scratch holds (three regions, each rounded up to 256 bytes)
-    long long R = (long long)((scratch_bytes - 768) / ((size_t)24 + (size_t)B.S * 20));
-    if (R < bake_min_rows(B)) R = bake_min_rows(B);                    // fits: scratch_bytes >= need
-    if (R > B.rows) R = B.rows;
-    const long long r_cap = ((1LL << 31) - 1) / B.S;                   // a slab's R x S points stay below 2^31, the bound the render path keeps
-    if (R > r_cap) R = r_cap;                                          // (never below bake_min_rows: that is about 2^22 points)
-    char* w = (char*)scratch;
-    float* rays = (float*)w;
-    float* z = (float*)(w + align256((size_t)R * 24));
-    float* raw = (float*)(w + align256((size_t)R * 24) + align256((size_t)R * B.S * 4));
+    rowslab::Slab slab;
+    if (!rowslab::plan(set_error, "mi_occ_bake_scratch_bytes", B.S, B.rows, BAKE_MIN_SLAB_POINTS, scratch, scratch_bytes, &slab)) return MI_OCC_EINVAL;
     if (!accumulate) OCC_HIP(hipMemsetAsync(bits, 0, grid_words(G) * 4, st));
-    for (long long r0 = 0; r0 < B.rows; r0 += R) {
-        const long long nr = B.rows - r0 < R ? B.rows - r0 : R;
+    float *rays = slab.rays, *z = slab.z, *raw = slab.raw;
+    return rowslab::for_each(slab, [&](long long r0, long long nr) {
         hipLaunchKernelGGL(occ_bake_gen_kernel, dim3(blocks_for(nr * B.S, 256)), dim3(256), 0, st, B, r0, nr, rays, z);
         OCC_LAUNCH_CHECK("occ_bake_gen_kernel");
         OCC_NERF(fn(net, packed, rays, z, nr, B.S, raw, (void*)st));
         hipLaunchKernelGGL(occ_bake_reduce_kernel, dim3(blocks_for(nr * B.rx, 256)), dim3(256), 0, st, B, r0, nr, raw, sigma_min, bits);
         OCC_LAUNCH_CHECK("occ_bake_reduce_kernel");
-    }
-    return MI_OCC_OK;
+        return MI_OCC_OK;
+    });
 }
 
 // ---- render ----------------------------------------------------------------------------------------
@@ -617,7 +523,7 @@ size_t mi_occ_bake_scratch_bytes(const mi_occ_grid* grid, int sub) {
     GridDev G;
     BakeGeom B;
     if (resolve_bake(grid, sub, &G, &B) != MI_OCC_OK) return 0;
-    return bake_slab_bytes(bake_min_rows(B), B.S);
+    return bake_scratch_bytes(B);
 }
 
 int mi_occ_bake(const mi_occ_grid* grid, uint32_t* bits, const mi_nerf_net* net, const void* packed, int mode, int sub, float sigma_min, int accumulate,

@@ -21,7 +21,7 @@
 //                          16-byte loads (B = 4, 9) for binary16, widened with v_cvt_f32_f16.  Active x neighbours have consecutive slots,
 //                          so the records of a pair of lanes are still adjacent.
 //   index_*_kernel         mi_vox_index: the active flag of 1024 points per workgroup into the slot plane and their count (ballots, wave
-//                          sums through LDS) | one block scans the counts | flags become record numbers.  Deterministic: no atomic.
+//                          sums through LDS) | one block scans the counts (block_scan.h) | flags become record numbers.  Deterministic: no atomic.
 //   pack_kernel<F16>       one thread per 16-byte piece of an fp32 record: copied, or converted to four binary16 values, to table[slot].
 //
 // No atomic, no host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include "../../include/mi_nerf_vox.h"
 #include "abi_error.h"
+#include "block_scan.h"
 #define VOX_RULE_NAMESPACE mivox
 #include "vox_rule.h"
 
@@ -136,34 +137,7 @@ __global__ __launch_bounds__(THREADS) void index_flag_kernel(const Lattice g, co
 
 // one block: the chunk counts -> their exclusive prefix sums in place; *total = M
 __global__ __launch_bounds__(1024) void index_scan_kernel(unsigned* __restrict__ counts, int nb, long long* __restrict__ total) {
-    __shared__ unsigned lds[1024 / 64 + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned carry = 0;
-    for (int c = 0; c < nb; c += 1024) {
-        const int i = c + (int)threadIdx.x;
-        const unsigned v = i < nb ? counts[i] : 0u;
-        unsigned x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned t = __shfl_up(x, d, 64);
-            if (lane >= d) x += t;
-        }
-        if (lane == 63) lds[wave] = x;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned run = 0;
-            for (int w = 0; w < 1024 / 64; ++w) {
-                const unsigned s = lds[w];
-                lds[w] = run;
-                run += s;
-            }
-            lds[1024 / 64] = run;
-        }
-        __syncthreads();
-        if (i < nb) counts[i] = carry + (x - v + lds[wave]);
-        carry += lds[1024 / 64];
-        __syncthreads();                                                   // lds is rewritten by the next round
-    }
+    const unsigned carry = miblock::scan_sums(counts, nb);
     if (threadIdx.x == 0) *total = (long long)carry;
 }
 

@@ -122,6 +122,33 @@ def test_compaction_equals_the_restatement_on_lego_rays(outside):
     assert 0.05 < share < 0.95
 
 
+def test_compaction_scan_carries_past_1024_blocks():
+    """2^20 + 1025 rays are 1026 blocks of the 64-bit scan: the one block over the block sums takes a second round, with a carry, and the last
+    block is ragged.  S = 1 and direction zero: a ray is one point, a survivor is one tile, so every output has a closed form in
+    mask = mi_occ_mark and its exclusive prefix sum, computed with torch on the device.  The surviving share of this seed is 0.5027 by the cell
+    rule of tests/test_occ_cpu.py."""
+    n = 1024 * 1024 + 1025
+    rs = np.random.RandomState(7)
+    grid = random_grid(res=(16, 16, 16), outside=False, seed=3)
+    rays_np = np.zeros((n, 6), np.float32)
+    rays_np[:, :3] = rs.uniform(-2.5, 2.5, (n, 3))
+    rays = torch.from_numpy(rays_np).to(DEV)
+    z = torch.from_numpy(rs.uniform(2.0, 6.0, (n, 1)).astype(np.float32)).to(DEV)
+    mask = grid.mark(rays, z).bool().view(-1)
+    total = int(mask.sum())
+    print(f"\n[compact {n} rays, S = 1] surviving share {total / n:.4f}")
+    assert 0.2 < total / n < 0.8
+    got = grid.compact(rays, z)
+    assert got["tiles"] == got["survivors"] == total
+    k = torch.cumsum(mask.long(), 0) - mask.long()                       # exclusive: the survivors before ray r
+    assert torch.equal(got["slot"].view(-1), torch.where(mask, 32 * k, torch.full_like(k, -1)).int())
+    alive = torch.nonzero(mask).view(-1)                                 # the surviving rays, in order
+    src = got["tile_src"]
+    assert src.shape == (total, 32) and torch.equal(src[:, 0], alive.int()) and bool((src[:, 1:] == -1).all())
+    assert torch.equal(got["tile_z"].view(torch.int32), z[alive].expand(total, 32).contiguous().view(torch.int32))
+    assert torch.equal(got["tile_rays"].view(torch.int32), rays[alive].view(torch.int32))
+
+
 def test_compaction_of_no_rays():
     grid = random_grid()
     got = grid.compact(torch.empty(0, 6, device=DEV), torch.empty(0, 64, device=DEV))
