@@ -5,7 +5,8 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10] [--mesh-view]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
-                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY]]]
+                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY]
+                                             [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -25,6 +26,10 @@ are rendered from the grid as well, with no network, and the PSNR of the grid's 
 (baked_train.finetune: the backward pass of the grid renderer) and its PSNR on the test views is printed before and after;
 ``--bake-reg TV_SIGMA:TV_COEF:SPARSITY`` adds the lattice regularisers to those steps (total variation of the density plane and of the
 records, Cauchy sparsity of the density; e.g. 0.01:0.01:0.01) and is refused without ``--bake-finetune``.
+``--bake-levels RES:STEPS[,RES:STEPS...]`` trains the grid coarse to fine (baked_train.coarse_to_fine): the network is baked at the first
+level's resolution -- eight times fewer evaluations per halving -- and each level's steps are followed by a resample to the next
+(RadianceGrid.resample); the final level is ``--bake`` RES with ``--bake-finetune`` STEPS.  ``--bake-prune TAU`` ends every level with
+RadianceGrid.prune(TAU): density and records are cleared away from density above TAU.  Both are refused without ``--bake RES --bake-finetune STEPS``.
 """
 import argparse
 import os
@@ -66,6 +71,9 @@ def main(argv=None):
     ap.add_argument("--bake-finetune", type=int, default=0, metavar="STEPS", help="after --bake (dense), fine-tune the grid on the training views for STEPS steps")
     ap.add_argument("--bake-reg", default=None, metavar="TV_SIGMA:TV_COEF:SPARSITY",
                     help="with --bake-finetune: weights of the total variation of the density plane and of the records and of the density's sparsity prior")
+    ap.add_argument("--bake-levels", default=None, metavar="RES:STEPS[,RES:STEPS...]",
+                    help="with --bake RES --bake-finetune STEPS: bake at the first level's resolution and train coarse to fine through these levels; the final level is RES with STEPS steps")
+    ap.add_argument("--bake-prune", type=float, default=None, metavar="TAU", help="with --bake-finetune: after each level, clear density and records away from density above TAU")
     a = ap.parse_args(argv)
     if a.warmup is not None and not 0 <= a.warmup < a.steps:
         ap.error("--warmup takes a number of steps below --steps")
@@ -86,6 +94,18 @@ def main(argv=None):
         if not all(np.isfinite(w) and w >= 0 for w in (w_tvs, w_tvc, w_sp)):
             ap.error("--bake-reg takes three non-negative numbers")
         bake_reg = {"tv_sigma": w_tvs, "tv_coef": w_tvc, "sparsity": w_sp}
+    bake_levels = []
+    if a.bake_levels is not None or a.bake_prune is not None:
+        if not a.bake_finetune:                                                                  # (without --bake, --bake-finetune was refused above)
+            ap.error("--bake-levels and --bake-prune shape the steps of --bake RES --bake-finetune STEPS: give those too")
+        if a.bake_prune is not None and not (np.isfinite(a.bake_prune) and a.bake_prune >= 0):
+            ap.error("--bake-prune takes a finite number >= 0")
+        try:
+            bake_levels = [tuple(int(v) for v in lv.split(":")) for lv in a.bake_levels.split(",")] if a.bake_levels else []
+        except ValueError:
+            ap.error("--bake-levels takes RES:STEPS[,RES:STEPS...], pairs of integers")
+        if any(len(lv) != 2 or not 1 <= lv[0] <= 512 or lv[1] < 0 for lv in bake_levels):
+            ap.error("--bake-levels takes RES in 1..512 and STEPS >= 0 per level")
     if a.bake is not None:
         fields = a.bake.split(":")
         try:
@@ -198,7 +218,7 @@ def main(argv=None):
         from nerf_pytorch_paeng_amd import baked
         t_bake = time.perf_counter()
         if bake_storage == "dense":
-            grid = baked.RadianceGrid(-a.mesh_box, a.mesh_box, bake_res, B=bake_B)
+            grid = baked.RadianceGrid(-a.mesh_box, a.mesh_box, bake_levels[0][0] if bake_levels else bake_res, B=bake_B)      # coarse to fine: the first level's lattice
         else:
             grid = baked.SparseRadianceGrid(-a.mesh_box, a.mesh_box, bake_res, B=bake_B, storage="f16" if bake_storage == "sparse16" else "fp32")
         grid = grid.bake(fresh, network="fine", precision=a.precision)
@@ -210,7 +230,7 @@ def main(argv=None):
         t_grid = time.perf_counter() - t_grid
         opts.baked = None
         mse = np.mean((rgbs_g.astype(np.float64) - rgbs.astype(np.float64)) ** 2, axis=(1, 2, 3)) / 255.0 ** 2
-        print(f"bake: {bake_res}^3 cells, B={bake_B}, {bake_storage}, {grid.nbytes / 2 ** 20:.1f} MiB in {t_bake:.2f} s; {rgbs_g.shape[0]} frames from the grid in {t_grid * 1e3:.1f} ms "
+        print(f"bake: {grid.res[0]}^3 cells, B={bake_B}, {bake_storage}, {grid.nbytes / 2 ** 20:.1f} MiB in {t_bake:.2f} s; {rgbs_g.shape[0]} frames from the grid in {t_grid * 1e3:.1f} ms "
               f"(the network: {t_net * 1e3:.1f} ms, PNG writing included in both); PSNR of the grid's frames against the network's "
               f"{['%.2f' % (-10.0 * np.log10(max(m, 1e-12))) for m in mse]} dB; {a.out}/render_baked")
         if a.bake_finetune > 0:
@@ -227,13 +247,18 @@ def main(argv=None):
 
             before = grid_psnr()
             t_ft = time.perf_counter()
-            losses = baked_train.finetune(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), a.bake_finetune, **bake_reg)
+            if bake_levels or a.bake_prune is not None:
+                levels = bake_levels + [(bake_res, a.bake_finetune)]
+                grid, losses = baked_train.coarse_to_fine(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), levels, prune=a.bake_prune, **bake_reg)
+                print(f"bake-levels: {levels}, prune {a.bake_prune}; {int(grid.skip.sum())} of {grid.skip.numel()} blocks of the skip plane occupied at the end")
+            else:
+                losses = baked_train.finetune(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), a.bake_finetune, **bake_reg)
             torch.cuda.synchronize()
             t_ft = time.perf_counter() - t_ft
             if bake_reg:
                 print(f"bake-reg: {bake_reg}; TV(sigma) {float(baked_train.lattice_tv(grid)):.4g}, TV(coef) {float(baked_train.lattice_tv(grid, 'coef')):.4g}, "
                       f"SP {float(baked_train.lattice_sparsity(grid)):.4g} after the steps")
-            print(f"bake-finetune: {a.bake_finetune} steps in {t_ft:.2f} s, batch loss {float(losses[0]):.5f} -> {float(losses[-1]):.5f}; the grid's PSNR on the test "
+            print(f"bake-finetune: {int(losses.numel())} steps{' over the levels ' + str(levels) if bake_levels or a.bake_prune is not None else ''} in {t_ft:.2f} s, batch loss {float(losses[0]):.5f} -> {float(losses[-1]):.5f}; the grid's PSNR on the test "
                   f"views {['%.2f' % p for p in before]} -> {['%.2f' % p for p in grid_psnr()]} dB")
     if a.mesh:
         from nerf_pytorch_paeng_amd import mesh

@@ -74,6 +74,26 @@
  *     coef[index[m], 3 b + c] = sum over j of proj[b, j] * s(raw[m, j, c]),  s(x) = 1 / (1 + expf(-x)),  in increasing j from 0;
  * the rest of the record is written as zero.  One thread writes one record; an index outside [0, P_x P_y P_z) is ignored; indices are
  * distinct.
+ *
+ * THE RESAMPLING RULE (mi_vox_resample) moves a grid's content to another lattice.  A source grid (lo_s, hi_s, res_s; sigma_s, coef_s) and
+ * a destination grid with a lo_d, hi_d and res_d of its own -- another resolution, and if wanted another box -- share B.  For every
+ * destination lattice point j, in THE LATTICE's arithmetic:
+ *     x_i = lo_d,i + (float)j_i * step_d,i;   g_i = (x_i - lo_s,i) * inv_s,i;   c_i = min(max((int)floorf(g_i), 0), res_s,i - 1);
+ *     f_i = fminf(fmaxf(g_i - (float)c_i, 0), 1);
+ * corners, weights w_e = (wx wy) wz and the pairwise sum exactly as in step 3 of THE RENDER RULE: that step applied to the lattice point
+ * itself, in the source grid.  A point outside the source box therefore takes the value at the nearest face (edge extension), and a
+ * destination box inside the source box crops.
+ *     sigma_d[j] = the interpolation of sigma_s;   coef_d[j][t] = the interpolation of coef_s[.][t] for each of the 3 B counted floats t;
+ * each padding float of the destination record is written as zero, and no source padding is read into a result.  Every element of sigma_d
+ * and coef_d is written; the source is not modified.  Trilinear interpolation reproduces a trilinear function, so on the same box a
+ * res_d that is a multiple of res_s represents the identical field (up to rounding): refining does not change the picture.
+ *
+ * THE PRUNING RULE (mi_vox_prune), with a threshold tau >= 0: a lattice point is KEPT iff it or one of its 26 neighbours (clipped to the
+ * lattice) has sigma_in > tau -- the active stencil above with a threshold; tau = 0 is exactly active.
+ *     sigma_out[j] = kept ? sigma_in[j] : 0;   the record of a point that is not kept is written as R zeros, in place;
+ * the record of a kept point is not written at all, and sigma_in is not modified.  Afterwards the records of the points that are not
+ * active (under sigma_out) are zero: the state a bake leaves, which training by include/mi_nerf_voxgrad.h relies on and does not keep.
+ * The result is bit-identical from run to run.
  */
 #ifndef MI_NERF_VOX_H
 #define MI_NERF_VOX_H
@@ -163,6 +183,16 @@ int mi_vox_pack(const mi_vox_grid* grid, int B, int fmt, const float* src_dev, c
 int mi_vox_render_sparse(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev, int64_t M,
                          const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev,
                          float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream);
+
+/* THE RESAMPLING RULE, dense fp32 grids (added within ABI 2: nothing earlier changed).  sigma_src_dev [P_z, P_y, P_x] and coef_src_dev
+ * [P_z, P_y, P_x, R] of src, sigma_dst_dev and coef_dst_dev of dst; the coef arrays 16-byte aligned, none NULL.  Refused when a
+ * destination array shares a byte with a source array or with the other destination array. */
+int mi_vox_resample(const mi_vox_grid* src, const mi_vox_grid* dst, int B, const float* sigma_src_dev, const float* coef_src_dev, float* sigma_dst_dev,
+                    float* coef_dst_dev, void* stream);
+
+/* THE PRUNING RULE.  tau finite and >= 0; sigma_out_dev must not be sigma_in_dev (refused: the stencil reads a point's neighbours);
+ * coef_dev [P_z, P_y, P_x, R], 16-byte aligned, is edited in place.  The caller rebuilds the skip plane from sigma_out_dev. */
+int mi_vox_prune(const mi_vox_grid* grid, int B, float tau, const float* sigma_in_dev, float* sigma_out_dev, float* coef_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,8 @@ SIGNATURES = {
     "mi_vox_index": (_I, [_GRIDP, _P, _P, _P, _P, _SZ, _P]),
     "mi_vox_pack": (_I, [_GRIDP, _I, _I, _P, _P, _I64, _P, _P]),
     "mi_vox_render_sparse": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P]),
+    "mi_vox_resample": (_I, [_GRIDP, _GRIDP, _I, _P, _P, _P, _P, _P]),
+    "mi_vox_prune": (_I, [_GRIDP, _I, _F, _P, _P, _P, _P]),
 }
 
 lib, check, last_error = loader(globals(), "mi_vox")

@@ -5,6 +5,8 @@
     opts.baked = grid                                                    # harness.test / harness.render then render every pose from it
     small = grid.compact("f16")                                          # records of the active points only (THE COMPACT GRID), fp32 or f16
     small = baked.SparseRadianceGrid(-1.2, 1.2, 512, B=9, storage="f16").bake(model)    # ... baked without the dense record array
+    fine = grid.resample(512)                                            # the same field on another lattice (THE RESAMPLING RULE)
+    grid.prune(0.5)                                                      # sigma and records cleared away from density > 0.5 (THE PRUNING RULE)
 
 The lattice is the one of mesh.density_lattice (include/mi_nerf_mesh.h): the grid's sigma plane is that lattice after a ReLU.  Colour is
 the network's post-sigmoid colour at the lattice point, seen from D fixed directions, projected by least squares onto B real spherical
@@ -211,6 +213,37 @@ class RadianceGrid:
         out.pack(self.coef, out.table, out.count, slot=out.slot)
         return out
 
+    # ---- coarse to fine ------------------------------------------------------------------------------
+    def resample(self, res, lo=None, hi=None) -> "RadianceGrid":
+        """mi_vox_resample: a new dense grid of resolution ``res`` on the box (lo, hi) -- this grid's own by default -- that holds this
+        grid's content by THE RESAMPLING RULE, with its skip plane built.  A multiple of the resolution on the same box represents the
+        identical field; a smaller box crops, a larger one extends the faces.  This grid is left as it is."""
+        self._need()
+        dev = self.sigma.device
+        out = RadianceGrid(self.lo if lo is None else lo, self.hi if hi is None else hi, res, self.B)
+        out.sigma = torch.empty(out.points, dtype=torch.float32, device=dev)
+        out.coef = torch.empty(*out.points, out.record_floats, dtype=torch.float32, device=dev)
+        out.skip = torch.empty(out.skip_shape, dtype=torch.uint8, device=dev)
+        gs, gd = self.c_grid(), out.c_grid()
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_resample(C.byref(gs), C.byref(gd), self.B, dev_ptr(self.sigma.detach(), "sigma"),
+                                                  dev_ptr(self.coef.detach(), "coef", torch.float32, 16), dev_ptr(out.sigma, "sigma_dst"),
+                                                  dev_ptr(out.coef, "coef_dst", torch.float32, 16), stream_ptr(dev)), "mi_vox_resample")
+        return out.build_skip()
+
+    def prune(self, tau: float) -> "RadianceGrid":
+        """mi_vox_prune: a point stays when it or one of its 26 neighbours has sigma > tau; everywhere else sigma becomes 0 and the record
+        zero (THE PRUNING RULE).  The new sigma plane replaces the old one and the skip plane is rebuilt."""
+        self._need()
+        dev = self.sigma.device
+        kept = torch.empty_like(self.sigma)
+        g = self.c_grid()
+        with ops._guard(dev):
+            _vox.check(_vox.lib().mi_vox_prune(C.byref(g), self.B, float(tau), dev_ptr(self.sigma.detach(), "sigma"), dev_ptr(kept, "sigma_out"),
+                                               dev_ptr(self.coef.detach(), "coef", torch.float32, 16), stream_ptr(dev)), "mi_vox_prune")
+        self.sigma = kept.requires_grad_(self.sigma.requires_grad)
+        return self.build_skip()
+
     # ---- baking --------------------------------------------------------------------------------------
     def bake(self, model_or_packed, network: str = "fine", D: int = 32, sigma_min: float = 0.0, precision=None,
              slab_points: int = SLAB_POINTS, shell: str = "field") -> "RadianceGrid":
@@ -296,6 +329,12 @@ class SparseRadianceGrid(RadianceGrid):
 
     def project(self, *args, **kwargs):
         raise MiNerfError("a SparseRadianceGrid has no dense record array to project into: bake_field(..., storage='sparse') fills its table")
+
+    def resample(self, *args, **kwargs):
+        raise MiNerfError("a SparseRadianceGrid has no dense record array to resample: refine the dense grid, then compact()")
+
+    def prune(self, *args, **kwargs):
+        raise MiNerfError("a SparseRadianceGrid has no dense record array to prune: refine the dense grid, then compact()")
 
     # ---- the library's entries -----------------------------------------------------------------------
     def index(self) -> "SparseRadianceGrid":

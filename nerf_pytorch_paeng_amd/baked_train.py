@@ -5,6 +5,7 @@
     rgb, disp, acc, depth = baked_train.render(grid, rays)               # one autograd node, for a loss of one's own
     tv = baked_train.lattice_tv(grid, "sigma", mask=True, scale=1e-4)    # the priors a grid trained from nothing wants: total variation and
     sp = baked_train.lattice_sparsity(grid, scale=1e-4)                  # Cauchy sparsity, value returned, gradient ADDED into .grad
+    grid, losses = baked_train.coarse_to_fine(grid, rays, target, [(64, 200), (128, 200)], prune=1.0, skip=(False, True))   # train coarse, resample, prune, go on
 
 The forward is ``grid.render`` (libmi_nerf_vox.so); the backward is mi_voxgrad_render_backward, which recomputes the march and ADDS
 dL/d sigma and dL/d coef by THE BACKWARD RULE of the header.  Its sums are fp32 hardware atomic adds: unlike every other entry of the
@@ -243,3 +244,49 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
         grid.sigma.grad = grid.coef.grad = None
     grid.build_skip()
     return torch.stack(losses) if losses else torch.zeros(0, dtype=torch.float32, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------
+# coarse to fine: THE RESAMPLING RULE and THE PRUNING RULE of include/mi_nerf_vox.h between runs of finetune
+# ---------------------------------------------------------------------------------------------------
+PER_LEVEL = ("lr_sigma", "lr_coef", "batch", "skip")
+
+
+def _per_level(name: str, v, n: int) -> list:
+    """One value for every level, or one per level."""
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise MiNerfError(f"{name}: one value or one per level ({n}) expected, got {len(v)}")
+        return list(v)
+    return [v] * n
+
+
+def coarse_to_fine(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, levels, prune=None, **finetune_kw):
+    """Train through ``levels``, a sequence of (res, steps): per level the grid is resampled to ``res`` (``grid.resample``; not when it has
+    that resolution already), ``finetune`` runs ``steps`` steps with a fresh optimiser, and with ``prune`` the level ends in
+    ``grid.prune(tau)`` -- ``prune`` one tau or one per level (None: that level is not pruned).  ``lr_sigma``, ``lr_coef``, ``batch`` and
+    ``skip`` may each be one value or one per level (a grid that starts empty wants ``skip=False`` on its first level only: after it the
+    skip plane describes what was learnt); every other keyword goes to ``finetune`` as it is.  Returns (the final grid, the levels' losses
+    concatenated as one device tensor).  The grid handed in is trained in place on the levels before the first resample and untouched
+    afterwards.  Nothing synchronises with the host."""
+    dev = _check(grid, rays)
+    levels = [tuple(lv) if isinstance(lv, (list, tuple)) else lv for lv in levels]
+    if not levels or any(not isinstance(lv, tuple) or len(lv) != 2 for lv in levels):
+        raise MiNerfError(f"levels: a sequence of (res, steps) pairs expected, got {levels!r}")
+    n = len(levels)
+    if "steps" in finetune_kw:
+        raise MiNerfError("steps are given per level, in levels")
+    taus = _per_level("prune", prune, n)
+    for tau in taus:
+        if tau is not None and not (isinstance(tau, (int, float)) and math.isfinite(tau) and tau >= 0):
+            raise MiNerfError(f"prune={prune!r}: each tau must be a finite number >= 0 (or None)")
+    each = {k: _per_level(k, finetune_kw.pop(k), n) for k in PER_LEVEL if k in finetune_kw}
+    losses = []
+    for i, (res, steps) in enumerate(levels):
+        res3 = tuple(int(r) for r in res) if isinstance(res, (list, tuple)) else (int(res),) * 3
+        if res3 != tuple(grid.res):
+            grid = grid.resample(res3)
+        losses.append(finetune(grid, rays, target, steps=int(steps), **{k: v[i] for k, v in each.items()}, **finetune_kw))
+        if taus[i] is not None:
+            grid.prune(taus[i])
+    return grid, (torch.cat(losses) if losses else torch.zeros(0, dtype=torch.float32, device=dev))

@@ -23,6 +23,16 @@
 //   index_*_kernel         mi_vox_index: the active flag of 1024 points per workgroup into the slot plane and their count (ballots, wave
 //                          sums through LDS) | one block scans the counts (block_scan.h) | flags become record numbers.  Deterministic: no atomic.
 //   pack_kernel<F16>       one thread per 16-byte piece of an fp32 record: copied, or converted to four binary16 values, to table[slot].
+//   resample_kernel<B>     THE RESAMPLING RULE, a gather: one thread per 16-byte piece of a destination record (1 / 4 / 8 threads per
+//                          point, x fastest), so a wave stores 1 KiB of consecutive bytes.  A thread finds its point's source cell with
+//                          vox_rule.h's cell_of (the renderer's), loads the same piece of the eight source records with 16-byte loads
+//                          (12-byte ones for B = 1, whose fourth float is always padding) -- the lanes of one point read eight whole
+//                          records between them -- and sums in the rule's order; piece 0's thread also interpolates sigma.  A piece
+//                          that is all padding is stored as zeros without a load; a padding float beside counted ones is masked
+//                          to zero after the sum, so that its load stays part of the 16 bytes.
+//   prune_kernel<B>        THE PRUNING RULE, the same thread shape: a point's R4 lanes split the 27 sigma reads of the stencil between
+//                          them and a ballot joins the answers; piece 0's thread writes sigma_out, and the record of a point that is
+//                          not kept is zeroed piece by piece.  A kept record is not touched.
 //
 // No atomic, no host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
 #include <hip/hip_runtime.h>
@@ -194,6 +204,108 @@ __global__ __launch_bounds__(THREADS) void pack_kernel(const float4* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// mi_vox_resample, mi_vox_prune: one thread per 16-byte piece of a destination record, x fastest
+// ------------------------------------------------------------------------------------------------
+struct ResampleArgs {
+    Lattice s, d;                                        // source, destination
+    float step_d[3];                                     // (hi_d - lo_d) / (float)res_d, formed on the host in fp32
+    const float* sigma_s;
+    const float4* coef_s;
+    float* sigma_d;
+    float4* coef_d;
+    long long pieces;                                    // destination points x R4
+};
+
+// the header's pairwise sum of eight weighted corners
+__device__ __forceinline__ float interp8(const float (&w)[8], const float (&q)[8]) {
+    return ((w[0] * q[0] + w[1] * q[1]) + (w[2] * q[2] + w[3] * q[3])) + ((w[4] * q[4] + w[5] * q[5]) + (w[6] * q[6] + w[7] * q[7]));
+}
+
+template <int B>
+__global__ __launch_bounds__(THREADS) void resample_kernel(const ResampleArgs a) {
+    constexpr int R4 = record_floats(B) / 4;               // pieces of a record
+    constexpr int V4 = (3 * B + 3) / 4;                    // the pieces that hold coefficients
+    const long long t = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (t >= a.pieces) return;
+    const unsigned j = (unsigned)(t / R4);                 // at most 513^3 points: 32-bit divisions below
+    const int q = (int)(t % R4);
+    float4* out = a.coef_d + t;                            // = coef_d[j * R4 + q]
+    if (q >= V4) {                                         // all padding: no load
+        *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const Lattice& s = a.s;
+    const unsigned row = j / (unsigned)a.d.P[0];
+    const int jd[3] = {(int)(j - row * (unsigned)a.d.P[0]), (int)(row % (unsigned)a.d.P[1]), (int)(row / (unsigned)a.d.P[1])};
+    int c[3];
+    float f[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float x = a.d.lo[i] + (float)jd[i] * a.step_d[i];
+        cell_of((x - s.lo[i]) * s.inv[i], s.res[i], c[i], f[i]);
+    }
+    float w[8];
+    long long at[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int ex = e & 1, ey = (e >> 1) & 1, ez = e >> 2;
+        const float wx = ex ? f[0] : 1.0f - f[0], wy = ey ? f[1] : 1.0f - f[1], wz = ez ? f[2] : 1.0f - f[2];
+        w[e] = (wx * wy) * wz;
+        at[e] = ((long long)(c[2] + ez) * s.P[1] + (c[1] + ey)) * s.P[0] + (c[0] + ex);
+    }
+    float4 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = a.coef_s[at[e] * R4 + q];
+    float qx[8], qy[8], qz[8], qw[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { qx[e] = v[e].x; qy[e] = v[e].y; qz[e] = v[e].z; qw[e] = v[e].w; }
+    float4 r;
+    r.x = interp8(w, qx);
+    r.y = interp8(w, qy);                                  // 3 B is a multiple of 3: the first three floats of a piece that holds any are counted
+    r.z = interp8(w, qz);
+    // the fourth may be padding (B = 1: always; B = 9: piece 6), written as zero whatever the source holds there.  The bits are masked
+    // and not selected: a select lets the compiler split the 16-byte load into 12 bytes and a 4-byte load under a branch
+    static_assert((3 * B) % 4 == 3 || (3 * B) % 4 == 0, "a piece holds 3 or 4 counted floats");
+    const int keep = 4 * q + 3 < 3 * B ? -1 : 0;
+    r.w = __int_as_float(__float_as_int(interp8(w, qw)) & keep);
+    *out = r;
+    if (q == 0) {
+        float qs[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qs[e] = a.sigma_s[at[e]];
+        a.sigma_d[j] = interp8(w, qs);
+    }
+}
+
+// kept: the point or one of its 26 neighbours (clipped) has sigma > tau.  The R4 lanes of a point share the 27 reads (lane q takes
+// neighbours q, q + R4, ...) and a ballot joins them: R4 divides 64, so a point's lanes sit in one wave.
+template <int B>
+__global__ __launch_bounds__(THREADS) void prune_kernel(const Lattice g, float tau, const float* __restrict__ sigma_in, float* __restrict__ sigma_out,
+                                                        float4* __restrict__ coef, long long pieces) {
+    constexpr int R4 = record_floats(B) / 4;
+    const long long t = (long long)blockIdx.x * THREADS + threadIdx.x;
+    const bool live = t < pieces;                          // no lane leaves before the ballot
+    const unsigned j = (unsigned)(t / R4);                 // used only when live: at most 513^3 points, 32-bit divisions below
+    const int q = (int)(t % R4);
+    bool hit = false;
+    if (live) {
+        const unsigned row = j / (unsigned)g.P[0];
+        const int x = (int)(j - row * (unsigned)g.P[0]), y = (int)(row % (unsigned)g.P[1]), z = (int)(row / (unsigned)g.P[1]);
+        for (int n = q; n < 27; n += R4) {
+            const int x1 = x + n % 3 - 1, y1 = y + (n / 3) % 3 - 1, z1 = z + n / 9 - 1;
+            if (x1 >= 0 && x1 < g.P[0] && y1 >= 0 && y1 < g.P[1] && z1 >= 0 && z1 < g.P[2])
+                hit |= sigma_in[((long long)z1 * g.P[1] + y1) * g.P[0] + x1] > tau;
+        }
+    }
+    const unsigned long long m = __ballot(hit);
+    const int first = (threadIdx.x & 63) & ~(R4 - 1);      // the wave lane of this point's piece 0
+    const bool kept = ((m >> first) & ((1ull << R4) - 1ull)) != 0ull;
+    if (!live) return;
+    if (q == 0) sigma_out[j] = kept ? sigma_in[j] : 0.0f;
+    if (!kept) coef[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// ------------------------------------------------------------------------------------------------
 // mi_vox_render, mi_vox_render_sparse
 // ------------------------------------------------------------------------------------------------
 struct RenderArgs {
@@ -267,9 +379,7 @@ __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const float p = o[i] + mk * d[i];
-                const float gi = (p - g.lo[i]) * g.inv[i];
-                c[i] = min(max((int)floorf(gi), 0), g.res[i] - 1);
-                f[i] = fminf(fmaxf(gi - (float)c[i], 0.0f), 1.0f);
+                cell_of((p - g.lo[i]) * g.inv[i], g.res[i], c[i], f[i]);
             }
             if (a.use_skip) {
                 const int bx = c[0] >> 3, by = c[1] >> 3, bz = c[2] >> 3;
@@ -353,6 +463,12 @@ static int check_march(const char* who, const mi_vox_grid* grid, const mi_vox_re
 
 __host__ __device__ constexpr int record_bytes(int B, int fmt) {
     return fmt == MI_VOX_FMT_F32 ? 4 * record_floats(B) : fmt == MI_VOX_FMT_F16 ? 2 * record_floats(B) : 0;
+}
+
+// two arrays share a byte (the same array included)
+static inline bool overlap(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + nq && b < a + np;
 }
 
 static inline long long index_chunks(const Lattice& g) { return ((long long)g.P[0] * g.P[1] * g.P[2] + IDX_CHUNK - 1) / IDX_CHUNK; }
@@ -530,6 +646,58 @@ int mi_vox_pack(const mi_vox_grid* grid, int B, int fmt, const float* src_dev, c
     if (fmt == MI_VOX_FMT_F16) hipLaunchKernelGGL(pack_kernel<true>, blocks, dim3(THREADS), 0, st, src4, slot_dev, records, (long long)M, R4, table_dev);
     else hipLaunchKernelGGL(pack_kernel<false>, blocks, dim3(THREADS), 0, st, src4, slot_dev, records, (long long)M, R4, table_dev);
     VOX_LAUNCH_CHECK("pack_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_resample(const mi_vox_grid* src, const mi_vox_grid* dst, int B, const float* sigma_src_dev, const float* coef_src_dev, float* sigma_dst_dev,
+                    float* coef_dst_dev, void* stream) {
+    const char* who = "mi_vox_resample";
+    ResampleArgs a{};
+    if (int rc = check_grid("mi_vox_resample: source", src, &a.s)) return rc;
+    if (int rc = check_grid("mi_vox_resample: destination", dst, &a.d)) return rc;
+    if (int rc = check_basis(who, B)) return rc;
+    VOX_CHECK_ARG(sigma_src_dev && coef_src_dev && sigma_dst_dev && coef_dst_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(coef_src_dev, 16) && aligned(coef_dst_dev, 16) && aligned(sigma_src_dev, 4) && aligned(sigma_dst_dev, 4),
+                  "%s: coef must be 16-byte aligned, sigma 4-byte aligned", who);
+    const int R4 = record_floats(B) / 4;
+    const size_t Ns = (size_t)a.s.P[0] * a.s.P[1] * a.s.P[2], Nd = (size_t)a.d.P[0] * a.d.P[1] * a.d.P[2];
+    VOX_CHECK_ARG(!overlap(sigma_dst_dev, 4 * Nd, sigma_src_dev, 4 * Ns) && !overlap(sigma_dst_dev, 4 * Nd, coef_src_dev, 16 * Ns * R4) &&
+                      !overlap(coef_dst_dev, 16 * Nd * R4, sigma_src_dev, 4 * Ns) && !overlap(coef_dst_dev, 16 * Nd * R4, coef_src_dev, 16 * Ns * R4) &&
+                      !overlap(sigma_dst_dev, 4 * Nd, coef_dst_dev, 16 * Nd * R4),
+                  "%s: a destination array overlaps a source array or the other destination array: the source is read while the destination is written", who);
+    for (int i = 0; i < 3; ++i) a.step_d[i] = (dst->hi[i] - dst->lo[i]) / (float)dst->res[i];
+    a.sigma_s = sigma_src_dev; a.coef_s = reinterpret_cast<const float4*>(coef_src_dev);
+    a.sigma_d = sigma_dst_dev; a.coef_d = reinterpret_cast<float4*>(coef_dst_dev);
+    a.pieces = (long long)Nd * R4;
+    const dim3 blocks((unsigned)((a.pieces + THREADS - 1) / THREADS));
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 1) hipLaunchKernelGGL(resample_kernel<1>, blocks, dim3(THREADS), 0, st, a);
+    else if (B == 4) hipLaunchKernelGGL(resample_kernel<4>, blocks, dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL(resample_kernel<9>, blocks, dim3(THREADS), 0, st, a);
+    VOX_LAUNCH_CHECK("resample_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_prune(const mi_vox_grid* grid, int B, float tau, const float* sigma_in_dev, float* sigma_out_dev, float* coef_dev, void* stream) {
+    const char* who = "mi_vox_prune";
+    Lattice g;
+    if (int rc = check_grid(who, grid, &g)) return rc;
+    if (int rc = check_basis(who, B)) return rc;
+    VOX_CHECK_ARG(isfinite(tau) && tau >= 0.0f, "%s: tau=%g must be a finite number >= 0", who, (double)tau);
+    VOX_CHECK_ARG(sigma_in_dev && sigma_out_dev && coef_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(coef_dev, 16) && aligned(sigma_in_dev, 4) && aligned(sigma_out_dev, 4), "%s: coef must be 16-byte aligned, sigma 4-byte aligned", who);
+    const int R4 = record_floats(B) / 4;
+    const size_t N = (size_t)g.P[0] * g.P[1] * g.P[2];
+    VOX_CHECK_ARG(!overlap(sigma_out_dev, 4 * N, sigma_in_dev, 4 * N), "%s: sigma_out overlaps sigma_in: the stencil reads a point's neighbours", who);
+    VOX_CHECK_ARG(!overlap(coef_dev, 16 * N * R4, sigma_in_dev, 4 * N) && !overlap(coef_dev, 16 * N * R4, sigma_out_dev, 4 * N), "%s: coef overlaps a sigma plane", who);
+    const long long pieces = (long long)N * R4;
+    const dim3 blocks((unsigned)((pieces + THREADS - 1) / THREADS));
+    hipStream_t st = (hipStream_t)stream;
+    float4* coef4 = reinterpret_cast<float4*>(coef_dev);
+    if (B == 1) hipLaunchKernelGGL(prune_kernel<1>, blocks, dim3(THREADS), 0, st, g, tau, sigma_in_dev, sigma_out_dev, coef4, pieces);
+    else if (B == 4) hipLaunchKernelGGL(prune_kernel<4>, blocks, dim3(THREADS), 0, st, g, tau, sigma_in_dev, sigma_out_dev, coef4, pieces);
+    else hipLaunchKernelGGL(prune_kernel<9>, blocks, dim3(THREADS), 0, st, g, tau, sigma_in_dev, sigma_out_dev, coef4, pieces);
+    VOX_LAUNCH_CHECK("prune_kernel");
     return MI_VOX_OK;
 }
 

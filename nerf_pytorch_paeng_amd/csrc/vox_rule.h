@@ -1,5 +1,5 @@
 // vox_rule.h -- what csrc/vox.hip (the radiance-grid renderer) and csrc/voxgrad.hip (its backward pass) both need of THE RENDER RULE of
-// include/mi_nerf_vox.h, written once: the launch-shape constants, the record layout, the Lattice, the basis, the sum over a group's eight
+// include/mi_nerf_vox.h, written once: the launch-shape constants, the record layout, the Lattice, the basis, a point's cell and fraction, the sum over a group's eight
 // lanes, lane e's record fetch for the three storages, and on the host side the checks of a grid and of a march configuration.  Like
 // abi_error.h it knows no public header: the two libraries' grid and cfg structs reach it as template parameters, and each source
 // static_asserts the constants below against its own header.  Everything here is __device__ __forceinline__ or static / inline host
@@ -50,6 +50,13 @@ __device__ __forceinline__ void sh_basis(float x, float y, float z, float (&Y)[B
         Y[7] = -1.0925484f * (x * z);
         Y[8] = 0.54627422f * (x * x - y * y);
     }
+}
+
+// step 3's cell and fraction on one axis, from the lattice coordinate g_i = (p_i - lo_i) * inv_i: the renderer's sample and THE RESAMPLING
+// RULE's lattice point find their cell here
+__device__ __forceinline__ void cell_of(float gi, int res, int& c, float& f) {
+    c = min(max((int)floorf(gi), 0), res - 1);
+    f = fminf(fmaxf(gi - (float)c, 0.0f), 1.0f);
 }
 
 // the sum over a group's eight lanes, in the header's order: x neighbours, y neighbours, then the two halves.  Every lane ends with the
