@@ -5,7 +5,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
     python examples/train_eval_render.py [--steps 2000] [--size 64] [--out /tmp/nerf_demo] [--precision fp32|f16s] [--net-width 256]
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10] [--mesh-view]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
-                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY]
+                                             [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY] [--bake-optimizer adam|lazy]
                                              [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
@@ -26,6 +26,7 @@ are rendered from the grid as well, with no network, and the PSNR of the grid's 
 (baked_train.finetune: the backward pass of the grid renderer) and its PSNR on the test views is printed before and after;
 ``--bake-reg TV_SIGMA:TV_COEF:SPARSITY`` adds the lattice regularisers to those steps (total variation of the density plane and of the
 records, Cauchy sparsity of the density; e.g. 0.01:0.01:0.01) and is refused without ``--bake-finetune``.
+``--bake-optimizer lazy`` runs those steps with optim.LazyAdam on finetune's direct path (docs/design/26_lazy_optimizer.md); the default is torch.optim.Adam.
 ``--bake-levels RES:STEPS[,RES:STEPS...]`` trains the grid coarse to fine (baked_train.coarse_to_fine): the network is baked at the first
 level's resolution -- eight times fewer evaluations per halving -- and each level's steps are followed by a resample to the next
 (RadianceGrid.resample); the final level is ``--bake`` RES with ``--bake-finetune`` STEPS.  ``--bake-prune TAU`` ends every level with
@@ -71,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--bake-finetune", type=int, default=0, metavar="STEPS", help="after --bake (dense), fine-tune the grid on the training views for STEPS steps")
     ap.add_argument("--bake-reg", default=None, metavar="TV_SIGMA:TV_COEF:SPARSITY",
                     help="with --bake-finetune: weights of the total variation of the density plane and of the records and of the density's sparsity prior")
+    ap.add_argument("--bake-optimizer", choices=("adam", "lazy"), default="adam",
+                    help="with --bake-finetune: torch.optim.Adam (default) or optim.LazyAdam, which steps only the grid elements a gradient reached")
     ap.add_argument("--bake-levels", default=None, metavar="RES:STEPS[,RES:STEPS...]",
                     help="with --bake RES --bake-finetune STEPS: bake at the first level's resolution and train coarse to fine through these levels; the final level is RES with STEPS steps")
     ap.add_argument("--bake-prune", type=float, default=None, metavar="TAU", help="with --bake-finetune: after each level, clear density and records away from density above TAU")
@@ -245,6 +248,9 @@ def main(argv=None):
                     rgb = grid.render(view_rays(i_test), want_all=False).reshape(len(i_test), -1)
                 return [float(-10.0 * torch.log10(torch.mean((rgb[j] - images[i].to(dev).reshape(-1)) ** 2))) for j, i in enumerate(i_test)]
 
+            if a.bake_optimizer == "lazy":                                                     # the direct path: steps only where a gradient arrived
+                from nerf_pytorch_paeng_amd.optim import LazyAdam
+                bake_reg = dict(bake_reg, optimizer=LazyAdam)
             before = grid_psnr()
             t_ft = time.perf_counter()
             if bake_levels or a.bake_prune is not None:

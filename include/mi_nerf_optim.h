@@ -27,6 +27,21 @@
  * A launch serves at most MI_OPTIM_MAX_TENSORS consecutive tensors of one configuration; a longer or mixed list is split into several
  * launches inside the call.  Each workgroup takes one chunk of MI_OPTIM_CHUNK elements of one tensor; it uses 16-byte accesses when that
  * tensor's four addresses (p, g, m, v) are 16-byte aligned and 4-byte accesses for the whole tensor otherwise.
+ *
+ * THE LAZY UPDATE (mi_optim_adam_step_lazy), for a table of which a step's gradient reaches a small part.  An element is TOUCHED iff
+ * g != 0 as an IEEE comparison: -0.0 is untouched, NaN is touched and propagates as in PyTorch.
+ *     untouched:  p, m and v are neither read nor written.  Nothing decays for the skipped step and nothing catches up later: the element
+ *                 is exactly what it was when its last gradient arrived.
+ *     touched:    THE UPDATE with c = 1, by the same routine as the plain step; the bias corrections come from step[i], the TENSOR's step
+ *                 count (not the element's), a host array as in mi_optim_adam_step.  Then the clamp, p = p < p_min[i] ? p_min[i] : p (a NaN
+ *                 stays NaN; -inf: no clamp).  With consume = 1 the element's gradient is overwritten with +0.0f in the same pass: after
+ *                 the call the gradient tensor compares equal to zero everywhere and the next backward adds into it without a memset
+ *                 (the zero is stored per 16-byte piece: a -0.0 that shares a piece with a touched element becomes +0.0 as well).
+ *                 With consume = 0 no gradient byte changes.
+ * weight_decay != 0 is refused: a lazy decay has more than one meaning and none is chosen here.  The launch shape is THE TENSOR LIST's; a
+ * launch is split where p_min changes as it is where the configuration changes.  A thread reads its gradients first and reads p, m, v
+ * only for a 16-byte piece (the 4-byte path: an element) in which some g != 0; it stores only such a piece, and inside one the untouched
+ * components are stored back with the bits that were loaded.  An untouched chunk costs its 16 KiB of gradient reads and nothing else.
  */
 #ifndef MI_NERF_OPTIM_H
 #define MI_NERF_OPTIM_H
@@ -38,7 +53,7 @@
 extern "C" {
 #endif
 
-#define MI_OPTIM_ABI_VERSION 1
+#define MI_OPTIM_ABI_VERSION 2
 
 /* status codes (the values of mi_nerf.h) */
 #define MI_OPTIM_OK 0
@@ -82,6 +97,12 @@ const char* mi_optim_last_error(void);
 int mi_optim_adam_step(int n, float* const* params, const float* const* grads, const int64_t* numel, const int64_t* state_off,
                        const int64_t* step, float* exp_avg, float* exp_avg_sq, int64_t state_numel, const mi_optim_adam_cfg* cfgs, int n_cfg,
                        const int32_t* cfg_of, void* stream);
+
+/* THE LAZY UPDATE over THE TENSOR LIST, grads writable.  p_min: a host array of n floats (NULL: no clamp anywhere; a NaN is refused);
+ * consume: 0 / 1; every configuration's weight_decay must be 0. */
+int mi_optim_adam_step_lazy(int n, float* const* params, float* const* grads, const int64_t* numel, const int64_t* state_off,
+                            const int64_t* step, float* exp_avg, float* exp_avg_sq, int64_t state_numel, const mi_optim_adam_cfg* cfgs, int n_cfg,
+                            const int32_t* cfg_of, const float* p_min, int consume, void* stream);
 
 /* bytes of scratch mi_optim_grad_stats needs for this tensor list (16-byte aligned; one 16-byte partial per workgroup); 0 when an
  * argument is bad */

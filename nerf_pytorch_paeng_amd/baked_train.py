@@ -23,6 +23,7 @@ from typing import Optional
 import torch
 
 from . import _geo, _voxgrad, ops
+from .optim import LazyAdam
 from ._lib import MiNerfError, dev_ptr, stream_ptr
 from .baked import RadianceGrid, SparseRadianceGrid
 
@@ -177,6 +178,17 @@ def lattice_sparsity(grid: RadianceGrid, mask=None, scale: Optional[float] = Non
     return _lattice(grid, "sparsity", "sigma", 0.0, mask, scale, out, True)
 
 
+def _regularise(grid: RadianceGrid, masked: bool, n_points: int, tv_sigma: float, tv_coef: float, sparsity: float, tv_eps: float) -> None:
+    """finetune's regularisers: their gradients are ADDED into ``grid.sigma.grad`` / ``grid.coef.grad``; a weight of 0 makes no call."""
+    plane = True if masked else None
+    if tv_sigma:
+        _lattice(grid, "tv", "sigma", tv_eps, plane, tv_sigma / n_points, None, False)
+    if tv_coef:
+        _lattice(grid, "tv", "coef", tv_eps, plane, tv_coef / (n_points * 3 * grid.B), None, False)
+    if sparsity:
+        _lattice(grid, "sparsity", "sigma", 0.0, plane, sparsity / n_points, None, False)
+
+
 def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps: int, batch: int = 4096, lr_sigma: float = 0.05, lr_coef: float = 0.005,
              optimizer=torch.optim.Adam, rebuild_skip_every: int = 1, seed: int = 0, step: Optional[float] = None, near: float = 0.0,
              far: float = math.inf, T_min: float = 0.0, bg=(1.0, 1.0, 1.0), skip: bool = True, tv_sigma: float = 0.0, tv_coef: float = 0.0,
@@ -199,7 +211,13 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
     gradients of ``tv_sigma TV(sigma) / N``, ``tv_coef TV(coef) / (N 3 B)`` and ``sparsity SP / N`` are added, N the number of lattice
     points (known on the host: nothing synchronises), ``tv_eps`` the eps of the total variation.  Their mask is ``grid.skip`` on the steps that
     render with the plane and none otherwise.  The returned losses stay the data loss; with all three weights 0 no regulariser is
-    called."""
+    called.
+
+    ``optimizer=optim.LazyAdam`` takes THE DIRECT PATH (docs/design/26_lazy_optimizer.md): ``.grad`` of both tensors becomes a zero buffer
+    once; a step renders under ``no_grad``, forms ``g_rgb = 2 (rgb - target) / (3 n)`` itself, has ``backward`` and the regularisers add
+    straight into those buffers, and ends in ``LazyAdam.step`` with ``clamp_min=0`` on sigma and ``consume=True``, which updates the touched
+    elements and leaves the buffers zero.  No ``zero_grad``, no ``clamp_``, no autograd node, no ``zeros_like``: nothing sweeps the grid
+    but the optimiser's read of the gradients.  An element no ray reaches stays what it is, moments included."""
     if not all(isinstance(w, (int, float)) and math.isfinite(w) and w >= 0 for w in (tv_sigma, tv_coef, sparsity)):
         raise MiNerfError(f"tv_sigma={tv_sigma}, tv_coef={tv_coef} and sparsity={sparsity} must be finite numbers >= 0")
     dev = _check(grid, rays)
@@ -215,25 +233,36 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
     grid.sigma.requires_grad_(True)
     grid.coef.requires_grad_(True)
     opt = optimizer([dict(params=[grid.sigma], lr=lr_sigma), dict(params=[grid.coef], lr=lr_coef)])
+    lazy = isinstance(opt, LazyAdam)
     losses = []
     try:
+        if lazy:                                                             # the direct path: no dense sweep of the grid per step
+            opt.param_groups[0]["clamp_min"] = 0.0                           # sigma >= 0, applied where the step lands
+            opt.consume = True                                               # the step leaves the gradients zero: no zero_grad
+            grid.sigma.grad, grid.coef.grad = torch.zeros_like(grid.sigma), torch.zeros_like(grid.coef)
+            kw = dict(step=step, near=near, far=far, T_min=T_min, bg=tuple(float(v) for v in bg))
         for it in range(steps):
             fresh = it % rebuild_skip_every == 0
             if fresh and skip:
                 grid.build_skip()
             idx = torch.randint(N, (min(batch, N),), generator=gen, device=dev)
+            if lazy:
+                with torch.no_grad():
+                    r = rays[idx]
+                    rgb = grid.render(r, skip=skip and fresh, **kw)[0]
+                    diff = rgb - target[idx]
+                    loss = torch.mean(diff ** 2)
+                    backward(grid, r, (diff * (2.0 / (3 * r.shape[0]))).contiguous(), d_sigma=grid.sigma.grad, d_coef=grid.coef.grad,
+                             skip=skip and fresh, **kw)
+                    _regularise(grid, skip and fresh, n_points, tv_sigma, tv_coef, sparsity, tv_eps)
+                    opt.step()
+                losses.append(loss)
+                continue
             rgb = render(grid, rays[idx], step=step, near=near, far=far, T_min=T_min, bg=bg, skip=skip and fresh)[0]
             loss = torch.mean((rgb - target[idx]) ** 2)
             opt.zero_grad(set_to_none=False)
             loss.backward()
-            if tv_sigma or tv_coef or sparsity:
-                plane = True if skip and fresh else None
-                if tv_sigma:
-                    _lattice(grid, "tv", "sigma", tv_eps, plane, tv_sigma / n_points, None, False)
-                if tv_coef:
-                    _lattice(grid, "tv", "coef", tv_eps, plane, tv_coef / (n_points * 3 * grid.B), None, False)
-                if sparsity:
-                    _lattice(grid, "sparsity", "sigma", 0.0, plane, sparsity / n_points, None, False)
+            _regularise(grid, skip and fresh, n_points, tv_sigma, tv_coef, sparsity, tv_eps)
             opt.step()
             with torch.no_grad():
                 grid.sigma.clamp_(min=0.0)

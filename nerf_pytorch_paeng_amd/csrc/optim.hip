@@ -7,6 +7,10 @@
 //                            when p, g, m and v of that tensor are 16-byte aligned, 4-byte accesses otherwise.  16 elements per thread, all
 //                            loads issued before the first store.  GUARDED: the clip coefficient and the skip word come from the control
 //                            block, the bias corrections from the per-tensor device state.
+//   lazy_adam_kernel         THE LAZY UPDATE on the same mapping: a thread loads its 16 gradients first and touches p, m, v only for a
+//                            16-byte piece (4-byte path: an element) in which some g != 0; untouched components of a touched piece are
+//                            stored back as loaded (a select), a touched gradient is overwritten with +0 under `consume`.  Whole waves
+//                            and chunks fall through on one predicate: an untouched chunk is 16 KiB of gradient reads and nothing else.
 //   grad_partial_kernel      the same mapping over the gradients alone: (sum of squares in double, non-finite count) of the chunk ->
 //                            scratch[chunk], thread-sequential, then lanes, then the four waves: a fixed order.
 //   grad_finish_kernel       one workgroup: adds the partials (a contiguous run per thread in index order, then a fixed tree), writes the
@@ -16,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 #include "../../include/mi_nerf_optim.h"
 #include "abi_error.h"
 
@@ -74,6 +79,8 @@ struct Table {
     const unsigned* control;
     long long chunk_base;                // grad_partial_kernel: index of this launch's first partial
     void* partial;
+    float p_min;                         // lazy_adam_kernel: the launch's clamp (-inf: none)
+    int consume;                         // lazy_adam_kernel: 1: a touched gradient is overwritten with +0
 };
 static_assert(sizeof(Table) <= 4096, "the table travels as kernel arguments");
 
@@ -176,6 +183,107 @@ __global__ __launch_bounds__(THREADS) void adam_kernel(const Table a) {
                 if (e < cnt) {
                     adam_elem<GUARDED>(P[i], G[i], M[i], V[i], c);
                     p[e] = P[i]; m[e] = M[i]; v[e] = V[i];
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// THE LAZY UPDATE
+// ------------------------------------------------------------------------------------------------
+// one touched element: THE UPDATE, then the clamp (a NaN compares false and stays)
+__device__ __forceinline__ void lazy_elem(float& p, float g, float& m, float& v, const Consts& c, float p_min) {
+    float pn = p, mn = m, vn = v;
+    adam_elem<false>(pn, g, mn, vn, c);
+    pn = pn < p_min ? p_min : pn;
+    const bool touched = g != 0.0f;                               // -0.0 is untouched, NaN is touched
+    p = touched ? pn : p;                                         // selects: an untouched component of a touched piece is stored back
+    m = touched ? mn : m;                                         // with the bits that were loaded
+    v = touched ? vn : v;
+}
+
+__device__ __forceinline__ bool any_touched(const float4& g) { return g.x != 0.0f || g.y != 0.0f || g.z != 0.0f || g.w != 0.0f; }
+
+__global__ __launch_bounds__(THREADS) void lazy_adam_kernel(const Table a) {
+    const int tid = threadIdx.x;
+    const int t = find_tensor(a, blockIdx.x);
+    const long long c0 = (long long)(blockIdx.x - a.prefix[t]) * CHUNK;
+    const long long left = a.numel[t] - c0;
+    const int cnt = left < CHUNK ? (int)left : CHUNK;
+    Consts c;
+    c.beta2 = a.beta2; c.omb1 = a.omb1; c.omb2 = a.omb2; c.eps = a.eps; c.wd = 0.0f; c.decay_mul = 1.0f;
+    c.wd_mode = 0;
+    c.coef = 1.0f;
+    c.sqrt_bc2 = a.sqrt_bc2[t];
+    c.step_size = a.step_size[t];
+    const float p_min = a.p_min;
+    const bool consume = a.consume != 0;
+    float* p = a.p[t] + c0;
+    float* g = const_cast<float*>(a.g[t]) + c0;                    // the lazy entry takes its gradients writable
+    float* m = a.m + a.off[t] + c0;
+    float* v = a.v + a.off[t] + c0;
+    if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v)) {
+        float4 G[4];
+        bool hit[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                              // every gradient load first: the untouched chunk ends after them
+            const int e = (i * THREADS + tid) * 4;
+            G[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (e + 4 <= cnt) G[i] = *reinterpret_cast<const float4*>(g + e);
+            hit[i] = any_touched(G[i]);
+        }
+        float4 P[4], M[4], V[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = (i * THREADS + tid) * 4;
+            if (hit[i]) {
+                P[i] = *reinterpret_cast<const float4*>(p + e);
+                M[i] = *reinterpret_cast<const float4*>(m + e);
+                V[i] = *reinterpret_cast<const float4*>(v + e);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = (i * THREADS + tid) * 4;
+            if (hit[i]) {
+                lazy_elem(P[i].x, G[i].x, M[i].x, V[i].x, c, p_min);
+                lazy_elem(P[i].y, G[i].y, M[i].y, V[i].y, c, p_min);
+                lazy_elem(P[i].z, G[i].z, M[i].z, V[i].z, c, p_min);
+                lazy_elem(P[i].w, G[i].w, M[i].w, V[i].w, c, p_min);
+                *reinterpret_cast<float4*>(p + e) = P[i];
+                *reinterpret_cast<float4*>(m + e) = M[i];
+                *reinterpret_cast<float4*>(v + e) = V[i];
+                if (consume) *reinterpret_cast<float4*>(g + e) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            } else if (e < cnt && e + 4 > cnt) {                   // the tensor's last one to three elements
+                for (int k = e; k < cnt; ++k) {
+                    const float gk = g[k];
+                    if (gk != 0.0f) {
+                        float pk = p[k], mk = m[k], vk = v[k];
+                        lazy_elem(pk, gk, mk, vk, c, p_min);
+                        p[k] = pk; m[k] = mk; v[k] = vk;
+                        if (consume) g[k] = 0.0f;
+                    }
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float G[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = (j * 4 + i) * THREADS + tid;
+                G[i] = e < cnt ? g[e] : 0.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = (j * 4 + i) * THREADS + tid;
+                if (G[i] != 0.0f) {
+                    float pe = p[e], me = m[e], ve = v[e];
+                    lazy_elem(pe, G[i], me, ve, c, p_min);
+                    p[e] = pe; m[e] = me; v[e] = ve;
+                    if (consume) g[e] = 0.0f;
                 }
             }
         }
@@ -340,11 +448,15 @@ static int check_list(const char* who, int n, float* const* params, bool with_pa
     return MI_OPTIM_OK;
 }
 
-// the launch that starts at tensor lo: consecutive tensors of one configuration, at most MAXT, at most 2^31 - 1 chunks
-static int batch_end(int lo, int n, const int64_t* numel, const int32_t* cfg_of) {
+// the launch that starts at tensor lo: consecutive tensors of one configuration (and, lazy, of one p_min: compared as bits, a NaN was
+// refused), at most MAXT, at most 2^31 - 1 chunks
+static inline uint32_t float_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static int batch_end(int lo, int n, const int64_t* numel, const int32_t* cfg_of, const float* p_min = nullptr) {
     long long chunks = 0;
     int hi = lo;
-    while (hi < n && hi - lo < MAXT && (!cfg_of || cfg_of[hi] == cfg_of[lo]) && chunks + chunks_of(numel[hi]) <= 0x7fffffffLL) chunks += chunks_of(numel[hi++]);
+    while (hi < n && hi - lo < MAXT && (!cfg_of || cfg_of[hi] == cfg_of[lo]) && (!p_min || float_bits(p_min[hi]) == float_bits(p_min[lo])) &&
+           chunks + chunks_of(numel[hi]) <= 0x7fffffffLL)
+        chunks += chunks_of(numel[hi++]);
     return hi > lo ? hi : lo + 1;        // (one tensor alone never exceeds the bound: numel <= 2^40 is 2^28 chunks)
 }
 
@@ -368,16 +480,21 @@ static void fill_cfg(Table& t, const mi_optim_adam_cfg& c) {
     t.decay_mul = (float)(1.0 - c.lr * c.weight_decay);
 }
 
-static int step_launches(bool guarded, int n, float* const* params, const float* const* grads, const int64_t* numel, const int64_t* state_off,
+enum StepKind { PLAIN, GUARDED, LAZY };
+
+static int step_launches(StepKind kind, int n, float* const* params, const float* const* grads, const int64_t* numel, const int64_t* state_off,
                          const int64_t* step, float* exp_avg, float* exp_avg_sq, const mi_optim_adam_cfg* cfgs, const int32_t* cfg_of,
-                         const int32_t* slot, const float* tstate, const void* control, hipStream_t st) {
+                         const int32_t* slot, const float* tstate, const void* control, const float* p_min, int consume, hipStream_t st) {
+    const bool guarded = kind == GUARDED;
     for (int lo = 0; lo < n;) {
-        const int hi = batch_end(lo, n, numel, cfg_of);
+        const int hi = batch_end(lo, n, numel, cfg_of, kind == LAZY ? p_min : nullptr);
         const mi_optim_adam_cfg& c = cfgs[cfg_of ? cfg_of[lo] : 0];
         Table t{};
         const long long chunks = fill_shape(t, lo, hi, grads, numel);
         fill_cfg(t, c);
         t.m = exp_avg; t.v = exp_avg_sq; t.tstate = tstate; t.control = (const unsigned*)control;
+        t.p_min = p_min ? p_min[lo] : -INFINITY;
+        t.consume = consume;
         for (int i = lo; i < hi; ++i) {
             t.p[i - lo] = params[i];
             t.off[i - lo] = state_off[i];
@@ -390,7 +507,8 @@ static int step_launches(bool guarded, int n, float* const* params, const float*
             }
         }
         if (chunks > 0) {
-            if (guarded) hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)chunks), dim3(THREADS), 0, st, t);
+            if (kind == LAZY) hipLaunchKernelGGL(lazy_adam_kernel, dim3((unsigned)chunks), dim3(THREADS), 0, st, t);
+            else if (guarded) hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)chunks), dim3(THREADS), 0, st, t);
             else hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)chunks), dim3(THREADS), 0, st, t);
             OPTIM_LAUNCH_CHECK("adam_kernel");
         }
@@ -417,7 +535,24 @@ int mi_optim_adam_step(int n, float* const* params, const float* const* grads, c
     OPTIM_CHECK_ARG(step != nullptr, "%s: step is NULL", who);
     for (int i = 0; i < n; ++i)
         OPTIM_CHECK_ARG(step[i] >= 1 && step[i] <= ((int64_t)1 << 53), "%s: step[%d]=%lld: the step being taken is at least 1", who, i, (long long)step[i]);
-    return step_launches(false, n, params, grads, numel, state_off, step, exp_avg, exp_avg_sq, cfgs, cfg_of, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return step_launches(PLAIN, n, params, grads, numel, state_off, step, exp_avg, exp_avg_sq, cfgs, cfg_of, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+int mi_optim_adam_step_lazy(int n, float* const* params, float* const* grads, const int64_t* numel, const int64_t* state_off,
+                            const int64_t* step, float* exp_avg, float* exp_avg_sq, int64_t state_numel, const mi_optim_adam_cfg* cfgs, int n_cfg,
+                            const int32_t* cfg_of, const float* p_min, int consume, void* stream) {
+    const char* who = "mi_optim_adam_step_lazy";
+    OPTIM_CHECK_ARG(exp_avg && exp_avg_sq && aligned(exp_avg, 4) && aligned(exp_avg_sq, 4) && state_numel >= 0, "%s: the state arenas must be given, 4-byte aligned", who);
+    if (int rc = check_list(who, n, params, true, grads, numel, state_off, state_numel, cfgs, n_cfg, cfg_of, nullptr, false, 0)) return rc;
+    OPTIM_CHECK_ARG(step != nullptr, "%s: step is NULL", who);
+    for (int i = 0; i < n; ++i)
+        OPTIM_CHECK_ARG(step[i] >= 1 && step[i] <= ((int64_t)1 << 53), "%s: step[%d]=%lld: the step being taken is at least 1", who, i, (long long)step[i]);
+    for (int k = 0; k < n_cfg; ++k)
+        OPTIM_CHECK_ARG(cfgs[k].weight_decay == 0.0, "%s: cfgs[%d].weight_decay=%g: a lazy weight decay is not defined, it must be 0", who, k, cfgs[k].weight_decay);
+    OPTIM_CHECK_ARG(consume == 0 || consume == 1, "%s: consume=%d must be 0 or 1", who, consume);
+    for (int i = 0; p_min && i < n; ++i)
+        OPTIM_CHECK_ARG(!isnan(p_min[i]), "%s: p_min[%d] is NaN (-inf: no clamp)", who, i);
+    return step_launches(LAZY, n, params, grads, numel, state_off, step, exp_avg, exp_avg_sq, cfgs, cfg_of, nullptr, nullptr, nullptr, p_min, consume, (hipStream_t)stream);
 }
 
 size_t mi_optim_grad_stats_scratch_bytes(int n, const int64_t* numel) {
@@ -478,7 +613,7 @@ int mi_optim_adam_step_guarded(int n, float* const* params, const float* const* 
     OPTIM_CHECK_ARG(exp_avg && exp_avg_sq && aligned(exp_avg, 4) && aligned(exp_avg_sq, 4) && state_numel >= 0, "%s: the state arenas must be given, 4-byte aligned", who);
     if (int rc = check_list(who, n, params, true, grads, numel, state_off, state_numel, cfgs, n_cfg, cfg_of, slot, true, n_slots)) return rc;
     OPTIM_CHECK_ARG(tstate && control && aligned(tstate, 16) && aligned(control, 16), "%s: tstate and control must be given, 16-byte aligned", who);
-    return step_launches(true, n, params, grads, numel, state_off, nullptr, exp_avg, exp_avg_sq, cfgs, cfg_of, slot, tstate, control, (hipStream_t)stream);
+    return step_launches(GUARDED, n, params, grads, numel, state_off, nullptr, exp_avg, exp_avg_sq, cfgs, cfg_of, slot, tstate, control, nullptr, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -5,6 +5,9 @@ a gradient in one library call (plain mode), or in two when the step is guarded 
 whose gradients are not finite, both decided on the device, without a host synchronisation.  Its ``state_dict()`` is ``torch.optim.Adam``'s,
 in both directions.  There is no fallback: anything but contiguous fp32 tensors on a HIP device raises ``MiNerfError``.
 
+``LazyAdam`` is its sparse counterpart for a large table that a step's gradient reaches in a few places (a radiance grid): it steps only the
+elements whose gradient is not zero and leaves every other bit alone (docs/design/26_lazy_optimizer.md).
+
 ``CosineAnnealingWarmupRestarts`` is the schedule of the reference's training recipe, written from its definition on the pure function
 ``lr_at``; it drives any ``torch.optim.Optimizer``.
 """
@@ -50,28 +53,28 @@ class FusedAdam(torch.optim.Optimizer):
     # ------------------------------------------------------------------------------------------------
     # checks
     # ------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _check_group(group) -> None:
+    @classmethod
+    def _check_group(cls, group) -> None:
         if group.get("amsgrad") or group.get("maximize") or group.get("differentiable"):
-            raise MiNerfError("FusedAdam: amsgrad, maximize and differentiable are not built")
+            raise MiNerfError(f"{cls.__name__}: amsgrad, maximize and differentiable are not built")
         lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
         if isinstance(lr, torch.Tensor) or isinstance(b1, torch.Tensor) or isinstance(b2, torch.Tensor):
-            raise MiNerfError("FusedAdam: lr and betas are Python numbers (the constants of the update are formed on the host)")
+            raise MiNerfError(f"{cls.__name__}: lr and betas are Python numbers (the constants of the update are formed on the host)")
         if not (math.isfinite(lr) and lr >= 0.0 and math.isfinite(eps) and eps >= 0.0 and math.isfinite(wd) and wd >= 0.0):
-            raise MiNerfError(f"FusedAdam: lr={lr}, eps={eps}, weight_decay={wd} must be finite and not negative")
+            raise MiNerfError(f"{cls.__name__}: lr={lr}, eps={eps}, weight_decay={wd} must be finite and not negative")
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
-            raise MiNerfError(f"FusedAdam: betas {(b1, b2)} must lie in [0, 1)")
+            raise MiNerfError(f"{cls.__name__}: betas {(b1, b2)} must lie in [0, 1)")
 
-    @staticmethod
-    def _check_tensor(t: torch.Tensor, what: str) -> None:
+    @classmethod
+    def _check_tensor(cls, t: torch.Tensor, what: str) -> None:
         if not t.is_cuda:
-            raise MiNerfError(f"FusedAdam: {what} must live on a HIP device (got {t.device}); there is no CPU fallback")
+            raise MiNerfError(f"{cls.__name__}: {what} must live on a HIP device (got {t.device}); there is no CPU fallback")
         if t.is_sparse or t.layout != torch.strided:
-            raise MiNerfError(f"FusedAdam: {what} is sparse; only dense tensors are built")
+            raise MiNerfError(f"{cls.__name__}: {what} is sparse; only dense tensors are built")
         if t.dtype != torch.float32:
-            raise MiNerfError(f"FusedAdam: {what} must be torch.float32 (got {t.dtype})")
+            raise MiNerfError(f"{cls.__name__}: {what} must be torch.float32 (got {t.dtype})")
         if not t.is_contiguous():
-            raise MiNerfError(f"FusedAdam: {what} must be contiguous")
+            raise MiNerfError(f"{cls.__name__}: {what} must be contiguous")
 
     # ------------------------------------------------------------------------------------------------
     # the arenas: every parameter of every group owns a run of both, 16-byte aligned, from the first step on
@@ -83,12 +86,12 @@ class FusedAdam(torch.optim.Optimizer):
         """Size the arenas and the device words for the parameters as they stand (again after add_param_group: what was there is kept)."""
         params = self._all_params()
         if not params:
-            raise MiNerfError("FusedAdam: no parameters")
+            raise MiNerfError(f"{type(self).__name__}: no parameters")
         for p in params:
             self._check_tensor(p, "a parameter")
         dev = params[0].device
         if any(p.device != dev for p in params):
-            raise MiNerfError("FusedAdam: all parameters must live on one device")
+            raise MiNerfError(f"{type(self).__name__}: all parameters must live on one device")
         kept = {p: (st["exp_avg"].clone(), st["exp_avg_sq"].clone()) for p, st in self.state.items() if "exp_avg" in st} if self._slot else {}
         old_rows = self._tstate[[self._slot[p] for p in kept]].clone() if kept else None
         old_steps = [self._steps[self._slot[p]] for p in kept]
@@ -128,12 +131,9 @@ class FusedAdam(torch.optim.Optimizer):
     # ------------------------------------------------------------------------------------------------
     # the step
     # ------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _collect(self):
+        """What a step hands to the library: the parameters that have a gradient, their slots, and the host arrays of the call (rebuilt only
+        when an address moved).  -> (ps, slots, cfgs), or None when no parameter has a gradient."""
         for group in self.param_groups:
             self._check_group(group)
         self._ensure_layout()
@@ -146,14 +146,14 @@ class FusedAdam(torch.optim.Optimizer):
                 self._check_tensor(p, "a parameter")
                 self._check_tensor(g, "a gradient")
                 if g.device != self._device or p.device != self._device or g.shape != p.shape:
-                    raise MiNerfError("FusedAdam: a parameter or gradient moved or changed shape after the first step")
+                    raise MiNerfError(f"{type(self).__name__}: a parameter or gradient moved or changed shape after the first step")
                 ps.append(p)
                 gs.append(g)
                 slots.append(self._slot[p])
                 cfg_of.append(gi)
         n = len(ps)
         if n == 0:
-            return loss
+            return None
         key = (tuple(p.data_ptr() for p in ps), tuple(g.data_ptr() for g in gs), tuple(slots), tuple(cfg_of))
         if key != self._key:                                                 # the host arrays of the call, rebuilt only when an address moved
             self._arr = ((C.c_void_p * n)(*key[0]), (C.c_void_p * n)(*key[1]), (C.c_int64 * n)(*[p.numel() for p in ps]),
@@ -164,12 +164,33 @@ class FusedAdam(torch.optim.Optimizer):
                     st = self.state[p]
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
                     st["exp_avg"], st["exp_avg_sq"] = self._views(p)
-        a_p, a_g, a_numel, a_off, a_cfg, a_slot, a_step = self._arr
         n_cfg = len(self.param_groups)
         cfgs = (_optim.AdamCfg * n_cfg)()
         for c, group in zip(cfgs, self.param_groups):
             c.size, c.decoupled = C.sizeof(_optim.AdamCfg), int(bool(group.get("decoupled_weight_decay", False)))
             c.lr, (c.beta1, c.beta2), c.eps, c.weight_decay = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+        return ps, slots, cfgs
+
+    def _count_steps(self, slots):
+        """Plain mode's bookkeeping: every slot that steps is one step further, and the call's step array says so."""
+        steps, a_step = self._steps, self._arr[6]
+        for i, s in enumerate(slots):
+            steps[s] += 1
+            a_step[i] = steps[s]
+        return a_step
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        got = self._collect()
+        if got is None:
+            return loss
+        ps, slots, cfgs = got
+        n, n_cfg = len(ps), len(cfgs)
+        a_p, a_g, a_numel, a_off, a_cfg, a_slot, a_step = self._arr
         L, dev = _optim.lib(), self._device
         m, v = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
         with torch.cuda.device(dev):
@@ -182,10 +203,7 @@ class FusedAdam(torch.optim.Optimizer):
                 _optim.check(L.mi_optim_adam_step_guarded(n, a_p, a_g, a_numel, a_off, m, v, self._total, cfgs, n_cfg, a_cfg, a_slot, len(self._slot), ts, ctl,
                                                           stream), "mi_optim_adam_step_guarded")
             else:
-                steps = self._steps
-                for i, s in enumerate(slots):
-                    steps[s] += 1
-                    a_step[i] = steps[s]
+                a_step = self._count_steps(slots)
                 _optim.check(L.mi_optim_adam_step(n, a_p, a_g, a_numel, a_off, a_step, m, v, self._total, cfgs, n_cfg, a_cfg, stream), "mi_optim_adam_step")
         torch.autograd.graph.increment_version(ps)                           # the kernel wrote behind autograd's back: caches keyed on _version must see it
         return loss
@@ -238,9 +256,9 @@ class FusedAdam(torch.optim.Optimizer):
         rows = torch.zeros(len(self._slot), _optim.TSTATE_WORDS, dtype=torch.float32)
         for p, st in loaded.items():
             if not {"step", "exp_avg", "exp_avg_sq"} <= set(st):
-                raise MiNerfError(f"FusedAdam.load_state_dict: a parameter's state has the keys {sorted(st)}, expected step, exp_avg, exp_avg_sq")
+                raise MiNerfError(f"{type(self).__name__}.load_state_dict: a parameter's state has the keys {sorted(st)}, expected step, exp_avg, exp_avg_sq")
             if "max_exp_avg_sq" in st:
-                raise MiNerfError("FusedAdam.load_state_dict: the checkpoint was written with amsgrad, which is not built")
+                raise MiNerfError(f"{type(self).__name__}.load_state_dict: the checkpoint was written with amsgrad, which is not built")
             m, v = self._views(p)
             m.copy_(st["exp_avg"])
             v.copy_(st["exp_avg_sq"])
@@ -249,6 +267,67 @@ class FusedAdam(torch.optim.Optimizer):
             rows[self._slot[p], 0] = float(step)
             self.state[p] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
         self._tstate.copy_(rows)
+
+
+class LazyAdam(FusedAdam):
+    """Adam that steps only where a gradient arrived (THE LAZY UPDATE of include/mi_nerf_optim.h, docs/design/26_lazy_optimizer.md): an
+    element whose gradient is zero (``g != 0`` is false; -0.0 counts as zero) keeps the bits of its parameter and of both moments, and
+    nothing catches up later.  Made for a table of which a step's gradient reaches a few per cent, a radiance grid's records; the bias
+    corrections come from the tensor's step count.  ``clamp_min`` (per group; None: no clamp) is applied to the touched elements after the
+    update.  ``consume=True`` overwrites every touched gradient element with +0 in the same pass: ``p.grad`` is then a persistent
+    accumulator that the next backward adds into, and ``zero_grad`` is not needed (``zero_grad(set_to_none=True)`` would discard the
+    buffer).  Arenas, step bookkeeping and ``state_dict`` are ``FusedAdam``'s: a checkpoint moves between this class, ``FusedAdam`` and
+    ``torch.optim.Adam``.  A weight decay is refused: a lazy decay has more than one meaning and none is chosen here."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, clamp_min=None, consume=True, weight_decay=0):
+        if weight_decay != 0:
+            raise MiNerfError(f"LazyAdam: weight_decay={weight_decay} is refused (a lazy weight decay is not defined)")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=0)
+        self.consume = bool(consume)
+        self.defaults["clamp_min"] = clamp_min                               # what add_param_group gives a group that names none
+        for group in self.param_groups:
+            group.setdefault("clamp_min", clamp_min)
+            self._check_group(group)
+
+    @classmethod
+    def _check_group(cls, group) -> None:
+        super()._check_group(group)
+        if group["weight_decay"] != 0:
+            raise MiNerfError(f"{cls.__name__}: weight_decay={group['weight_decay']} is refused (a lazy weight decay is not defined)")
+        lo = group.get("clamp_min")
+        if lo is not None and (isinstance(lo, torch.Tensor) or math.isnan(lo)):
+            raise MiNerfError(f"{cls.__name__}: clamp_min={lo} must be a Python number, not NaN (None: no clamp)")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        got = self._collect()
+        if got is None:
+            return loss
+        ps, slots, cfgs = got
+        n, n_cfg = len(ps), len(cfgs)
+        a_p, a_g, a_numel, a_off, a_cfg, _, _ = self._arr
+        lows = [self.param_groups[gi].get("clamp_min") for gi in a_cfg]
+        p_min = None if all(lo is None for lo in lows) else (C.c_float * n)(*[-math.inf if lo is None else float(lo) for lo in lows])
+        a_step = self._count_steps(slots)
+        dev = self._device
+        with torch.cuda.device(dev):
+            _optim.check(_optim.lib().mi_optim_adam_step_lazy(n, a_p, a_g, a_numel, a_off, a_step, self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
+                                                              self._total, cfgs, n_cfg, a_cfg, p_min, int(self.consume), stream_ptr(dev)),
+                         "mi_optim_adam_step_lazy")
+        torch.autograd.graph.increment_version(ps)
+        return loss
+
+    def load_state_dict(self, state_dict) -> None:
+        """As ``FusedAdam.load_state_dict``; a group of a checkpoint that names no ``clamp_min`` (one written by ``torch.optim.Adam`` or
+        ``FusedAdam``) keeps the one this optimiser's group had."""
+        lows = [group.get("clamp_min") for group in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, lo in zip(self.param_groups, lows):
+            group.setdefault("clamp_min", lo)
 
 
 # ---------------------------------------------------------------------------------------------------
