@@ -68,7 +68,7 @@ def composite_geo_backward(raw: torch.Tensor, z: torch.Tensor, rays_or_d: torch.
 
 
 # ---------------------------------------------------------------------------------------------------
-# the compositing pair of the training nodes (train_path._RenderTrain, occupancy_train._RenderTrainOcc)
+# the compositing pair of the training node (train_path._RenderTrain, whichever route runs its networks)
 # ---------------------------------------------------------------------------------------------------
 def _grad(g: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return None if g is None else g.contiguous().float()

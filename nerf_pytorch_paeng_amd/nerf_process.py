@@ -5,7 +5,7 @@ Same function names, positional arguments and return structures as the reference
 ``sample_pdf``, ``ndc_rays``), executed by hand-written HIP kernels through ``libmi_nerf.so``.
 Keyword-only extras (``t_rand=``, ``u=``, ``seed=``, ``ray_offset=``) make the randomness explicit;
 ``occupancy=`` (an ``occupancy.OccupancyGrid``) skips the networks at samples the grid marks empty (inference only;
-``train_occupancy=`` is the same grid for the training path, occupancy_train.py):
+``train_occupancy=`` is the same grid for the training path, the node's route of occupancy_train.py):
 the reference draws unseeded ``torch.rand`` (nerf_process.py:58-60,162-163); here the default is a
 counter-based generator keyed on (seed, global ray index, sample index), so a frame renders
 identically however its rays are chunked or sharded across GPUs.
@@ -51,11 +51,7 @@ def _next_seed(seed: Optional[int]) -> int:
     return s
 
 
-def _det(opts) -> bool:
-    # the reference compares the raw attribute with 0. (nerf_process.py:65); a value read from a config
-    # file can be a string (config.py:76 has no type=), for which `== 0.` is False
-    p = getattr(opts, "perturb", 1.0)
-    return isinstance(p, (int, float)) and p == 0.0
+_det = ops.deterministic
 
 
 # --------------------------------------------------------------------------------------------------
@@ -219,8 +215,7 @@ def _train_occupancy_arg(grid, training: bool, prec: ops.Precision):
     """``train_occupancy=``: None, or an OccupancyGrid for the training path (occupancy_train.py) -- gradients enabled, fp32 or f16s."""
     if grid is None:
         return None
-    if not isinstance(grid, occ.OccupancyGrid):
-        raise MiNerfError(f"train_occupancy must be an occupancy.OccupancyGrid, got {type(grid).__name__}")
+    occupancy_train.check_grid(grid)
     if not training:
         raise MiNerfError("train_occupancy= is a training feature: gradients are disabled or no parameter of the model requires them "
                           "(under torch.no_grad() render with occupancy=)")
@@ -242,9 +237,17 @@ def _geometry_kw(geometry, ray_grad=False) -> Dict[str, bool]:
     return {**({"geometry": True} if geometry else {}), **({"ray_grad": True} if ray_grad else {})}
 
 
+def _render_train(rays, model, opts, train_occupancy, t_rand, u, seed: int, ray_offset: int, f16s: bool, geometry, ray_grad):
+    """The training call of ``render_rays`` and of every slab: one node, its route through the grid when ``train_occupancy`` is one
+    (what occupancy_train.render_train calls)."""
+    grid = {} if train_occupancy is None else {"grid": train_occupancy}
+    return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=seed, ray_offset=ray_offset, f16s=f16s,
+                                   **_geometry_kw(geometry, ray_grad), **grid)
+
+
 def _ray_grad_arg(ray_grad, train_occupancy) -> bool:
     if ray_grad and train_occupancy is not None:
-        raise MiNerfError("ray_grad=True with train_occupancy= is not built: the occupancy-training node differentiates the parameters only")
+        raise MiNerfError(train_path.RAY_GRAD_WITH_GRID)
     return bool(ray_grad)
 
 
@@ -267,11 +270,7 @@ def render_rays(rays, model, posenc, opts, *, t_rand=None, u=None, seed=None, ra
         train_f16s = _train_f16s(prec, return_intermediates)
         if rays.dim() != 2 or rays.shape[1] != 6:
             raise MiNerfError(f"rays must be [n, 6] (o, d), got {tuple(rays.shape)}")
-        if train_occupancy is not None:
-            return occupancy_train.render_train(rays, model, opts, train_occupancy, t_rand=t_rand, u=u, seed=_next_seed(seed),
-                                                ray_offset=int(ray_offset), f16s=train_f16s, **_geometry_kw(geometry))
-        return train_path.render_train(rays, model, opts, t_rand=t_rand, u=u, seed=_next_seed(seed), ray_offset=int(ray_offset), f16s=train_f16s,
-                                       **_geometry_kw(geometry, ray_grad))
+        return _render_train(rays, model, opts, train_occupancy, t_rand, u, _next_seed(seed), int(ray_offset), train_f16s, geometry, ray_grad)
     packed = packed_for(model)
     rays = as_f32_dev(rays, packed.device)
     if rays.dim() != 2 or rays.shape[1] != 6:
@@ -325,13 +324,11 @@ def batchify_rays_and_render_by_chunk(ray_o, ray_d, model, posenc, H, W, K, opts
     for i in range(0, N, slab):
         j = min(N, i + slab)
         tr, uu = (None if t_rand is None else t_rand[i:j]), (None if u is None else u[i:j])
-        if train_occupancy is not None:
-            parts.append(occupancy_train.render_train(rays[i:j].contiguous(), model, opts, train_occupancy, t_rand=tr, u=uu, seed=seed,
-                                                      ray_offset=int(ray_offset) + i, f16s=train_f16s, **_geometry_kw(geometry)))
-            train_stats = occ.add_stats(train_stats, train_occupancy.last_stats)
-        elif training:                                              # train.py:53-54: one autograd node per slab
-            parts.append(train_path.render_train(rays[i:j].contiguous(), model, opts, t_rand=tr, u=uu, seed=seed,
-                                                 ray_offset=int(ray_offset) + i, f16s=train_f16s, **_geometry_kw(geometry, ray_grad)))
+        if training:                                                # train.py:53-54: one autograd node per slab
+            parts.append(_render_train(rays[i:j].contiguous(), model, opts, train_occupancy, tr, uu, seed, int(ray_offset) + i, train_f16s, geometry,
+                                       ray_grad))
+            if train_occupancy is not None:
+                train_stats = occ.add_stats(train_stats, train_occupancy.last_stats)
         else:
             parts.append(_render(rays[i:j], packed, opts, tr, uu, seed, int(ray_offset) + i, prec, False, occupancy, **_geometry_kw(geometry)))
     if train_occupancy is not None:

@@ -154,6 +154,14 @@ def ndc_rays(H: int, W: int, focal: float, near: float, rays_o: torch.Tensor, ra
 # ------------------------------------------------------------------------------------------------
 # sampling
 # ------------------------------------------------------------------------------------------------
+def deterministic(opts) -> bool:
+    """``opts.perturb`` switches the jitter off (the ``det`` of stratified_z / fine_z), for the inference and the training path alike."""
+    # the reference compares the raw attribute with 0. (nerf_process.py:65); a value read from a config
+    # file can be a string (config.py:76 has no type=), for which `== 0.` is False
+    p = getattr(opts, "perturb", 1.0)
+    return isinstance(p, (int, float)) and p == 0.0
+
+
 def fill_uniform(seed: int, stream_id: int, ray0: int, n_rays: int, n_samples: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     device = torch.device(device)
     if out is None:

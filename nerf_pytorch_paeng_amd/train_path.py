@@ -11,6 +11,10 @@ optimizer); no PyTorch kernel touches the activations.
 Semantics copied from the reference: only ``rgb_c`` / ``rgb_f`` carry gradient; the fine depths are
 detached (nerf_process.py:66), so the fine loss does not reach the coarse network; disparity outputs are
 not differentiable here (the reference's loss never reads them, train.py:60-66).
+
+The node, ``_RenderTrain``, owns everything around the two networks once: parameters -> blobs, depths, compositing, what is saved, which
+gradients arrived, the split-precision bookkeeping.  How one network's samples reach the kernels is a route handed to it: ``Dense``
+evaluates every sample, occupancy_train.Compacted only those an occupancy grid keeps (``render_train(..., grid=)``).
 """
 from __future__ import annotations
 
@@ -116,6 +120,18 @@ class _TrainState:
         self.map_f16s()
         return self._map_bwd_f16s
 
+    def forward_blob(self, flat: torch.Tensor, f16s: bool = False) -> torch.Tensor:
+        """The weight stream a forward launch reads, re-packed on the device from the flat vector: the fp32 one, or the split-precision one."""
+        if f16s:
+            return ops.pack_apply_f16s(self.net, self.map_f16s(), flat, self.f16s_out_of_range)
+        return ops.pack_apply(self.map_fwd, flat)
+
+    def backward_blob(self, flat: torch.Tensor, f16s_dgrad: bool = False) -> torch.Tensor:
+        """The transposed stream of the backward-data chain: the fp32 one, or the one of the split-precision chain."""
+        if f16s_dgrad:
+            return ops.pack_apply_f16s(self.net, self.map_bwd_f16s(), flat, self.f16s_out_of_range, backward=True)
+        return ops.pack_apply(self.map_bwd, flat)
+
     def flat(self, params) -> torch.Tensor:
         """Flat fp32 parameter vector of the network the kernels run (zero-padded to its width when the module's is narrower)."""
         f = _flat(params)
@@ -186,44 +202,67 @@ def _flat(params) -> torch.Tensor:
     return torch.cat([p.detach().reshape(-1) for p in params]).float()
 
 
+class Dense:
+    """The route of ``_RenderTrain`` that evaluates every sample.  A route says how one network's samples reach the kernels and how d_raw gets
+    back, in these four members; the other one, occupancy_train.Compacted, is this one run on the tiles of the samples a grid keeps."""
+    saves = 0                                      # tensors per network the route adds to the node's (flat, blob, z, raw, stash)
+
+    def forward(self, st, f16s, which, flat, blob, rays, z):
+        """-> raw [n, S, 4], the stash, the ``saves`` tensors.  f16s: the launch runs in split precision (fp32-grade outputs and stash; blob
+        re-packed on the device like the fp32 one); the backward keeps reading the fp32 ``blob``'s side tables either way."""
+        if f16s:
+            return (*ops.mlp_rays_train(st.net, st.forward_blob(flat, True), rays, z, f16s=True), ())
+        return (*ops.mlp_rays_train(st.net, blob, rays, z), ())
+
+    def skipped(self, saved) -> bool:
+        """The forward launched nothing, so the parameters did not reach the outputs: their gradient is zero."""
+        return False
+
+    def backward(self, st, f16s, f16s_dgrad, blob, blob_b, rays, z, d_raw, stash, saved, stage):
+        grads, work = ops.mlp_backward(st.net, blob, blob_b, rays, z, d_raw, stash, stage=stage, f16s_wgrad=f16s, f16s_dgrad=f16s_dgrad)
+        if f16s:
+            st.note_f16s_backward(work, z.shape[0], z.shape[1])
+        return grads, work
+
+
+# what _RenderTrain.forward takes before the parameters and saves per network after the rays: every index of needs_input_grad and of
+# saved_tensors comes from these two
+_INPUTS = ("st", "route", "rays", "cfg", "t_rand", "u", "z_override")
+_KEPT = ("flat", "blob", "z", "raw", "stash")
+
+
 class _RenderTrain(torch.autograd.Function):
     """rays (+ explicit randomness) and the two networks' parameters -> rgb_c, disp_c, rgb_f, disp_f; with ``cfg["geometry"]`` also
     acc_c, depth_c, distortion_c, acc_f, depth_f, distortion_f, differentiable like the colours (geometry.node_forward / node_backward).
+    ``route`` (``Dense``, or with an occupancy grid occupancy_train.Compacted) runs the networks; everything around them is here once.
     With ``cfg["ray_grad"]`` the backward also returns the gradient of ``rays`` (pose.input_grad on the deltas the backward-data chain left
     in its workspace: no second backward pass), and a network none of whose parameters requires grad runs that chain alone (stage 1)."""
 
     @staticmethod
-    def forward(ctx, st: _TrainState, rays, cfg: Dict, t_rand, u, z_override, *params):
+    def forward(ctx, st: _TrainState, route, rays, cfg: Dict, t_rand, u, z_override, *params):
         n_each = len(st.names)
-        net = st.net
-        Sc, Nf, det = cfg["Sc"], cfg["Nf"], cfg["det"]
+        Nf, det = cfg["Nf"], cfg["det"]
         f16s = bool(cfg.get("f16s", False))
+        saved = [rays]
 
-        def forward_net(flat, blob, z):
-            # f16s: the forward launch runs in split precision (fp32-grade outputs and stash; blob re-packed on the device like the fp32
-            # one); the backward is the same fp32 kernels either way and keeps reading the fp32 blob's side tables
-            if f16s:
-                return ops.mlp_rays_train(net, ops.pack_apply_f16s(net, st.map_f16s(), flat, st.f16s_out_of_range), rays, z, f16s=True)
-            return ops.mlp_rays_train(net, blob, rays, z)
+        def network(k, depths):
+            flat = st.flat(params[k * n_each:(k + 1) * n_each])
+            blob = st.forward_blob(flat)
+            z = depths()
+            raw, stash, more = route.forward(st, f16s, ("coarse", "fine")[k], flat, blob, rays, z)
+            rgb, disp, weights, extra = geo.node_forward(cfg, raw, z, rays, k == 0)
+            saved.extend((flat, blob, z, raw, stash, *more))
+            return rgb, disp, extra, z, weights
 
-        flat_c = st.flat(params[:n_each])
-        blob_c = ops.pack_apply(st.map_fwd, flat_c)
-        z_c = ops.stratified_z(cfg["near"], cfg["far"], t_rand) if z_override is None else z_override[0]
-        raw_c, stash_c = forward_net(flat_c, blob_c, z_c)
-        rgb_c, disp_c, w_c, extra_c = geo.node_forward(cfg, raw_c, z_c, rays, True)
-        ctx.st, ctx.Nf, ctx.f16s, ctx.cfg = st, Nf, f16s, cfg
-        saved = [rays, flat_c, blob_c, z_c, raw_c, stash_c]
+        rgb_c, disp_c, extra_c, z_c, w_c = network(0, lambda: ops.stratified_z(cfg["near"], cfg["far"], t_rand) if z_override is None else z_override[0])
         if Nf > 0:
-            flat_f = st.flat(params[n_each:])
-            blob_f = ops.pack_apply(st.map_fwd, flat_f)
-            z_f = ops.fine_z(z_c, w_c, Nf, det, None if det else u) if (z_override is None or z_override[1] is None) else z_override[1]
-            raw_f, stash_f = forward_net(flat_f, blob_f, z_f)
-            rgb_f, disp_f, _, extra_f = geo.node_forward(cfg, raw_f, z_f, rays, False)
-            saved += [flat_f, blob_f, z_f, raw_f, stash_f]
+            rgb_f, disp_f, extra_f, _, _ = network(1, lambda: ops.fine_z(z_c, w_c, Nf, det, None if det else u)
+                                                   if (z_override is None or z_override[1] is None) else z_override[1])
         else:
             rgb_f = torch.empty(0, 3, device=rays.device)
             disp_f = torch.empty(0, device=rays.device)
             extra_f = tuple(torch.empty(0, device=rays.device) for _ in extra_c)
+        ctx.st, ctx.route, ctx.Nf, ctx.f16s, ctx.cfg = st, route, Nf, f16s, cfg
         ctx.save_for_backward(*saved)
         ctx.mark_non_differentiable(disp_c, disp_f)
         ctx.set_materialize_grads(False)
@@ -232,39 +271,45 @@ class _RenderTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb_c, g_disp_c, g_rgb_f, g_disp_f, *g_extra):
         st: _TrainState = ctx.st
-        net = st.net
-        saved = ctx.saved_tensors
-        rays = saved[0]
-        g_extra_c, g_extra_f = g_extra[:len(g_extra) // 2], g_extra[len(g_extra) // 2:]
-
+        route, cfg, net = ctx.route, ctx.cfg, st.net
+        rays, *kept = ctx.saved_tensors
+        per_net = len(_KEPT) + route.saves
         n_each = len(st.names)
-        need_rays = bool(ctx.cfg.get("ray_grad", False)) and ctx.needs_input_grad[1]
+        g_extra_c, g_extra_f = g_extra[:len(g_extra) // 2], g_extra[len(g_extra) // 2:]
+        f16s = ctx.f16s and net.W == 256
+        ray_grad = bool(cfg.get("ray_grad", False))
+        need_rays = ray_grad and ctx.needs_input_grad[_INPUTS.index("rays")]
         g_rays: List[torch.Tensor] = []
+        launched = False
 
-        def one(flat, blob, z, raw, stash, g_rgb, g_ext, need_params: bool = True) -> List[Optional[torch.Tensor]]:
+        def one(k, g_rgb, g_ext) -> List[Optional[torch.Tensor]]:
+            nonlocal launched
             if g_rgb is None and all(g is None for g in g_ext):
-                return [None] * len(st.names)
-            f16s = ctx.f16s and net.W == 256
+                return [None] * n_each
+            flat, blob, z, raw, stash, *more = kept[k * per_net:(k + 1) * per_net]
+            if route.skipped(more):
+                return st.split_grads(torch.zeros(st.n_flat, dtype=torch.float32, device=rays.device))
+            # without ray_grad every call is what it was (stage 0); with it a network whose parameters are all frozen skips the weight gradients
+            first = len(_INPUTS) + k * n_each
+            need_params = not ray_grad or any(ctx.needs_input_grad[first:first + n_each])
             f16s_dgrad = f16s and ops.f16s_dgrad_fits(net)   # the split-precision chain keeps a tile's ReLU' words of all layers in LDS
-            blob_b = ops.pack_apply_f16s(net, st.map_bwd_f16s(), flat, st.f16s_out_of_range, backward=True) if f16s_dgrad else ops.pack_apply(st.map_bwd, flat)
-            d_raw = geo.node_backward(ctx.cfg, raw, z, rays, g_rgb, g_ext)
-            grads, work = ops.mlp_backward(net, blob, blob_b, rays, z, d_raw, stash, stage=0 if need_params else 1, f16s_wgrad=f16s,
-                                           f16s_dgrad=f16s_dgrad)
-            if f16s:
-                st.note_f16s_backward(work, z.shape[0], z.shape[1])
+            blob_b = st.backward_blob(flat, f16s_dgrad)
+            d_raw = geo.node_backward(cfg, raw, z, rays, g_rgb, g_ext)
+            grads, work = route.backward(st, f16s, f16s_dgrad, blob, blob_b, rays, z, d_raw, stash, more, 0 if need_params else 1)
+            launched = True
             if need_rays:
                 from . import pose
                 g_rays.append(pose.input_grad(net, flat, rays, z, raw, d_raw, work))
-            return st.split_grads(grads) if need_params else [None] * len(st.names)
+            return st.split_grads(grads) if need_params else [None] * n_each
 
-        # without ray_grad every call is what it was (stage 0); with it a network whose parameters are all frozen skips the weight gradients
-        frozen = [bool(ctx.cfg.get("ray_grad", False)) and not any(ctx.needs_input_grad[6 + k * n_each:6 + (k + 1) * n_each]) for k in (0, 1)]
-        gc = one(*saved[1:6], g_rgb_c, g_extra_c, not frozen[0])
-        gf = one(*saved[6:11], g_rgb_f, g_extra_f, not frozen[1]) if ctx.Nf > 0 else [None] * len(st.names)
-        if ctx.f16s and net.W == 256 and any(g is not None for g in (g_rgb_c, g_rgb_f, *g_extra)):
+        gc = one(0, g_rgb_c, g_extra_c)
+        gf = one(1, g_rgb_f, g_extra_f) if ctx.Nf > 0 else [None] * n_each
+        if f16s and launched:                                  # dense: a gradient arrived; compacted: and a sample had survived
             st.end_f16s_step()                                 # both nets' range words are folded: read them at the cadence
-        g_r = None if not g_rays else (g_rays[0] if len(g_rays) == 1 else g_rays[0] + g_rays[1])
-        return (None, g_r, None, None, None, None, *gc, *gf)
+        g_in: List[Optional[torch.Tensor]] = [None] * len(_INPUTS)
+        if g_rays:
+            g_in[_INPUTS.index("rays")] = g_rays[0] if len(g_rays) == 1 else g_rays[0] + g_rays[1]
+        return (*g_in, *gc, *gf)
 
 
 class _EmbeddedTrain(torch.autograd.Function):
@@ -288,25 +333,28 @@ class _EmbeddedTrain(torch.autograd.Function):
         return (None, None, *st.split_grads(grads))
 
 
-def render_train(rays: torch.Tensor, model: torch.nn.Module, opts, *, t_rand=None, u=None, seed: int = 0, ray_offset: int = 0,
-                 z_override=None, det: Optional[bool] = None, f16s: bool = False, geometry: bool = False,
-                 ray_grad: bool = False) -> Dict[str, torch.Tensor]:
-    """Differentiable ``render_rays`` (nerf_process.py:185-216) for one slab of rays [n, 6].  ``f16s``: the two forward launches run in
-    split precision (fp32-grade results, ~3x faster); the backward kernels are the fp32 ones.  ``geometry``: the dict also carries
-    ``acc_*``, ``depth_*`` and ``distortion_*`` per network, differentiable like the colours (geometry.py).  ``ray_grad``: rays that require
-    grad are accepted and receive their gradient (pose.py: d rays, from there d pose); the depths stay constants, as in the reference.
-    Without it such rays are refused, so that a gradient is never dropped silently."""
+RAY_GRAD_WITH_GRID = "ray_grad=True with train_occupancy= is not built: with a grid the training node differentiates the parameters only"
+
+
+def node_inputs(rays, model, opts, t_rand, u, seed: int, ray_offset: int, det: Optional[bool], f16s: bool, geometry: bool, ray_grad: bool, grid):
+    """What ``_RenderTrain.apply`` takes for one slab, but for ``z_override``: st, route, rays, cfg, t_rand, u and the parameter list."""
+    if ray_grad and grid is not None:
+        raise MiNerfError(RAY_GRAD_WITH_GRID)
     st = _state_for(model, f16s)                 # f16s: the 256-wide state (any netWidth <= 256 is scattered into it)
     dev = st.device
     if isinstance(rays, torch.Tensor) and rays.requires_grad and not ray_grad:
         raise MiNerfError("rays require grad: the training path differentiates w.r.t. the MLP parameters only (the reference trains "
                           "nothing else, main.py:79-80); detach the rays, or a gradient would be dropped silently")
+    if grid is None:
+        route = Dense()
+    else:
+        from . import occupancy_train                                # at call time: that module imports this one
+        route = occupancy_train.Compacted(grid, dev)
     rays = as_f32_dev(rays, dev)
     n = rays.shape[0]
     Sc, Nf = int(opts.N_samples_c), int(opts.N_samples_f)
     if det is None:
-        p = getattr(opts, "perturb", 1.0)
-        det = isinstance(p, (int, float)) and p == 0.0
+        det = ops.deterministic(opts)
     t_rand = ops.fill_uniform(seed, 0, ray_offset, n, Sc, dev) if t_rand is None else as_f32_dev(t_rand, dev)
     if Nf > 0 and not det:
         u = ops.fill_uniform(seed, 1, ray_offset, n, Nf, dev) if u is None else as_f32_dev(u, dev)
@@ -315,9 +363,23 @@ def render_train(rays: torch.Tensor, model: torch.nn.Module, opts, *, t_rand=Non
     cfg = {"near": float(opts.near), "far": float(opts.far), "Sc": Sc, "Nf": Nf, "det": bool(det), "f16s": bool(f16s), "geometry": bool(geometry)}
     if ray_grad:
         cfg["ray_grad"] = True
-    params = st.params(model.model_coarse) + st.params(model.model_fine)
-    rgb_c, disp_c, rgb_f, disp_f, *extra = _RenderTrain.apply(st, rays, cfg, t_rand, u, z_override, *params)
-    return node_outputs(rgb_c, disp_c, rgb_f, disp_f, extra, Nf)
+    return st, route, rays, cfg, t_rand, u, st.params(model.model_coarse) + st.params(model.model_fine)
+
+
+def render_train(rays: torch.Tensor, model: torch.nn.Module, opts, *, t_rand=None, u=None, seed: int = 0, ray_offset: int = 0,
+                 z_override=None, det: Optional[bool] = None, f16s: bool = False, geometry: bool = False,
+                 ray_grad: bool = False, grid=None) -> Dict[str, torch.Tensor]:
+    """Differentiable ``render_rays`` (nerf_process.py:185-216) for one slab of rays [n, 6].  ``f16s``: the two forward launches run in
+    split precision (fp32-grade results, ~3x faster); the backward kernels are the fp32 ones.  ``geometry``: the dict also carries
+    ``acc_*``, ``depth_*`` and ``distortion_*`` per network, differentiable like the colours (geometry.py).  ``ray_grad``: rays that require
+    grad are accepted and receive their gradient (pose.py: d rays, from there d pose); the depths stay constants, as in the reference.
+    Without it such rays are refused, so that a gradient is never dropped silently.  ``grid``: an occupancy.OccupancyGrid -- the networks
+    skip the samples it marks empty, forward and backward (occupancy_train.py; not with ``ray_grad``)."""
+    st, route, rays, cfg, t_rand, u, params = node_inputs(rays, model, opts, t_rand, u, seed, ray_offset, det, f16s, geometry, ray_grad, grid)
+    rgb_c, disp_c, rgb_f, disp_f, *extra = _RenderTrain.apply(st, route, rays, cfg, t_rand, u, z_override, *params)
+    if grid is not None:
+        grid.last_stats = route.stats                               # the sample counts of the call
+    return node_outputs(rgb_c, disp_c, rgb_f, disp_f, extra, cfg["Nf"])
 
 
 def node_outputs(rgb_c, disp_c, rgb_f, disp_f, extra, Nf: int) -> Dict[str, torch.Tensor]:
