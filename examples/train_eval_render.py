@@ -6,7 +6,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10] [--mesh-view]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
                                              [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY] [--bake-optimizer adam|lazy]
-                                             [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]]]
+                                             [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]] [--bake-prune-seen T_VIS]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -31,6 +31,8 @@ records, Cauchy sparsity of the density; e.g. 0.01:0.01:0.01) and is refused wit
 level's resolution -- eight times fewer evaluations per halving -- and each level's steps are followed by a resample to the next
 (RadianceGrid.resample); the final level is ``--bake`` RES with ``--bake-finetune`` STEPS.  ``--bake-prune TAU`` ends every level with
 RadianceGrid.prune(TAU): density and records are cleared away from density above TAU.  Both are refused without ``--bake RES --bake-finetune STEPS``.
+``--bake-prune-seen T_VIS`` (dense storage) prunes the grid by the training views (RadianceGrid.seen, RadianceGrid.prune(seen=...)): after the
+bake, and with ``--bake-levels`` after every level instead; active points, record MiB and the held-out PSNR are printed before and after.
 """
 import argparse
 import os
@@ -77,6 +79,9 @@ def main(argv=None):
     ap.add_argument("--bake-levels", default=None, metavar="RES:STEPS[,RES:STEPS...]",
                     help="with --bake RES --bake-finetune STEPS: bake at the first level's resolution and train coarse to fine through these levels; the final level is RES with STEPS steps")
     ap.add_argument("--bake-prune", type=float, default=None, metavar="TAU", help="with --bake-finetune: after each level, clear density and records away from density above TAU")
+    ap.add_argument("--bake-prune-seen", type=float, default=None, metavar="T_VIS",
+                    help="with --bake (dense): prune the grid by the training views -- density stays only around points that some training view sees with "
+                         "transmittance at least T_VIS; after the bake, and after every level with --bake-levels")
     a = ap.parse_args(argv)
     if a.warmup is not None and not 0 <= a.warmup < a.steps:
         ap.error("--warmup takes a number of steps below --steps")
@@ -86,6 +91,11 @@ def main(argv=None):
     bake_storage = "dense"
     if a.bake_finetune and (a.bake is None or len(a.bake.split(":")) > 2 and a.bake.split(":")[2] != "dense"):
         ap.error("--bake-finetune needs --bake with dense storage (fine-tune dense, then compact)")
+    if a.bake_prune_seen is not None:
+        if a.bake is None or len(a.bake.split(":")) > 2 and a.bake.split(":")[2] != "dense":
+            ap.error("--bake-prune-seen needs --bake with dense storage (prune dense, then compact)")
+        if not 0.0 <= a.bake_prune_seen <= 1.0:
+            ap.error("--bake-prune-seen takes a transmittance, 0 .. 1")
     bake_reg = {}
     if a.bake_reg is not None:
         if not a.bake_finetune:
@@ -236,17 +246,31 @@ def main(argv=None):
         print(f"bake: {grid.res[0]}^3 cells, B={bake_B}, {bake_storage}, {grid.nbytes / 2 ** 20:.1f} MiB in {t_bake:.2f} s; {rgbs_g.shape[0]} frames from the grid in {t_grid * 1e3:.1f} ms "
               f"(the network: {t_net * 1e3:.1f} ms, PNG writing included in both); PSNR of the grid's frames against the network's "
               f"{['%.2f' % (-10.0 * np.log10(max(m, 1e-12))) for m in mse]} dB; {a.out}/render_baked")
+        from nerf_pytorch_paeng_amd.rays import make_o_d
+
+        def view_rays(idx):
+            return torch.cat([torch.cat([x.reshape(-1, 3) for x in make_o_d(W, H, K, poses[i][:3, :4].to(dev))], -1) for i in idx]).float().contiguous()
+
+        def grid_psnr():
+            with torch.no_grad():
+                rgb = grid.render(view_rays(i_test), want_all=False).reshape(len(i_test), -1)
+            return [float(-10.0 * torch.log10(torch.mean((rgb[j] - images[i].to(dev).reshape(-1)) ** 2))) for j, i in enumerate(i_test)]
+
+        def prune_seen(what):
+            """Prune the dense grid by the training views; active points, record MiB and the held-out PSNR before and after."""
+            n0, p0 = grid.compact().count, grid_psnr()
+            grid.prune(0.0 if a.bake_prune is None else a.bake_prune, seen=grid.seen(train_views), T_vis=a.bake_prune_seen)
+            n1 = grid.compact().count
+            mib = 4 * grid.record_floats / 2 ** 20
+            print(f"bake-prune-seen ({what}): T_vis {a.bake_prune_seen:g}, {len(train_views)} training views; active points {n0} -> {n1}, records "
+                  f"{n0 * mib:.1f} -> {n1 * mib:.1f} MiB (fp32), {int(grid.skip.sum())} of {grid.skip.numel()} blocks of the skip plane occupied; the grid's "
+                  f"PSNR on the test views {['%.2f' % p for p in p0]} -> {['%.2f' % p for p in grid_psnr()]} dB")
+
+        train_views = baked.Views(H, W, K, poses[i_train]) if a.bake_prune_seen is not None else None
+        if train_views is not None and not bake_levels:
+            prune_seen("after the bake")
         if a.bake_finetune > 0:
             from nerf_pytorch_paeng_amd import baked_train
-            from nerf_pytorch_paeng_amd.rays import make_o_d
-
-            def view_rays(idx):
-                return torch.cat([torch.cat([x.reshape(-1, 3) for x in make_o_d(W, H, K, poses[i][:3, :4].to(dev))], -1) for i in idx]).float().contiguous()
-
-            def grid_psnr():
-                with torch.no_grad():
-                    rgb = grid.render(view_rays(i_test), want_all=False).reshape(len(i_test), -1)
-                return [float(-10.0 * torch.log10(torch.mean((rgb[j] - images[i].to(dev).reshape(-1)) ** 2))) for j, i in enumerate(i_test)]
 
             if a.bake_optimizer == "lazy":                                                     # the direct path: steps only where a gradient arrived
                 from nerf_pytorch_paeng_amd.optim import LazyAdam
@@ -255,8 +279,9 @@ def main(argv=None):
             t_ft = time.perf_counter()
             if bake_levels or a.bake_prune is not None:
                 levels = bake_levels + [(bake_res, a.bake_finetune)]
-                grid, losses = baked_train.coarse_to_fine(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), levels, prune=a.bake_prune, **bake_reg)
-                print(f"bake-levels: {levels}, prune {a.bake_prune}; {int(grid.skip.sum())} of {grid.skip.numel()} blocks of the skip plane occupied at the end")
+                grid, losses = baked_train.coarse_to_fine(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), levels, prune=a.bake_prune, prune_views=train_views,
+                                                          prune_T=1e-3 if a.bake_prune_seen is None else a.bake_prune_seen, **bake_reg)
+                print(f"bake-levels: {levels}, prune {a.bake_prune}{'' if train_views is None else ', by the training views at T_vis %g' % a.bake_prune_seen}; {int(grid.skip.sum())} of {grid.skip.numel()} blocks of the skip plane occupied at the end")
             else:
                 losses = baked_train.finetune(grid, view_rays(i_train), images[i_train].to(dev).reshape(-1, 3).float(), a.bake_finetune, **bake_reg)
             torch.cuda.synchronize()

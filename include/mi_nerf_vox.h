@@ -94,6 +94,43 @@
  * the record of a kept point is not written at all, and sigma_in is not modified.  Afterwards the records of the points that are not
  * active (under sigma_out) are zero: the state a bake leaves, which training by include/mi_nerf_voxgrad.h relies on and does not keep.
  * The result is bit-identical from run to run.
+ *
+ * PRUNING BY VISIBILITY: what no training camera sees with measurable transmittance is removed.  Three rules, all gathers and plain
+ * stores: per view a volume of optical depth along the pixel rays, then every lattice point looks itself up in that volume and keeps the
+ * minimum over the views, then the pruning stencil with a second condition on the seed.  A view is the pinhole camera of
+ * include/mi_nerf_mesh.h (its Camera paragraph: H rows, W columns, fx, fy, cx, cy, c2w = (R | t) row-major, pixel (i, j) = column i,
+ * row j) with a depth range cut into K slices: slice k covers the ray parameters depth_near + k depth_step .. depth_near + (k + 1)
+ * depth_step (the parameter t of the pixel's ray x = o + t d, which is that header's camera depth z).
+ *
+ * THE SHADOW RULE (mi_vox_shadow), per pixel (column i, row j) of a view:
+ *     a = ((float)i - cx) / fx,   b = -(((float)j - cy) / fy),   c = -1;     d_r = (R_r0 a + R_r1 b) + R_r2 c;     o = t;
+ *     L = sqrtf((d_x d_x + d_y d_y) + d_z d_z);     delta = depth_step * L.
+ * For k = 0 .. K - 1 in increasing order, with od_0 = 0:
+ *     tvol[j][i][k] = od_k                            the optical depth BEFORE slice k
+ *     m_k = depth_near + ((float)k + 0.5f) * depth_step;     p_i = o_i + m_k * d_i;
+ *     sigma_s = step 3 of THE RENDER RULE at p (cell, clamps, weights, pairwise sum) when lo_i <= p_i <= hi_i on all three axes;
+ *               otherwise 0, and nothing is fetched (a NaN p_i fails the comparison);
+ *     od_{k+1} = od_k + sigma_s * delta.
+ * With a skip plane, a sample whose cell's block byte is 0 takes sigma_s = 0 without a fetch: its eight values are 0, so tvol is
+ * BIT-IDENTICAL with and without the plane.  Every element of tvol [H, W, K] is written.  There is no exponential anywhere: the rule
+ * can be restated bit for bit.  exp(-od) is the transmittance with which the view sees the front of the slice.
+ *
+ * THE VISIBILITY RULE (mi_vox_seen), per lattice point x (THE LATTICE's arithmetic) and one view with its tvol:
+ *     e_k = x_k - t_k;   q_i = (R_0i e_0 + R_1i e_1) + R_2i e_2;   z = -q_z;   sx = cx + (fx * q_x) / z;   sy = cy - (fy * q_y) / z;
+ *     fi = rintf(sx),  fj = rintf(sy)                 (ties to even: the nearest pixel)
+ * The point is LOOKED AT iff z > 0, z is finite, 0 <= fi <= (float)(W - 1) and 0 <= fj <= (float)(H - 1), compared as floats (a NaN
+ * fails).  A point that is not looked at is left alone.  Otherwise
+ *     k = (int)floorf((z - depth_near) / depth_step) - bias          (formed without overflow: a quotient beyond +-2^40 counts as that)
+ *     k < 0: od = 0;     k >= K: the point is left alone;     otherwise od = tvol[(int)fj][(int)fi][k];
+ *     od_plane[x] = fminf(od_plane[x], od).
+ * The caller fills od_plane with +inf and runs one mi_vox_shadow + mi_vox_seen pair per view, on one stream, through the same tvol.  A
+ * minimum does not depend on the order of the views, and each element is read and written by one thread: no atomic, bit-identical from
+ * run to run.  Afterwards od_plane is the smallest optical depth under which any view sees the point, +inf where none looks.  bias is
+ * the shadow-map bias in slices: a point is not to be hidden by the shell of density it belongs to.
+ *
+ * THE SEEN PRUNING RULE (mi_vox_prune_seen), with tau >= 0 and od_max >= 0: a lattice point is a SEED iff sigma_in > tau and
+ * od_plane <= od_max (a NaN od fails); it is KEPT iff it or one of its 26 neighbours (clipped to the lattice) is a seed.  The writes are
+ * THE PRUNING RULE's.  With od_max = +inf and an od_plane without NaN the result is that rule's bit for bit.
  */
 #ifndef MI_NERF_VOX_H
 #define MI_NERF_VOX_H
@@ -193,6 +230,31 @@ int mi_vox_resample(const mi_vox_grid* src, const mi_vox_grid* dst, int B, const
 /* THE PRUNING RULE.  tau finite and >= 0; sigma_out_dev must not be sigma_in_dev (refused: the stencil reads a point's neighbours);
  * coef_dev [P_z, P_y, P_x, R], 16-byte aligned, is edited in place.  The caller rebuilds the skip plane from sigma_out_dev. */
 int mi_vox_prune(const mi_vox_grid* grid, int B, float tau, const float* sigma_in_dev, float* sigma_out_dev, float* coef_dev, void* stream);
+
+/* PRUNING BY VISIBILITY (added within ABI 2: nothing earlier changed).  One view: the camera and its slices. */
+typedef struct mi_vox_view {
+    int32_t H, W;              /* 1 .. 8192 */
+    float fx, fy, cx, cy;      /* finite; fx and fy not 0 */
+    float c2w[12];             /* [3,4] row-major (R | t), finite */
+    float depth_near;          /* finite, >= 0 */
+    float depth_step;          /* finite, > 0: the depth of one slice, in units of the pixel ray's parameter t (= camera depth) */
+    int32_t slices;            /* K: a multiple of 8, 8 .. MI_VOX_MAX_STEPS */
+} mi_vox_view;
+
+/* Bytes of a view's tvol: H * W * K * 4 (0 + error text if the view is refused). */
+size_t mi_vox_shadow_bytes(const mi_vox_view* view);
+
+/* THE SHADOW RULE.  tvol_dev float [H, W, K], 32-byte aligned, every element written; skip_dev may be NULL (no plane is used).  Refused
+ * when tvol shares a byte with sigma. */
+int mi_vox_shadow(const mi_vox_grid* grid, const float* sigma_dev, const uint8_t* skip_dev, const mi_vox_view* view, float* tvol_dev, void* stream);
+
+/* THE VISIBILITY RULE.  od_dev float [P_z, P_y, P_x] is read and written; bias >= 0.  Refused when od shares a byte with tvol. */
+int mi_vox_seen(const mi_vox_grid* grid, const mi_vox_view* view, const float* tvol_dev, int32_t bias, float* od_dev, void* stream);
+
+/* THE SEEN PRUNING RULE.  Everything as mi_vox_prune, with od_max >= 0 (it may be +inf, not NaN) and od_dev float [P_z, P_y, P_x], which
+ * is read only and shares no byte with sigma_out_dev or coef_dev. */
+int mi_vox_prune_seen(const mi_vox_grid* grid, int B, float tau, float od_max, const float* sigma_in_dev, const float* od_dev, float* sigma_out_dev,
+                      float* coef_dev, void* stream);
 
 #ifdef __cplusplus
 }

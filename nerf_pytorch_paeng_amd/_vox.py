@@ -27,8 +27,13 @@ class RenderCfg(C.Structure):         # mi_vox_render_cfg
                 ("use_skip", C.c_int32)]
 
 
+class View(C.Structure):              # mi_vox_view
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("c2w", C.c_float * 12), ("depth_near", C.c_float), ("depth_step", C.c_float), ("slices", C.c_int32)]
+
+
 _P, _I, _I64, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
-_GRIDP, _CFGP = C.POINTER(Grid), C.POINTER(RenderCfg)
+_GRIDP, _CFGP, _VIEWP = C.POINTER(Grid), C.POINTER(RenderCfg), C.POINTER(View)
 
 # name -> (restype, argtypes); mirrors include/mi_nerf_vox.h declaration by declaration
 SIGNATURES = {
@@ -47,6 +52,10 @@ SIGNATURES = {
     "mi_vox_render_sparse": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P]),
     "mi_vox_resample": (_I, [_GRIDP, _GRIDP, _I, _P, _P, _P, _P, _P]),
     "mi_vox_prune": (_I, [_GRIDP, _I, _F, _P, _P, _P, _P]),
+    "mi_vox_shadow_bytes": (_SZ, [_VIEWP]),
+    "mi_vox_shadow": (_I, [_GRIDP, _P, _P, _VIEWP, _P, _P]),
+    "mi_vox_seen": (_I, [_GRIDP, _VIEWP, _P, C.c_int32, _P, _P]),
+    "mi_vox_prune_seen": (_I, [_GRIDP, _I, _F, _F, _P, _P, _P, _P, _P]),
 }
 
 lib, check, last_error = loader(globals(), "mi_vox")

@@ -7,6 +7,8 @@
     small = baked.SparseRadianceGrid(-1.2, 1.2, 512, B=9, storage="f16").bake(model)    # ... baked without the dense record array
     fine = grid.resample(512)                                            # the same field on another lattice (THE RESAMPLING RULE)
     grid.prune(0.5)                                                      # sigma and records cleared away from density > 0.5 (THE PRUNING RULE)
+    od = grid.seen(baked.Views(H, W, K, poses))                          # the least optical depth under which a camera sees each point
+    grid.prune(0.0, seen=od, T_vis=1e-3)                                 # ... and what no camera sees with transmittance 1e-3 goes too
 
 The lattice is the one of mesh.density_lattice (include/mi_nerf_mesh.h): the grid's sigma plane is that lattice after a ReLU.  Colour is
 the network's post-sigmoid colour at the lattice point, seen from D fixed directions, projected by least squares onto B real spherical
@@ -85,6 +87,24 @@ def projection_matrix(D: int = 32, B: int = 9) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------------
 # the grid
 # ---------------------------------------------------------------------------------------------------
+class Views:
+    """The training cameras for ``RadianceGrid.seen``: ``H`` rows, ``W`` columns, the harness's ``K`` ([[fx, 0, cx], [0, fy, cy], ...]) and
+    camera-to-world ``poses`` [V,3,4] or [V,4,4] (a tensor on any device, or host numbers).  The values are read to the host once, here, as
+    mesh.Camera does; ``poses`` is kept as float32 [V,3,4]."""
+
+    def __init__(self, H: int, W: int, K, poses):
+        k = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
+        p = np.asarray(poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else poses, dtype=np.float32)
+        if p.ndim != 3 or p.shape[1:] not in ((3, 4), (4, 4)):
+            raise MiNerfError(f"poses must be [V,3,4] or [V,4,4], got {list(p.shape)}")
+        self.H, self.W = int(H), int(W)
+        self.fx, self.fy, self.cx, self.cy = (float(np.float32(v)) for v in (k[0][0], k[1][1], k[0][2], k[1][2]))
+        self.poses = np.ascontiguousarray(p[:, :3, :4])
+
+    def __len__(self) -> int:
+        return int(self.poses.shape[0])
+
+
 class RadianceGrid:
     """``sigma`` float [P_z, P_y, P_x], ``coef`` float [P_z, P_y, P_x, R], ``skip`` uint8 [B_z, B_y, B_x] on ``device`` (THE GRID of the
     header); None until ``allocate`` / ``bake`` / ``load``."""
@@ -231,18 +251,85 @@ class RadianceGrid:
                                                   dev_ptr(out.coef, "coef_dst", torch.float32, 16), stream_ptr(dev)), "mi_vox_resample")
         return out.build_skip()
 
-    def prune(self, tau: float) -> "RadianceGrid":
+    def prune(self, tau: float, seen: Optional[torch.Tensor] = None, T_vis: float = 1e-3) -> "RadianceGrid":
         """mi_vox_prune: a point stays when it or one of its 26 neighbours has sigma > tau; everywhere else sigma becomes 0 and the record
-        zero (THE PRUNING RULE).  The new sigma plane replaces the old one and the skip plane is rebuilt."""
+        zero (THE PRUNING RULE).  The new sigma plane replaces the old one and the skip plane is rebuilt.
+        With ``seen`` (the plane ``self.seen(views)`` returns) a neighbour counts only if some view sees it with transmittance at least
+        ``T_vis`` as well: mi_vox_prune_seen with od_max = -log(T_vis) (THE SEEN PRUNING RULE)."""
         self._need()
         dev = self.sigma.device
+        if seen is not None:
+            if not isinstance(seen, torch.Tensor) or tuple(seen.shape) != self.points or seen.device != dev:
+                raise MiNerfError(f"seen must be the grid's od plane {self.points} on {dev}: what seen(views) returns")
+            if not (isinstance(T_vis, (int, float)) and 0.0 <= T_vis <= 1.0):
+                raise MiNerfError(f"T_vis={T_vis!r}: a transmittance, 0 .. 1")
+            od_max = float(np.float32(-math.log(T_vis))) if T_vis > 0.0 else math.inf      # formed in double, rounded once
         kept = torch.empty_like(self.sigma)
         g = self.c_grid()
         with ops._guard(dev):
-            _vox.check(_vox.lib().mi_vox_prune(C.byref(g), self.B, float(tau), dev_ptr(self.sigma.detach(), "sigma"), dev_ptr(kept, "sigma_out"),
-                                               dev_ptr(self.coef.detach(), "coef", torch.float32, 16), stream_ptr(dev)), "mi_vox_prune")
+            if seen is None:
+                _vox.check(_vox.lib().mi_vox_prune(C.byref(g), self.B, float(tau), dev_ptr(self.sigma.detach(), "sigma"), dev_ptr(kept, "sigma_out"),
+                                                   dev_ptr(self.coef.detach(), "coef", torch.float32, 16), stream_ptr(dev)), "mi_vox_prune")
+            else:
+                _vox.check(_vox.lib().mi_vox_prune_seen(C.byref(g), self.B, float(tau), od_max, dev_ptr(self.sigma.detach(), "sigma"), dev_ptr(seen, "seen"),
+                                                        dev_ptr(kept, "sigma_out"), dev_ptr(self.coef.detach(), "coef", torch.float32, 16), stream_ptr(dev)),
+                           "mi_vox_prune_seen")
         self.sigma = kept.requires_grad_(self.sigma.requires_grad)
         return self.build_skip()
+
+    # ---- visibility ----------------------------------------------------------------------------------
+    def view_slices(self, views: "Views", step: Optional[float] = None):
+        """Per view of ``views`` a mi_vox_view whose slices of depth ``step`` cover the box: depth_near is the smallest camera depth of the
+        box's eight corners clamped at 0, the number of slices reaches past the largest, rounded up to a multiple of 8."""
+        step = float(np.float32(0.5 * self.cell_edge() if step is None else step))
+        if not (math.isfinite(step) and step > 0.0):
+            raise MiNerfError(f"step={step!r} must be a positive finite number")
+        corners = np.array([[(self.lo, self.hi)[(e >> i) & 1][i] for i in range(3)] for e in range(8)], np.float64)
+        out = []
+        for pose in views.poses.astype(np.float64):
+            z = -((corners - pose[:, 3]) @ pose[:, :3])[:, 2]                               # camera depth: -(R^T (x - t))_z
+            near = float(np.float32(max(float(z.min()), 0.0)))
+            K = 8 * max(1, -(-(int(math.floor(max(float(z.max()) - near, 0.0) / step)) + 1) // 8))
+            if K > _vox.MAX_STEPS:
+                raise MiNerfError(f"step={step:g} cuts the box into {K} slices along a view, more than {_vox.MAX_STEPS}")
+            out.append(_vox.View(views.H, views.W, views.fx, views.fy, views.cx, views.cy, (C.c_float * 12)(*pose.reshape(-1).tolist()), near, step, K))
+        return out
+
+    def seen(self, views: "Views", step: Optional[float] = None, bias: int = 2, skip: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The od plane, float [P_z, P_y, P_x]: the smallest optical depth under which any of ``views`` sees each lattice point, +inf where
+        none looks (THE SHADOW RULE and THE VISIBILITY RULE, one mi_vox_shadow + mi_vox_seen pair per view through one scratch volume).
+        exp(-od) is the best transmittance a view has to the point.  ``step`` is the depth of a slice (default: the renderer's default
+        step), ``bias`` the shadow-map bias in slices, ``skip`` uses the grid's skip plane (the result is the same bit for bit),
+        ``out`` a plane to reuse."""
+        self._need()
+        dev = self.sigma.device
+        if not isinstance(views, Views):
+            raise MiNerfError(f"views: a baked.Views expected, got {type(views).__name__}")
+        if out is None:
+            out = torch.empty(self.points, dtype=torch.float32, device=dev)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != self.points or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise MiNerfError(f"out must be a contiguous float32 plane {self.points} on {dev}")
+        out.fill_(math.inf)
+        cviews = self.view_slices(views, step)
+        L = _vox.lib()
+        need = 0
+        for v in cviews:
+            n = int(L.mi_vox_shadow_bytes(C.byref(v)))
+            if n == 0:
+                raise MiNerfError(f"the view is refused: {_vox.last_error()}")
+            need = max(need, n)
+        if not cviews:
+            return out
+        tvol = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        g = self.c_grid()
+        sigma = self.sigma.detach()
+        with ops._guard(dev):
+            for v in cviews:
+                _vox.check(L.mi_vox_shadow(C.byref(g), dev_ptr(sigma, "sigma"), dev_ptr(self.skip, "skip", torch.uint8, 1) if skip else None, C.byref(v),
+                                           dev_ptr(tvol, "tvol", torch.float32, 32), stream_ptr(dev)), "mi_vox_shadow")
+                _vox.check(L.mi_vox_seen(C.byref(g), C.byref(v), dev_ptr(tvol, "tvol", torch.float32, 32), int(bias), dev_ptr(out, "od"), stream_ptr(dev)),
+                           "mi_vox_seen")
+        return out
 
     # ---- baking --------------------------------------------------------------------------------------
     def bake(self, model_or_packed, network: str = "fine", D: int = 32, sigma_min: float = 0.0, precision=None,

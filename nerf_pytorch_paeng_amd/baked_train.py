@@ -25,7 +25,7 @@ import torch
 from . import _geo, _voxgrad, ops
 from .optim import LazyAdam
 from ._lib import MiNerfError, dev_ptr, stream_ptr
-from .baked import RadianceGrid, SparseRadianceGrid
+from .baked import RadianceGrid, SparseRadianceGrid, Views
 
 
 def _check_grid(grid) -> torch.device:
@@ -290,14 +290,18 @@ def _per_level(name: str, v, n: int) -> list:
     return [v] * n
 
 
-def coarse_to_fine(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, levels, prune=None, **finetune_kw):
+def coarse_to_fine(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, levels, prune=None, prune_views=None, prune_T: float = 1e-3,
+                   **finetune_kw):
     """Train through ``levels``, a sequence of (res, steps): per level the grid is resampled to ``res`` (``grid.resample``; not when it has
     that resolution already), ``finetune`` runs ``steps`` steps with a fresh optimiser, and with ``prune`` the level ends in
     ``grid.prune(tau)`` -- ``prune`` one tau or one per level (None: that level is not pruned).  ``lr_sigma``, ``lr_coef``, ``batch`` and
     ``skip`` may each be one value or one per level (a grid that starts empty wants ``skip=False`` on its first level only: after it the
     skip plane describes what was learnt); every other keyword goes to ``finetune`` as it is.  Returns (the final grid, the levels' losses
     concatenated as one device tensor).  The grid handed in is trained in place on the levels before the first resample and untouched
-    afterwards.  Nothing synchronises with the host."""
+    afterwards.  Nothing synchronises with the host.
+    With ``prune_views`` (a ``baked.Views``: the training cameras) every level that is pruned is pruned by visibility as well:
+    ``grid.prune(tau, seen=grid.seen(prune_views), T_vis=prune_T)``, THE SEEN PRUNING RULE (``prune=None`` then stands for tau = 0 at
+    every level).  Without it nothing changes."""
     dev = _check(grid, rays)
     levels = [tuple(lv) if isinstance(lv, (list, tuple)) else lv for lv in levels]
     if not levels or any(not isinstance(lv, tuple) or len(lv) != 2 for lv in levels):
@@ -305,7 +309,9 @@ def coarse_to_fine(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor,
     n = len(levels)
     if "steps" in finetune_kw:
         raise MiNerfError("steps are given per level, in levels")
-    taus = _per_level("prune", prune, n)
+    if prune_views is not None and not isinstance(prune_views, Views):
+        raise MiNerfError(f"prune_views: a baked.Views expected, got {type(prune_views).__name__}")
+    taus = _per_level("prune", 0.0 if prune is None and prune_views is not None else prune, n)
     for tau in taus:
         if tau is not None and not (isinstance(tau, (int, float)) and math.isfinite(tau) and tau >= 0):
             raise MiNerfError(f"prune={prune!r}: each tau must be a finite number >= 0 (or None)")
@@ -317,5 +323,8 @@ def coarse_to_fine(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor,
             grid = grid.resample(res3)
         losses.append(finetune(grid, rays, target, steps=int(steps), **{k: v[i] for k, v in each.items()}, **finetune_kw))
         if taus[i] is not None:
-            grid.prune(taus[i])
+            if prune_views is None:
+                grid.prune(taus[i])
+            else:
+                grid.prune(taus[i], seen=grid.seen(prune_views), T_vis=prune_T)
     return grid, (torch.cat(losses) if losses else torch.zeros(0, dtype=torch.float32, device=dev))

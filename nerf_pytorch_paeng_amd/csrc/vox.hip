@@ -33,6 +33,17 @@
 //   prune_kernel<B>        THE PRUNING RULE, the same thread shape: a point's R4 lanes split the 27 sigma reads of the stencil between
 //                          them and a ballot joins the answers; piece 0's thread writes sigma_out, and the record of a point that is
 //                          not kept is zeroed piece by piece.  A kept record is not touched.
+//   shadow_kernel          THE SHADOW RULE: the renderer's group of 8 lanes per pixel ray, 32 rays per workgroup -- sigma only, never a
+//                          record.  tvol is ray-major [H, W, K] with K a multiple of 8 so that lane k & 7 holds od_k and a group stores
+//                          eight consecutive floats as one aligned 32-byte piece every eight slices.  Unlike the renderer, lane e takes
+//                          a SLICE, not a corner: it evaluates slice 8 c + e of chunk c whole (eight sigma loads, the rule's pairwise
+//                          sum), and the running sum goes from lane to lane in the rule's order by seven DPP shifts.  With a lane per
+//                          corner every lane repeated the cell arithmetic of every slice, and that arithmetic bounded the kernel.  A chunk of eight slices that lies wholly before the ray's entry into the box or
+//                          behind its exit (the slab, widened by the fp32 error of a sample position) is stored without a sample.
+//   seen_kernel            THE VISIBILITY RULE: one thread per lattice point, x fastest: it projects itself into the view, loads one
+//                          float of tvol and folds it into its own element of the od plane (a coalesced read-modify-write).  No LDS.
+//   prune_seen_kernel<B>   THE SEEN PRUNING RULE: prune_kernel with the seed's second condition, a kernel of its own so that
+//                          prune_kernel's code stays what it was.
 //
 // No atomic, no host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
 #include <hip/hip_runtime.h>
@@ -305,6 +316,172 @@ __global__ __launch_bounds__(THREADS) void prune_kernel(const Lattice g, float t
     if (!kept) coef[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
+// a lane's value handed to the next lane of its row of 16 (row_shr:1); lane 0 of a row receives 0
+__device__ __forceinline__ float dpp_row_shr1(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true)); }
+
+// THE SEEN PRUNING RULE: the same kernel with the seed's second condition (od <= od_max; a NaN fails).  od is loaded only where
+// sigma_in > tau.
+template <int B>
+__global__ __launch_bounds__(THREADS) void prune_seen_kernel(const Lattice g, float tau, float od_max, const float* __restrict__ sigma_in,
+                                                             const float* __restrict__ od, float* __restrict__ sigma_out, float4* __restrict__ coef,
+                                                             long long pieces) {
+    constexpr int R4 = record_floats(B) / 4;
+    const long long t = (long long)blockIdx.x * THREADS + threadIdx.x;
+    const bool live = t < pieces;                          // no lane leaves before the ballot
+    const unsigned j = (unsigned)(t / R4);
+    const int q = (int)(t % R4);
+    bool hit = false;
+    if (live) {
+        const unsigned row = j / (unsigned)g.P[0];
+        const int x = (int)(j - row * (unsigned)g.P[0]), y = (int)(row % (unsigned)g.P[1]), z = (int)(row / (unsigned)g.P[1]);
+        for (int n = q; n < 27; n += R4) {
+            const int x1 = x + n % 3 - 1, y1 = y + (n / 3) % 3 - 1, z1 = z + n / 9 - 1;
+            if (x1 >= 0 && x1 < g.P[0] && y1 >= 0 && y1 < g.P[1] && z1 >= 0 && z1 < g.P[2]) {
+                const long long at = ((long long)z1 * g.P[1] + y1) * g.P[0] + x1;
+                if (sigma_in[at] > tau) hit |= od[at] <= od_max;
+            }
+        }
+    }
+    const unsigned long long m = __ballot(hit);
+    const int first = (threadIdx.x & 63) & ~(R4 - 1);      // the wave lane of this point's piece 0
+    const bool kept = ((m >> first) & ((1ull << R4) - 1ull)) != 0ull;
+    if (!live) return;
+    if (q == 0) sigma_out[j] = kept ? sigma_in[j] : 0.0f;
+    if (!kept) coef[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// ------------------------------------------------------------------------------------------------
+// mi_vox_shadow, mi_vox_seen: one view
+// ------------------------------------------------------------------------------------------------
+struct ViewArgs {
+    int H, W, K;
+    float fx, fy, cx, cy;
+    float R[9], t[3];                                    // c2w = (R | t): R[3 r + c]
+    float depth_near, depth_step;
+};
+
+struct ShadowArgs {
+    Lattice g;
+    ViewArgs v;
+    const float* sigma;
+    const uint8_t* skip;                                 // NULL: no plane
+    float* tvol;
+};
+
+__global__ __launch_bounds__(THREADS) void shadow_kernel(const ShadowArgs a) {
+    const int e = threadIdx.x & (GROUP - 1);               // the slice of a chunk that this lane evaluates and whose od it stores
+    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 3);
+    const ViewArgs& v = a.v;
+    if (ray >= (long long)v.H * v.W) return;               // a whole group leaves together
+    const Lattice& g = a.g;
+    const int pj = (int)(ray / v.W), pi = (int)(ray - (long long)pj * v.W);
+    const float ca = ((float)pi - v.cx) / v.fx, cb = -(((float)pj - v.cy) / v.fy);
+    float d[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) d[r] = (v.R[3 * r] * ca + v.R[3 * r + 1] * cb) + v.R[3 * r + 2] * -1.0f;
+    const float* o = v.t;
+    const float L = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    const float delta = v.depth_step * L;
+    // The ray's slab of the box in the parameter m, widened by more than the fp32 error of a sample position o + m d and of the slab's own
+    // quotients: a sample with m outside (m_in, m_out) fails the rule's test lo <= p <= hi, so a chunk of eight slices on one side of it
+    // needs no sample.  The samples that are evaluated make the rule's test themselves: the slab decides nothing but which are skipped.
+    const float m_last = v.depth_near + ((float)(v.K - 1) + 0.5f) * v.depth_step;
+    float m_in = -INFINITY, m_out = INFINITY;
+    bool never = false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (d[i] != 0.0f) {
+            const float ta = (g.lo[i] - o[i]) / d[i], tb = (g.hi[i] - o[i]) / d[i];
+            const float pad = 8.0f * EPS32 * ((fabsf(ta) + fabsf(tb)) + ((fabsf(o[i]) + fabsf(g.lo[i]) + fabsf(g.hi[i])) / fabsf(d[i]) + m_last));
+            m_in = fmaxf(m_in, fminf(ta, tb) - pad);       // fmaxf / fminf drop a NaN: such an axis bounds nothing
+            m_out = fminf(m_out, fmaxf(ta, tb) + pad);
+        } else if (!(g.lo[i] <= o[i] && o[i] <= g.hi[i])) {
+            never = true;                                  // p_i = o_i at every sample
+        }
+    }
+    float* out = a.tvol + ray * v.K + e;
+    float od = 0.0f;                                       // od before the chunk's first slice: the same in the group's eight lanes
+    for (int kb = 0; kb < v.K; kb += GROUP) {
+        float mine = od;                                   // od_(kb + e); of a chunk without a sample it is od itself
+        const float m_first = v.depth_near + ((float)kb + 0.5f) * v.depth_step;
+        const float m_end = v.depth_near + ((float)(kb + GROUP - 1) + 0.5f) * v.depth_step;
+        if (!never && !(m_end < m_in) && !(m_first > m_out)) {                             // uniform in a group
+            // lane e evaluates slice kb + e, all eight corners of its cell: x = sigma_s * delta, 0 where the rule fetches nothing
+            const float mk = v.depth_near + ((float)(kb + e) + 0.5f) * v.depth_step;
+            float p[3];
+            bool inside = true;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                p[i] = o[i] + mk * d[i];
+                inside = inside && g.lo[i] <= p[i] && p[i] <= g.hi[i];
+            }
+            float x = 0.0f;
+            if (inside) {
+                int c[3];
+                float f[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) cell_of((p[i] - g.lo[i]) * g.inv[i], g.res[i], c[i], f[i]);
+                if (a.skip == nullptr || a.skip[((c[2] >> 3) * g.nb[1] + (c[1] >> 3)) * g.nb[0] + (c[0] >> 3)] != 0) {
+                    float w[8], q[8];
+#pragma unroll
+                    for (int n = 0; n < 8; ++n) {
+                        const int nx = n & 1, ny = (n >> 1) & 1, nz = n >> 2;
+                        const float wx = nx ? f[0] : 1.0f - f[0], wy = ny ? f[1] : 1.0f - f[1], wz = nz ? f[2] : 1.0f - f[2];
+                        w[n] = (wx * wy) * wz;
+                        q[n] = a.sigma[((long long)(c[2] + nz) * g.P[1] + (c[1] + ny)) * g.P[0] + (c[0] + nx)];
+                    }
+                    x = interp8(w, q) * delta;
+                }
+            }
+            // od_(k+1) = od_k + x_k in the rule's order: a chain handed from lane s to lane s + 1 (row_shr:1; lane 0 of a group starts
+            // from od and never takes what the neighbouring group's lane 7 hands over).  All eight lanes are active together.
+#pragma unroll
+            for (int s2 = 0; s2 < GROUP - 1; ++s2) {
+                const float handed = dpp_row_shr1(mine + x);
+                if (e == s2 + 1) mine = handed;
+            }
+            od = group_sum(e == GROUP - 1 ? mine + x : 0.0f);                              // lane 7's sum plus seven zeros: exact
+        }
+        out[kb] = mine;                                    // the group's eight lanes: 32 consecutive, aligned bytes
+    }
+}
+
+struct SeenArgs {
+    Lattice g;
+    ViewArgs v;
+    float step[3];                                       // (hi - lo) / (float)res, formed on the host in fp32
+    const float* tvol;
+    float* od;
+    int bias;
+    long long N;
+};
+
+__global__ __launch_bounds__(THREADS) void seen_kernel(const SeenArgs a) {
+    const long long t = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (t >= a.N) return;
+    const Lattice& g = a.g;
+    const ViewArgs& v = a.v;
+    const unsigned j = (unsigned)t;                        // at most 513^3 points: 32-bit divisions below
+    const unsigned row = j / (unsigned)g.P[0];
+    const int jd[3] = {(int)(j - row * (unsigned)g.P[0]), (int)(row % (unsigned)g.P[1]), (int)(row / (unsigned)g.P[1])};
+    float ek[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ek[i] = (g.lo[i] + (float)jd[i] * a.step[i]) - v.t[i];
+    float q[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) q[i] = (v.R[i] * ek[0] + v.R[3 + i] * ek[1]) + v.R[6 + i] * ek[2];
+    const float z = -q[2];
+    const float sx = v.cx + (v.fx * q[0]) / z, sy = v.cy - (v.fy * q[1]) / z;
+    const float fi = rintf(sx), fj = rintf(sy);
+    if (!(z > 0.0f && isfinite(z) && fi >= 0.0f && fi <= (float)(v.W - 1) && fj >= 0.0f && fj <= (float)(v.H - 1))) return;
+    const float kf = fminf(fmaxf(floorf((z - v.depth_near) / v.depth_step), -1099511627776.0f), 1099511627776.0f);      // +-2^40
+    const long long k = (long long)kf - a.bias;
+    if (k >= v.K) return;
+    float od = 0.0f;
+    if (k >= 0) od = a.tvol[((long long)(int)fj * v.W + (int)fi) * v.K + k];
+    a.od[t] = fminf(a.od[t], od);
+}
+
 // ------------------------------------------------------------------------------------------------
 // mi_vox_render, mi_vox_render_sparse
 // ------------------------------------------------------------------------------------------------
@@ -473,6 +650,36 @@ static inline bool overlap(const void* p, size_t np, const void* q, size_t nq) {
 
 static inline long long index_chunks(const Lattice& g) { return ((long long)g.P[0] * g.P[1] * g.P[2] + IDX_CHUNK - 1) / IDX_CHUNK; }
 static inline size_t index_scratch_bytes(const Lattice& g) { return ((size_t)index_chunks(g) * sizeof(unsigned) + 15) & ~(size_t)15; }
+
+static constexpr int VIEW_MAX_DIM = 8192;
+
+// a view, and the ViewArgs of it (out may be NULL)
+static int check_view(const char* who, const mi_vox_view* view, ViewArgs* out) {
+    VOX_CHECK_ARG(view != nullptr, "%s: view is NULL", who);
+    VOX_CHECK_ARG(view->H >= 1 && view->H <= VIEW_MAX_DIM && view->W >= 1 && view->W <= VIEW_MAX_DIM, "%s: H=%d, W=%d: 1 .. %d", who, view->H, view->W,
+                  VIEW_MAX_DIM);
+    VOX_CHECK_ARG(isfinite(view->fx) && isfinite(view->fy) && isfinite(view->cx) && isfinite(view->cy) && view->fx != 0.0f && view->fy != 0.0f,
+                  "%s: fx=%g, fy=%g, cx=%g, cy=%g must be finite, fx and fy not 0", who, (double)view->fx, (double)view->fy, (double)view->cx, (double)view->cy);
+    for (int i = 0; i < 12; ++i) VOX_CHECK_ARG(isfinite(view->c2w[i]), "%s: c2w[%d]=%g is not finite", who, i, (double)view->c2w[i]);
+    VOX_CHECK_ARG(isfinite(view->depth_near) && view->depth_near >= 0.0f, "%s: depth_near=%g must be a finite number >= 0", who, (double)view->depth_near);
+    VOX_CHECK_ARG(isfinite(view->depth_step) && view->depth_step > 0.0f, "%s: depth_step=%g must be a positive finite number", who, (double)view->depth_step);
+    VOX_CHECK_ARG(view->slices >= GROUP && view->slices <= MI_VOX_MAX_STEPS && view->slices % GROUP == 0, "%s: slices=%d: a multiple of %d, %d .. %d", who,
+                  view->slices, GROUP, GROUP, MI_VOX_MAX_STEPS);
+    if (out) {
+        ViewArgs v{};
+        v.H = view->H; v.W = view->W; v.K = view->slices;
+        v.fx = view->fx; v.fy = view->fy; v.cx = view->cx; v.cy = view->cy;
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) v.R[3 * r + c] = view->c2w[4 * r + c];
+            v.t[r] = view->c2w[4 * r + 3];
+        }
+        v.depth_near = view->depth_near; v.depth_step = view->depth_step;
+        *out = v;
+    }
+    return MI_VOX_OK;
+}
+
+static inline size_t shadow_bytes(const ViewArgs& v) { return (size_t)v.H * v.W * v.K * sizeof(float); }
 
 template <int ST>
 static void launch_render(int B, dim3 blocks, hipStream_t st, const RenderArgs& a) {
@@ -698,6 +905,72 @@ int mi_vox_prune(const mi_vox_grid* grid, int B, float tau, const float* sigma_i
     else if (B == 4) hipLaunchKernelGGL(prune_kernel<4>, blocks, dim3(THREADS), 0, st, g, tau, sigma_in_dev, sigma_out_dev, coef4, pieces);
     else hipLaunchKernelGGL(prune_kernel<9>, blocks, dim3(THREADS), 0, st, g, tau, sigma_in_dev, sigma_out_dev, coef4, pieces);
     VOX_LAUNCH_CHECK("prune_kernel");
+    return MI_VOX_OK;
+}
+
+size_t mi_vox_shadow_bytes(const mi_vox_view* view) {
+    ViewArgs v;
+    if (check_view("mi_vox_shadow_bytes", view, &v)) return 0;
+    return shadow_bytes(v);
+}
+
+int mi_vox_shadow(const mi_vox_grid* grid, const float* sigma_dev, const uint8_t* skip_dev, const mi_vox_view* view, float* tvol_dev, void* stream) {
+    const char* who = "mi_vox_shadow";
+    ShadowArgs a{};
+    if (int rc = check_grid(who, grid, &a.g)) return rc;
+    if (int rc = check_view(who, view, &a.v)) return rc;
+    VOX_CHECK_ARG(sigma_dev && tvol_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(sigma_dev, 4) && aligned(tvol_dev, 32), "%s: sigma must be 4-byte aligned, tvol 32-byte aligned", who);
+    const size_t N = (size_t)a.g.P[0] * a.g.P[1] * a.g.P[2];
+    VOX_CHECK_ARG(!overlap(tvol_dev, shadow_bytes(a.v), sigma_dev, 4 * N), "%s: tvol overlaps sigma: sigma is read while tvol is written", who);
+    a.sigma = sigma_dev; a.skip = skip_dev; a.tvol = tvol_dev;
+    const long long rays = (long long)a.v.H * a.v.W;
+    hipLaunchKernelGGL(shadow_kernel, dim3((unsigned)((rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK)), dim3(THREADS), 0, (hipStream_t)stream, a);
+    VOX_LAUNCH_CHECK("shadow_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_seen(const mi_vox_grid* grid, const mi_vox_view* view, const float* tvol_dev, int32_t bias, float* od_dev, void* stream) {
+    const char* who = "mi_vox_seen";
+    SeenArgs a{};
+    if (int rc = check_grid(who, grid, &a.g)) return rc;
+    if (int rc = check_view(who, view, &a.v)) return rc;
+    VOX_CHECK_ARG(bias >= 0, "%s: bias=%d must be >= 0 slices", who, bias);
+    VOX_CHECK_ARG(tvol_dev && od_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(tvol_dev, 32) && aligned(od_dev, 4), "%s: tvol must be 32-byte aligned, od 4-byte aligned", who);
+    a.N = (long long)a.g.P[0] * a.g.P[1] * a.g.P[2];
+    VOX_CHECK_ARG(!overlap(od_dev, 4 * (size_t)a.N, tvol_dev, shadow_bytes(a.v)), "%s: od overlaps tvol: tvol is read while od is written", who);
+    for (int i = 0; i < 3; ++i) a.step[i] = (grid->hi[i] - grid->lo[i]) / (float)grid->res[i];
+    a.tvol = tvol_dev; a.od = od_dev; a.bias = bias;
+    hipLaunchKernelGGL(seen_kernel, dim3((unsigned)((a.N + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, a);
+    VOX_LAUNCH_CHECK("seen_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_prune_seen(const mi_vox_grid* grid, int B, float tau, float od_max, const float* sigma_in_dev, const float* od_dev, float* sigma_out_dev,
+                      float* coef_dev, void* stream) {
+    const char* who = "mi_vox_prune_seen";
+    Lattice g;
+    if (int rc = check_grid(who, grid, &g)) return rc;
+    if (int rc = check_basis(who, B)) return rc;
+    VOX_CHECK_ARG(isfinite(tau) && tau >= 0.0f, "%s: tau=%g must be a finite number >= 0", who, (double)tau);
+    VOX_CHECK_ARG(od_max >= 0.0f, "%s: od_max=%g must be >= 0 (it may be infinite)", who, (double)od_max);
+    VOX_CHECK_ARG(sigma_in_dev && od_dev && sigma_out_dev && coef_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(coef_dev, 16) && aligned(sigma_in_dev, 4) && aligned(sigma_out_dev, 4) && aligned(od_dev, 4),
+                  "%s: coef must be 16-byte aligned, sigma and od 4-byte aligned", who);
+    const int R4 = record_floats(B) / 4;
+    const size_t N = (size_t)g.P[0] * g.P[1] * g.P[2];
+    VOX_CHECK_ARG(!overlap(sigma_out_dev, 4 * N, sigma_in_dev, 4 * N), "%s: sigma_out overlaps sigma_in: the stencil reads a point's neighbours", who);
+    VOX_CHECK_ARG(!overlap(coef_dev, 16 * N * R4, sigma_in_dev, 4 * N) && !overlap(coef_dev, 16 * N * R4, sigma_out_dev, 4 * N), "%s: coef overlaps a sigma plane", who);
+    VOX_CHECK_ARG(!overlap(od_dev, 4 * N, sigma_out_dev, 4 * N) && !overlap(od_dev, 4 * N, coef_dev, 16 * N * R4), "%s: od overlaps sigma_out or coef: it is read while they are written", who);
+    const long long pieces = (long long)N * R4;
+    const dim3 blocks((unsigned)((pieces + THREADS - 1) / THREADS));
+    hipStream_t st = (hipStream_t)stream;
+    float4* coef4 = reinterpret_cast<float4*>(coef_dev);
+    if (B == 1) hipLaunchKernelGGL(prune_seen_kernel<1>, blocks, dim3(THREADS), 0, st, g, tau, od_max, sigma_in_dev, od_dev, sigma_out_dev, coef4, pieces);
+    else if (B == 4) hipLaunchKernelGGL(prune_seen_kernel<4>, blocks, dim3(THREADS), 0, st, g, tau, od_max, sigma_in_dev, od_dev, sigma_out_dev, coef4, pieces);
+    else hipLaunchKernelGGL(prune_seen_kernel<9>, blocks, dim3(THREADS), 0, st, g, tau, od_max, sigma_in_dev, od_dev, sigma_out_dev, coef4, pieces);
+    VOX_LAUNCH_CHECK("prune_seen_kernel");
     return MI_VOX_OK;
 }
 
