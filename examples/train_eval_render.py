@@ -6,7 +6,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10] [--mesh-view]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
                                              [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY] [--bake-optimizer adam|lazy]
-                                             [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]] [--bake-prune-seen T_VIS]]
+                                             [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]] [--bake-prune-seen T_VIS] [--bake-locate DEG:DIST]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -33,6 +33,9 @@ level's resolution -- eight times fewer evaluations per halving -- and each leve
 RadianceGrid.prune(TAU): density and records are cleared away from density above TAU.  Both are refused without ``--bake RES --bake-finetune STEPS``.
 ``--bake-prune-seen T_VIS`` (dense storage) prunes the grid by the training views (RadianceGrid.seen, RadianceGrid.prune(seen=...)): after the
 bake, and with ``--bake-levels`` after every level instead; active points, record MiB and the held-out PSNR are printed before and after.
+``--bake-locate DEG:DIST`` (any storage) turns the first held-out pose by DEG degrees and moves it by DIST, then recovers it against the
+grid from that view's image alone (baked_pose.locate, docs/design/28_grid_ray_gradients.md); the image error and both pose errors are
+printed before and after.
 """
 import argparse
 import os
@@ -82,7 +85,17 @@ def main(argv=None):
     ap.add_argument("--bake-prune-seen", type=float, default=None, metavar="T_VIS",
                     help="with --bake (dense): prune the grid by the training views -- density stays only around points that some training view sees with "
                          "transmittance at least T_VIS; after the bake, and after every level with --bake-levels")
+    ap.add_argument("--bake-locate", default=None, metavar="DEG:DIST",
+                    help="with --bake: perturb the first held-out pose by DEG degrees and DIST, recover it against the grid, print the errors before and after")
     a = ap.parse_args(argv)
+    bake_locate = None
+    if a.bake_locate is not None:
+        try:
+            bake_locate = tuple(float(v) for v in a.bake_locate.split(":"))
+        except ValueError:
+            bake_locate = ()
+        if a.bake is None or len(bake_locate) != 2 or not all(np.isfinite(v) and v >= 0 for v in bake_locate):
+            ap.error("--bake-locate takes DEG:DIST, two finite numbers >= 0, and needs --bake RES")
     if a.warmup is not None and not 0 <= a.warmup < a.steps:
         ap.error("--warmup takes a number of steps below --steps")
     if a.mesh_view and not a.mesh:
@@ -291,6 +304,34 @@ def main(argv=None):
                       f"SP {float(baked_train.lattice_sparsity(grid)):.4g} after the steps")
             print(f"bake-finetune: {int(losses.numel())} steps{' over the levels ' + str(levels) if bake_levels or a.bake_prune is not None else ''} in {t_ft:.2f} s, batch loss {float(losses[0]):.5f} -> {float(losses[-1]):.5f}; the grid's PSNR on the test "
                   f"views {['%.2f' % p for p in before]} -> {['%.2f' % p for p in grid_psnr()]} dB")
+        if bake_locate is not None:
+            import math
+
+            from nerf_pytorch_paeng_amd import baked_pose
+            i = i_test[0]
+            true = poses[i][:3, :4].to(dev).float()
+            axis = torch.tensor([0.5, -0.7, 0.5], dtype=torch.float64)
+            axis = axis / axis.norm() * math.radians(bake_locate[0])
+            turn = torch.matrix_exp(torch.tensor([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]], dtype=torch.float64))
+            start = true.clone()
+            start[:, :3] = (turn @ true[:, :3].double().cpu()).float().to(dev)
+            start[:, 3] += torch.tensor([0.6, -0.6, 0.53], device=dev) * (bake_locate[1] / math.sqrt(0.6 ** 2 + 0.6 ** 2 + 0.53 ** 2))
+            target = images[i].to(dev).reshape(-1, 3).float()
+
+            def errors(p):
+                cos = float(((p[:, :3].double().T @ true[:, :3].double()).trace() - 1.0) / 2.0)
+                with torch.no_grad():
+                    rgb = grid.render(torch.cat([x.reshape(-1, 3) for x in make_o_d(W, H, K, p)], -1).float().contiguous(), want_all=False)
+                return float(torch.mean((rgb - target) ** 2)), math.degrees(math.acos(max(-1.0, min(1.0, cos)))), float((p[:, 3] - true[:, 3]).norm())
+
+            e0 = errors(start)
+            t_loc = time.perf_counter()
+            found, _ = baked_pose.locate(grid, H, W, K, start, target)
+            torch.cuda.synchronize()
+            t_loc = time.perf_counter() - t_loc
+            e1 = errors(found)
+            print(f"bake-locate: test view {i} turned by {bake_locate[0]:g} deg and moved by {bake_locate[1]:g}, 200 steps of 1024 pixels in {t_loc:.2f} s: image MSE "
+                  f"{e0[0]:.3e} -> {e1[0]:.3e}, rotation error {e0[1]:.3f} -> {e1[1]:.3f} deg, translation error {e0[2]:.4f} -> {e1[2]:.4f}")
     if a.mesh:
         from nerf_pytorch_paeng_amd import mesh
         with torch.no_grad():

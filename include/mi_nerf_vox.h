@@ -131,6 +131,41 @@
  * THE SEEN PRUNING RULE (mi_vox_prune_seen), with tau >= 0 and od_max >= 0: a lattice point is a SEED iff sigma_in > tau and
  * od_plane <= od_max (a NaN od fails); it is KEPT iff it or one of its 26 neighbours (clipped to the lattice) is a seed.  The writes are
  * THE PRUNING RULE's.  With od_max = +inf and an od_plane without NaN the result is that rule's bit for bit.
+ *
+ * THE RAY GRADIENT RULE (mi_vox_render_backward_rays, mi_vox_render_sparse_backward_rays): the derivative of THE RENDER RULE's rgb, acc
+ * and depth with respect to the ray, d_rays [n, 6] = dLoss/d(o, d), under upstream gradients G[3] of rgb, ga of acc and gd of depth (an
+ * absent array is all zeros; disp carries nothing).  It is the exact derivative away from the rule's kinks: a sample crossing a cell
+ * boundary, a change in the number of intervals, a change of the slab axis that gives entry or exit, the colour clamp, the clamps of c_i
+ * and f_i; at a kink it is one of the one-sided values.  The stop at T_min, the bound on k, t_near and t_far are treated as fixed.  All
+ * three storages are differentiated: a record is fetched as the render rule (or the compact render rule) fetches it.
+ * (G . x) stands for (G[0] x[0] + G[1] x[1]) + G[2] x[2]; every sum below runs in increasing k, over the corners as step 3's pairwise
+ * sum, and in increasing b.
+ *   Forward.   Steps 1 to 5 as written above, sample by sample; T_k is the transmittance BEFORE sample k, w_k = T_k alpha_k.  The
+ *              colour is evaluated only where sigma_s > 0, as the renderer does; elsewhere q_e[c] = q_k[c] = colour_k[c] = 0 below.
+ *              ga' = ga - (G . bg);   s_k = ((G . colour_k) + ga') + gd * m_k;   S = sum of w_k * s_k;   P_k = the same sum over j < k.
+ *   Sample k.  E_k = T_k * s_k - (S - P_k);   D_k = delta_k * E_k (dLoss/d sigma_s);   Z_k = sigma_s * E_k (dLoss/d delta_k);
+ *              Q_k[c] = w_k * G[c] where sigma_s > 0 and 0 <= q_k[c] <= 1 (q_k[c] the interpolation of q_e[c] BEFORE the clamp), else 0;
+ *              h_e = D_k * sigma_e + (Q_k . q_e)                         per corner, q_e corner e's own colour before the weight;
+ *              v_e,x = +-(wy * wz), v_e,y = +-(wx * wz), v_e,z = +-(wx * wy): + on the far side of the axis, - on the near side, and 0
+ *              on an axis where g_i - (float)c_i lies outside [0, 1] (the clamp of f_i is active);
+ *              gp_i = inv_i * (the pairwise sum over the corners of v_e,i * h_e)           (dLoss/dp_i at the sample)
+ *              go_i += gp_i;   gd_i += m_k * gp_i;   M_k = (d . gp) + gd * w_k             (dLoss/dm_k)
+ *              an interval that is not cut (not t1 < t0 + (float)(k + 1) * dt):   g_t0 += M_k;   g_dt += ((float)k + 0.5f) * M_k;
+ *              the cut last interval:   r = 0.5f * M_k - L * Z_k;   g_t0 += r;   g_dt += (float)k * r;   g_t1 += 0.5f * M_k + L * Z_k;
+ *                                       g_L += (t1 - a_k) * Z_k;
+ *              y_e,b += (Q_k . (w_e * coef_e[3 b + .]))                  per corner and b: the corner's share of dLoss/dY_b.
+ *   The end.   gY_b = the pairwise sum over the corners of y_e,b;  du = sum over b >= 1 of gY_b * grad Y_b(u), the basis differentiated
+ *              as the polynomials written above, component by component in increasing b, each term as (constant * u_j) * gY_b
+ *              (degree 1: constant * gY_b; the doubled constants 0.63078314, 1.26156628, 1.09254844 for Y_6 and Y_8);
+ *              gd_i = ((gd_i + (du_i - u_i * (u . du)) / L) + (g_dt * -(step / ((L * L) * L))) * d_i) + (g_L / L) * d_i;
+ *              when entry > t_near, with i the first axis that attains entry:  r = g_t0 / d_i;  go_i -= r;  gd_i -= r * t0;
+ *              when exit < t_far, with i the first axis that attains exit:     r = g_t1 / d_i;  go_i -= r;  gd_i -= r * t1.
+ *              d_rays = (go, gd).  A MISS gives six zeros.
+ * d_rays is WRITTEN, not added; one lane stores a ray's six floats and no other ray touches them: no atomic, BIT-IDENTICAL from run to
+ * run.  A sample whose eight sigma_e are all 0 contributes exactly nothing (h_e = 0, w_k = 0, Z_k = 0), so the march jumps over empty
+ * blocks exactly as step 5 lets the renderer: d_rays with use_skip 0 and 1 are EQUAL.  The check outputs rgb_check, acc_check and
+ * depth_check receive the forward values, the renderer's own bit for bit.  expf is the one operation a restatement in another fp32
+ * arithmetic cannot be held to bit for bit, as in the render rule.
  */
 #ifndef MI_NERF_VOX_H
 #define MI_NERF_VOX_H
@@ -255,6 +290,21 @@ int mi_vox_seen(const mi_vox_grid* grid, const mi_vox_view* view, const float* t
  * is read only and shares no byte with sigma_out_dev or coef_dev. */
 int mi_vox_prune_seen(const mi_vox_grid* grid, int B, float tau, float od_max, const float* sigma_in_dev, const float* od_dev, float* sigma_out_dev,
                       float* coef_dev, void* stream);
+
+/* THE RAY GRADIENT RULE (added within ABI 2: nothing earlier changed).  grid, B, sigma_dev, coef_dev, skip_dev, rays_dev, n and cfg as
+ * mi_vox_render takes them, with its NULL, alignment and n == 0 conventions.  g_rgb_dev [n, 3]; g_acc_dev and g_depth_dev [n] may each be
+ * NULL (zeros); d_rays_dev [n, 6] is written and shares no byte with rays_dev; rgb_check_dev [n, 3], acc_check_dev and depth_check_dev [n]
+ * may each be NULL.  Every float array 4-byte aligned. */
+int mi_vox_render_backward_rays(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev,
+                                const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, const float* g_rgb_dev, const float* g_acc_dev,
+                                const float* g_depth_dev, float* d_rays_dev, float* rgb_check_dev, float* acc_check_dev, float* depth_check_dev,
+                                void* stream);
+
+/* The same for THE COMPACT GRID: fmt, slot_dev, table_dev and M as mi_vox_render_sparse takes them. */
+int mi_vox_render_sparse_backward_rays(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev,
+                                       int64_t M, const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg,
+                                       const float* g_rgb_dev, const float* g_acc_dev, const float* g_depth_dev, float* d_rays_dev, float* rgb_check_dev,
+                                       float* acc_check_dev, float* depth_check_dev, void* stream);
 
 #ifdef __cplusplus
 }

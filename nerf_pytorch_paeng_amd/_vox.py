@@ -56,6 +56,8 @@ SIGNATURES = {
     "mi_vox_shadow": (_I, [_GRIDP, _P, _P, _VIEWP, _P, _P]),
     "mi_vox_seen": (_I, [_GRIDP, _VIEWP, _P, C.c_int32, _P, _P]),
     "mi_vox_prune_seen": (_I, [_GRIDP, _I, _F, _F, _P, _P, _P, _P, _P]),
+    "mi_vox_render_backward_rays": (_I, [_GRIDP, _I, _P, _P, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mi_vox_render_sparse_backward_rays": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 lib, check, last_error = loader(globals(), "mi_vox")

@@ -223,6 +223,38 @@ class RadianceGrid:
                                             dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
                                             dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render")
 
+    def render_backward_rays(self, rays: torch.Tensor, g_rgb: torch.Tensor, g_acc: Optional[torch.Tensor] = None,
+                             g_depth: Optional[torch.Tensor] = None, step: Optional[float] = None, near: float = 0.0, far: float = math.inf,
+                             T_min: float = 0.0, bg=(1.0, 1.0, 1.0), skip: bool = True, check: bool = False):
+        """d_rays [n,6], the gradient of a loss on ``render``'s rgb, acc and depth with respect to rays [n,6] under g_rgb [n,3] (and g_acc,
+        g_depth [n]; None: zeros) by THE RAY GRADIENT RULE (mi_vox_render_backward_rays): written, not added, bit-identical from run to run
+        and equal with and without the skip plane.  ``check=True`` returns (d_rays, rgb [n,3], acc [n], depth [n]): the forward the entry
+        recomputed, ``render``'s own bits.  The other arguments are ``render``'s."""
+        self._need()
+        dev = self.sigma.device
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+            raise MiNerfError(f"rays [n,6] expected, got {tuple(rays.shape) if isinstance(rays, torch.Tensor) else type(rays).__name__}")
+        if rays.device != dev:
+            raise MiNerfError(f"rays live on {rays.device}, the grid on {dev}")
+        n = rays.shape[0]
+        if not isinstance(g_rgb, torch.Tensor) or tuple(g_rgb.shape) != (n, 3) or any(t is not None and tuple(t.shape) != (n,) for t in (g_acc, g_depth)):
+            raise MiNerfError(f"g_rgb [{n},3] and g_acc, g_depth [{n}] expected")
+        cfg = RenderCfg(float(0.5 * self.cell_edge() if step is None else step), float(near), float(far), float(T_min),
+                        (C.c_float * 3)(*(float(v) for v in bg)), int(bool(skip)))
+        d_rays = torch.empty(n, 6, dtype=torch.float32, device=dev)
+        rgb = torch.empty(n, 3, dtype=torch.float32, device=dev) if check else None
+        acc, depth = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2)) if check else (None, None)
+        with ops._guard(dev):
+            self._launch_ray_grad(rays, n, cfg, (dev_ptr(g_rgb, "g_rgb"), dev_ptr(g_acc, "g_acc"), dev_ptr(g_depth, "g_depth"), dev_ptr(d_rays, "d_rays"),
+                                                 dev_ptr(rgb, "rgb_check"), dev_ptr(acc, "acc_check"), dev_ptr(depth, "depth_check"), stream_ptr(dev)))
+        return (d_rays, rgb, acc, depth) if check else d_rays
+
+    def _launch_ray_grad(self, rays, n, cfg, tail) -> None:
+        g = self.c_grid()
+        _vox.check(_vox.lib().mi_vox_render_backward_rays(C.byref(g), self.B, dev_ptr(self.sigma.detach(), "sigma"),
+                                                          dev_ptr(self.coef.detach(), "coef", torch.float32, 16), dev_ptr(self.skip, "skip", torch.uint8, 1),
+                                                          dev_ptr(rays, "rays"), n, C.byref(cfg), *tail), "mi_vox_render_backward_rays")
+
     def compact(self, storage: str = "fp32") -> "SparseRadianceGrid":
         """The same grid as a SparseRadianceGrid: mi_vox_index, one read-back of the count, mi_vox_pack.  sigma and skip are copies."""
         self._need()
@@ -457,6 +489,14 @@ class SparseRadianceGrid(RadianceGrid):
                                                    dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
                                                    dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
                                                    dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render_sparse")
+
+    def _launch_ray_grad(self, rays, n, cfg, tail) -> None:
+        g = self.c_grid()
+        _vox.check(_vox.lib().mi_vox_render_sparse_backward_rays(C.byref(g), self.B, self.fmt, dev_ptr(self.sigma, "sigma"),
+                                                                 dev_ptr(self.slot, "slot", torch.int32),
+                                                                 dev_ptr(self.table, "table", STORAGES[self.storage][1], 16) if self.count else None,
+                                                                 self.count, dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n,
+                                                                 C.byref(cfg), *tail), "mi_vox_render_sparse_backward_rays")
 
     def compact(self, storage: str = "fp32") -> "SparseRadianceGrid":
         raise MiNerfError("the grid is compact already")

@@ -44,6 +44,13 @@
 //                          float of tvol and folds it into its own element of the od plane (a coalesced read-modify-write).  No LDS.
 //   prune_seen_kernel<B>   THE SEEN PRUNING RULE: prune_kernel with the seed's second condition, a kernel of its own so that
 //                          prune_kernel's code stays what it was.
+//   ray_grad_kernel<B, ST> THE RAY GRADIENT RULE: the renderer's group of 8 lanes per ray and its three storages.  March 1 is the renderer's loop
+//                          operation by operation (the check outputs are its bits) plus S = sum w_k s_k.  March 2 walks the same samples with
+//                          the prefix P and jumps over empty blocks as march 1 does (a sample without density adds exact zeros): per sample
+//                          lane e forms h_e from its corner's sigma and colour, three more group sums give dL/dp, and the sums to o, d, t0,
+//                          dt, t1, L and lane e's share of dL/dY_b stay in registers.  At the ray's end the shares are group-summed, the
+//                          basis, dt, L and the slab's entry and exit are differentiated, and lane 0 stores six floats.  A struct of its own
+//                          (RayGradArgs), so that RenderArgs and the renderer's code stay what they were.
 //
 // No atomic, no host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
 #include <hip/hip_runtime.h>
@@ -629,6 +636,301 @@ __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// mi_vox_render_backward_rays, mi_vox_render_sparse_backward_rays
+// ------------------------------------------------------------------------------------------------
+struct RayGradArgs {
+    Lattice g;
+    const float* sigma;
+    const float4* coef;                                  // the dense coef array, or the table of a compact grid (either format)
+    const int* slot;                                     // compact grids only
+    long long M;
+    const uint8_t* skip;
+    const float* rays;
+    long long n;
+    float step, t_near, t_far, T_min;
+    float bg[3];
+    int use_skip;
+    int max_steps;
+    const float *g_rgb, *g_acc, *g_depth;
+    float* d_rays;
+    float *rgb, *acc, *depth;                            // the check outputs
+};
+
+template <int B, int ST>
+__global__ __launch_bounds__(THREADS) void ray_grad_kernel(const RayGradArgs a) {
+    const int e = threadIdx.x & (GROUP - 1);               // this lane's corner
+    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 3);
+    if (ray >= a.n) return;                                // a whole group leaves together
+    const Lattice& g = a.g;
+    const float* rp = a.rays + ray * 6;
+    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
+    const float L = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    bool miss = !(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(L)) || L == 0.0f;
+    float entry = -INFINITY, exit_ = INFINITY;
+    int ie = -1, ix = -1;                                  // the axes that give entry and exit
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (d[i] != 0.0f) {
+            const float ta = (g.lo[i] - o[i]) / d[i], tb = (g.hi[i] - o[i]) / d[i];
+            const float tn = fminf(ta, tb), tf = fmaxf(ta, tb);
+            if (tn > entry) ie = i;
+            if (tf < exit_) ix = i;
+            entry = fmaxf(entry, tn);
+            exit_ = fminf(exit_, tf);
+        } else if (!(g.lo[i] <= o[i] && o[i] <= g.hi[i])) {
+            miss = true;
+        }
+    }
+    const float t0 = fmaxf(a.t_near, entry), t1 = fminf(a.t_far, exit_);
+    if (!(t1 > t0)) miss = true;
+    if (!(entry > a.t_near)) ie = -1;                      // t0 = t_near: fixed
+    if (!(exit_ < a.t_far)) ix = -1;                       // t1 = t_far: fixed
+    // upstream
+    const float G[3] = {a.g_rgb[ray * 3 + 0], a.g_rgb[ray * 3 + 1], a.g_rgb[ray * 3 + 2]};
+    const float ga = a.g_acc ? a.g_acc[ray] : 0.0f, gd = a.g_depth ? a.g_depth[ray] : 0.0f;
+    const float gap = ga - ((G[0] * a.bg[0] + G[1] * a.bg[1]) + G[2] * a.bg[2]);
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, sd = 0.0f;
+    float go[3] = {0.0f, 0.0f, 0.0f}, gdir[3] = {0.0f, 0.0f, 0.0f};
+    if (!miss) {
+        const float dt = a.step / L;
+        const float ux = d[0] / L, uy = d[1] / L, uz = d[2] / L;
+        float Y[B];
+        sh_basis<B>(ux, uy, uz, Y);
+        // jumping over an empty block: allowed only where the fp32 position error stays below an eighth of a cell
+        const float tmax = fmaxf(fabsf(t0), fabsf(t1));
+        float gu[3], gv[3];
+        bool can_jump = a.use_skip != 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            gu[i] = (o[i] - g.lo[i]) * g.inv[i];
+            gv[i] = d[i] * g.inv[i];
+            const float err = 16.0f * EPS32 * (fabsf(o[i]) + tmax * fabsf(d[i]) + fabsf(g.lo[i]) + fabsf(g.hi[i])) * g.inv[i];
+            can_jump = can_jump && err <= 0.125f;
+        }
+        const int ex = e & 1, ey = (e >> 1) & 1, ez = e >> 2;
+        // ---- march 1: the renderer's loop, and S ----------------------------------------------------------
+        float S = 0.0f;
+        {
+            float T = 1.0f;
+            int k = 0;
+            while (k < a.max_steps) {
+                const float ak = t0 + (float)k * dt;
+                if (!(ak < t1)) break;
+                const float bk = fminf(t0 + (float)(k + 1) * dt, t1);
+                const float mk = 0.5f * (ak + bk);
+                int c[3];
+                float f[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const float p = o[i] + mk * d[i];
+                    cell_of((p - g.lo[i]) * g.inv[i], g.res[i], c[i], f[i]);
+                }
+                if (a.use_skip) {
+                    const int bx = c[0] >> 3, by = c[1] >> 3, bz = c[2] >> 3;
+                    if (a.skip[(bz * g.nb[1] + by) * g.nb[0] + bx] == 0) {
+                        int next = k + 1;
+                        if (can_jump) {
+                            const int bb[3] = {bx, by, bz};
+                            float t_exit = INFINITY;
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) {
+                                const float far_ = (float)min(BLK * bb[i] + BLK, g.res[i]) + 0.5f, near_ = (float)(BLK * bb[i]) - 0.5f;
+                                if (gv[i] > 0.0f) t_exit = fminf(t_exit, (far_ - gu[i]) / gv[i]);
+                                else if (gv[i] < 0.0f) t_exit = fminf(t_exit, (near_ - gu[i]) / gv[i]);
+                            }
+                            const float kf = floorf((t_exit - t0) / dt) - 1.0f;
+                            if (kf > (float)next) next = (int)fminf(kf, (float)a.max_steps);
+                        }
+                        k = next;
+                        continue;
+                    }
+                }
+                const long long at = ((long long)(c[2] + ez) * g.P[1] + (c[1] + ey)) * g.P[0] + (c[0] + ex);
+                const float wx = ex ? f[0] : 1.0f - f[0], wy = ey ? f[1] : 1.0f - f[1], wz = ez ? f[2] : 1.0f - f[2];
+                const float w = (wx * wy) * wz;
+                const float sigma_s = group_sum(w * a.sigma[at]);
+                const float delta = (bk - ak) * L;
+                const float alpha = 1.0f - expf(-(sigma_s * delta));
+                const float wt = T * alpha;
+                float col[3] = {0.0f, 0.0f, 0.0f};
+                if (sigma_s > 0.0f) {
+                    float kc[record_regs<B, ST>()];
+                    fetch_record<B, ST>(a.coef, a.slot, a.M, at, kc);
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        float q = kc[ch] * Y[0];
+#pragma unroll
+                        for (int b = 1; b < B; ++b) q += kc[3 * b + ch] * Y[b];
+                        col[ch] = fminf(fmaxf(group_sum(w * q), 0.0f), 1.0f);
+                    }
+                    sr += wt * col[0]; sg += wt * col[1]; sb += wt * col[2];
+                }
+                const float sk = (((G[0] * col[0] + G[1] * col[1]) + G[2] * col[2]) + gap) + gd * mk;
+                S += wt * sk;
+                sw += wt;
+                sd += wt * mk;
+                T = T * (1.0f - alpha);
+                ++k;
+                if (T < a.T_min) break;
+            }
+        }
+        // ---- march 2: the same samples (it jumps as march 1 does), the prefix P, the sums of THE RAY GRADIENT RULE --------
+        {
+            float T = 1.0f, P = 0.0f;
+            float gpo[3] = {0.0f, 0.0f, 0.0f}, gpd[3] = {0.0f, 0.0f, 0.0f};       // sum g_p, sum m_k g_p
+            float gt0 = 0.0f, gdt = 0.0f, gt1 = 0.0f, gL = 0.0f;
+            float gy[B];                                                       // this lane's share of dL/dY_b
+#pragma unroll
+            for (int b = 0; b < B; ++b) gy[b] = 0.0f;
+            int k = 0;
+            while (k < a.max_steps) {
+                const float ak = t0 + (float)k * dt;
+                if (!(ak < t1)) break;
+                const float nk = t0 + (float)(k + 1) * dt;
+                const float bk = fminf(nk, t1);
+                const bool cut = t1 < nk;                                      // the truncated last interval
+                const float mk = 0.5f * (ak + bk);
+                int c[3];
+                float f[3];
+                bool moves[3];                                                 // the clamp of f_i is not active
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const float p = o[i] + mk * d[i];
+                    const float gi = (p - g.lo[i]) * g.inv[i];
+                    cell_of(gi, g.res[i], c[i], f[i]);
+                    const float r = gi - (float)c[i];
+                    moves[i] = r >= 0.0f && r <= 1.0f;
+                }
+                if (a.use_skip) {
+                    const int bx = c[0] >> 3, by = c[1] >> 3, bz = c[2] >> 3;
+                    if (a.skip[(bz * g.nb[1] + by) * g.nb[0] + bx] == 0) {
+                        int next = k + 1;
+                        if (can_jump) {
+                            const int bb[3] = {bx, by, bz};
+                            float t_exit = INFINITY;
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) {
+                                const float far_ = (float)min(BLK * bb[i] + BLK, g.res[i]) + 0.5f, near_ = (float)(BLK * bb[i]) - 0.5f;
+                                if (gv[i] > 0.0f) t_exit = fminf(t_exit, (far_ - gu[i]) / gv[i]);
+                                else if (gv[i] < 0.0f) t_exit = fminf(t_exit, (near_ - gu[i]) / gv[i]);
+                            }
+                            const float kf = floorf((t_exit - t0) / dt) - 1.0f;
+                            if (kf > (float)next) next = (int)fminf(kf, (float)a.max_steps);
+                        }
+                        k = next;
+                        continue;
+                    }
+                }
+                const long long at = ((long long)(c[2] + ez) * g.P[1] + (c[1] + ey)) * g.P[0] + (c[0] + ex);
+                const float wx = ex ? f[0] : 1.0f - f[0], wy = ey ? f[1] : 1.0f - f[1], wz = ez ? f[2] : 1.0f - f[2];
+                const float w = (wx * wy) * wz;
+                const float se = a.sigma[at];
+                const float sigma_s = group_sum(w * se);
+                const float delta = (bk - ak) * L;
+                const float alpha = 1.0f - expf(-(sigma_s * delta));
+                const float wt = T * alpha;
+                float qe[3] = {0.0f, 0.0f, 0.0f}, col[3] = {0.0f, 0.0f, 0.0f}, Q[3] = {0.0f, 0.0f, 0.0f};
+                float kc[record_regs<B, ST>()];
+#pragma unroll
+                for (int i = 0; i < record_regs<B, ST>(); ++i) kc[i] = 0.0f;
+                if (sigma_s > 0.0f) {
+                    fetch_record<B, ST>(a.coef, a.slot, a.M, at, kc);
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        float q = kc[ch] * Y[0];
+#pragma unroll
+                        for (int b = 1; b < B; ++b) q += kc[3 * b + ch] * Y[b];
+                        qe[ch] = q;
+                        const float qs = group_sum(w * q);
+                        col[ch] = fminf(fmaxf(qs, 0.0f), 1.0f);
+                        Q[ch] = (qs >= 0.0f && qs <= 1.0f) ? wt * G[ch] : 0.0f;
+                    }
+                }
+                const float sk = (((G[0] * col[0] + G[1] * col[1]) + G[2] * col[2]) + gap) + gd * mk;
+                const float E = T * sk - (S - P);
+                const float Dk = delta * E, Lk = sigma_s * E;                    // dL/d sigma_s, dL/d delta_k
+                const float h = Dk * se + ((Q[0] * qe[0] + Q[1] * qe[1]) + Q[2] * qe[2]);
+                const float yz = wy * wz, xz = wx * wz, xy = wx * wy;
+                const float dwx = moves[0] ? (ex ? yz : -yz) : 0.0f;
+                const float dwy = moves[1] ? (ey ? xz : -xz) : 0.0f;
+                const float dwz = moves[2] ? (ez ? xy : -xy) : 0.0f;
+                const float gp[3] = {g.inv[0] * group_sum(dwx * h), g.inv[1] * group_sum(dwy * h), g.inv[2] * group_sum(dwz * h)};
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    gpo[i] += gp[i];
+                    gpd[i] += mk * gp[i];
+                }
+                const float Mk = ((d[0] * gp[0] + d[1] * gp[1]) + d[2] * gp[2]) + gd * wt;   // dL/dm_k
+                if (!cut) {
+                    gt0 += Mk;
+                    gdt += ((float)k + 0.5f) * Mk;
+                } else {
+                    const float hm = 0.5f * Mk, ld = L * Lk;
+                    const float lower = hm - ld;
+                    gt0 += lower;
+                    gdt += (float)k * lower;
+                    gt1 += hm + ld;
+                    gL += (t1 - ak) * Lk;
+                }
+#pragma unroll
+                for (int b = 0; b < B; ++b) gy[b] += (Q[0] * (w * kc[3 * b]) + Q[1] * (w * kc[3 * b + 1])) + Q[2] * (w * kc[3 * b + 2]);
+                P += wt * sk;
+                T = T * (1.0f - alpha);
+                ++k;
+                if (T < a.T_min) break;
+            }
+            // ---- the ray's end: the basis, dt, L, entry and exit --------------------------------------------
+            float du[3] = {0.0f, 0.0f, 0.0f};                                   // dL/du = sum over b of dL/dY_b grad Y_b(u), increasing b
+            if constexpr (B >= 4) {
+                const float y1 = group_sum(gy[1]), y2 = group_sum(gy[2]), y3 = group_sum(gy[3]);
+                du[1] = -0.48860251f * y1;
+                du[2] = 0.48860251f * y2;
+                du[0] = -0.48860251f * y3;
+            }
+            if constexpr (B >= 9) {
+                const float y4 = group_sum(gy[4]), y5 = group_sum(gy[5]), y6 = group_sum(gy[6]), y7 = group_sum(gy[7]), y8 = group_sum(gy[8]);
+                du[0] += (1.0925484f * uy) * y4;   du[1] += (1.0925484f * ux) * y4;
+                du[1] += (-1.0925484f * uz) * y5;  du[2] += (-1.0925484f * uy) * y5;
+                du[0] += (-0.63078314f * ux) * y6; du[1] += (-0.63078314f * uy) * y6; du[2] += (1.26156628f * uz) * y6;
+                du[0] += (-1.0925484f * uz) * y7;  du[2] += (-1.0925484f * ux) * y7;
+                du[0] += (1.09254844f * ux) * y8;  du[1] += (-1.09254844f * uy) * y8;
+            }
+            const float u[3] = {ux, uy, uz};
+            const float udu = (ux * du[0] + uy * du[1]) + uz * du[2];
+            const float cdt = gdt * -(a.step / ((L * L) * L)), cl = gL / L;
+            const float q0 = ie >= 0 ? gt0 / (ie == 0 ? d[0] : ie == 1 ? d[1] : d[2]) : 0.0f;
+            const float q1 = ix >= 0 ? gt1 / (ix == 0 ? d[0] : ix == 1 ? d[1] : d[2]) : 0.0f;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                go[i] = gpo[i];
+                gdir[i] = ((gpd[i] + (du[i] - u[i] * udu) / L) + cdt * d[i]) + cl * d[i];
+                if (i == ie) {
+                    go[i] -= q0;
+                    gdir[i] -= q0 * t0;
+                }
+                if (i == ix) {
+                    go[i] -= q1;
+                    gdir[i] -= q1 * t1;
+                }
+            }
+        }
+    }
+    if (e == 0) {
+        float* out = a.d_rays + ray * 6;
+        out[0] = go[0]; out[1] = go[1]; out[2] = go[2];
+        out[3] = gdir[0]; out[4] = gdir[1]; out[5] = gdir[2];
+        const float rest = 1.0f - sw;
+        if (a.rgb) {
+            a.rgb[ray * 3 + 0] = sr + rest * a.bg[0];
+            a.rgb[ray * 3 + 1] = sg + rest * a.bg[1];
+            a.rgb[ray * 3 + 2] = sb + rest * a.bg[2];
+        }
+        if (a.acc) a.acc[ray] = sw;
+        if (a.depth) a.depth[ray] = sd;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side: checks, launches
 // ------------------------------------------------------------------------------------------------
 // vox_rule.h's checks under this library's status values
@@ -724,6 +1026,55 @@ static int render(const char* who, bool sparse, const mi_vox_grid* grid, int B, 
     else if (fmt == MI_VOX_FMT_F32) launch_render<SPARSE32>(B, blocks, st, a);
     else launch_render<SPARSE16>(B, blocks, st, a);
     VOX_LAUNCH_CHECK("render_kernel");
+    return MI_VOX_OK;
+}
+
+template <int ST>
+static void launch_ray_grad(int B, dim3 blocks, hipStream_t st, const RayGradArgs& a) {
+    if (B == 1) hipLaunchKernelGGL((ray_grad_kernel<1, ST>), blocks, dim3(THREADS), 0, st, a);
+    else if (B == 4) hipLaunchKernelGGL((ray_grad_kernel<4, ST>), blocks, dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL((ray_grad_kernel<9, ST>), blocks, dim3(THREADS), 0, st, a);
+}
+
+// mi_vox_render_backward_rays (slot_dev NULL, fmt and M unused) and mi_vox_render_sparse_backward_rays: render()'s checks and conventions
+static int ray_grad(const char* who, bool sparse, const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const void* coef_dev,
+                    const int32_t* slot_dev, int64_t M, const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg,
+                    const float* g_rgb_dev, const float* g_acc_dev, const float* g_depth_dev, float* d_rays_dev, float* rgb_check_dev,
+                    float* acc_check_dev, float* depth_check_dev, void* stream) {
+    RayGradArgs a{};
+    if (int rc = check_grid(who, grid, &a.g)) return rc;
+    if (int rc = check_basis(who, B)) return rc;
+    if (sparse) {
+        VOX_CHECK_ARG(fmt == MI_VOX_FMT_F32 || fmt == MI_VOX_FMT_F16, "%s: fmt=%d: MI_VOX_FMT_F32 (0) or MI_VOX_FMT_F16 (1)", who, fmt);
+        VOX_CHECK_ARG(M >= 0 && M <= (int64_t)a.g.P[0] * a.g.P[1] * a.g.P[2], "%s: M=%lld: 0 .. the lattice's points", who, (long long)M);
+    }
+    int64_t steps;
+    if (int rc = check_march(who, grid, cfg, n, &steps)) return rc;
+    if (n == 0) return MI_VOX_OK;                                      // no work: the arrays of an empty ray set may be NULL
+    if (sparse) {
+        VOX_CHECK_ARG(sigma_dev && slot_dev && rays_dev && g_rgb_dev && d_rays_dev && (coef_dev || M == 0), "%s: NULL pointer", who);
+        VOX_CHECK_ARG(aligned(coef_dev, 16) && aligned(slot_dev, 4), "%s: the table must be 16-byte aligned, slot 4-byte aligned", who);
+    } else {
+        VOX_CHECK_ARG(sigma_dev && coef_dev && rays_dev && g_rgb_dev && d_rays_dev, "%s: NULL pointer", who);
+        VOX_CHECK_ARG(aligned(coef_dev, 16), "%s: coef must be 16-byte aligned", who);
+    }
+    VOX_CHECK_ARG(skip_dev || !cfg->use_skip, "%s: use_skip needs the skip plane", who);
+    VOX_CHECK_ARG(aligned(sigma_dev, 4) && aligned(rays_dev, 4) && aligned(g_rgb_dev, 4) && aligned(g_acc_dev, 4) && aligned(g_depth_dev, 4) &&
+                      aligned(d_rays_dev, 4) && aligned(rgb_check_dev, 4) && aligned(acc_check_dev, 4) && aligned(depth_check_dev, 4),
+                  "%s: a float array is not 4-byte aligned", who);
+    VOX_CHECK_ARG(!overlap(d_rays_dev, 24 * (size_t)n, rays_dev, 24 * (size_t)n), "%s: d_rays overlaps rays: the rays are read while d_rays is written", who);
+    a.sigma = sigma_dev; a.coef = reinterpret_cast<const float4*>(coef_dev); a.slot = slot_dev; a.M = M; a.skip = skip_dev; a.rays = rays_dev; a.n = n;
+    a.step = cfg->step; a.t_near = cfg->t_near; a.t_far = cfg->t_far; a.T_min = cfg->T_min;
+    a.bg[0] = cfg->bg[0]; a.bg[1] = cfg->bg[1]; a.bg[2] = cfg->bg[2];
+    a.use_skip = cfg->use_skip; a.max_steps = (int)steps;
+    a.g_rgb = g_rgb_dev; a.g_acc = g_acc_dev; a.g_depth = g_depth_dev; a.d_rays = d_rays_dev;
+    a.rgb = rgb_check_dev; a.acc = acc_check_dev; a.depth = depth_check_dev;
+    const dim3 blocks((unsigned)((n + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK));
+    hipStream_t st = (hipStream_t)stream;
+    if (!sparse) launch_ray_grad<DENSE>(B, blocks, st, a);
+    else if (fmt == MI_VOX_FMT_F32) launch_ray_grad<SPARSE32>(B, blocks, st, a);
+    else launch_ray_grad<SPARSE16>(B, blocks, st, a);
+    VOX_LAUNCH_CHECK("ray_grad_kernel");
     return MI_VOX_OK;
 }
 
@@ -972,6 +1323,22 @@ int mi_vox_prune_seen(const mi_vox_grid* grid, int B, float tau, float od_max, c
     else hipLaunchKernelGGL(prune_seen_kernel<9>, blocks, dim3(THREADS), 0, st, g, tau, od_max, sigma_in_dev, od_dev, sigma_out_dev, coef4, pieces);
     VOX_LAUNCH_CHECK("prune_seen_kernel");
     return MI_VOX_OK;
+}
+
+int mi_vox_render_backward_rays(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev,
+                                const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, const float* g_rgb_dev, const float* g_acc_dev,
+                                const float* g_depth_dev, float* d_rays_dev, float* rgb_check_dev, float* acc_check_dev, float* depth_check_dev,
+                                void* stream) {
+    return ray_grad("mi_vox_render_backward_rays", false, grid, B, MI_VOX_FMT_F32, sigma_dev, coef_dev, nullptr, 0, skip_dev, rays_dev, n, cfg, g_rgb_dev,
+                    g_acc_dev, g_depth_dev, d_rays_dev, rgb_check_dev, acc_check_dev, depth_check_dev, stream);
+}
+
+int mi_vox_render_sparse_backward_rays(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev,
+                                       int64_t M, const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg,
+                                       const float* g_rgb_dev, const float* g_acc_dev, const float* g_depth_dev, float* d_rays_dev, float* rgb_check_dev,
+                                       float* acc_check_dev, float* depth_check_dev, void* stream) {
+    return ray_grad("mi_vox_render_sparse_backward_rays", true, grid, B, fmt, sigma_dev, table_dev, slot_dev, M, skip_dev, rays_dev, n, cfg, g_rgb_dev,
+                    g_acc_dev, g_depth_dev, d_rays_dev, rgb_check_dev, acc_check_dev, depth_check_dev, stream);
 }
 
 }  // extern "C"
