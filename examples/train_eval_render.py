@@ -6,7 +6,7 @@ reference's names and call shapes (train.py:12, test.py:17, test.py:111); swap t
                                              [--scene teacher|solid] [--mesh PATH.ply [--mesh-res 128] [--mesh-iso 10] [--mesh-view]]
                                              [--train-occupancy WARMUP:EVERY] [--geometry ACC:DEPTH:DIST]
                                              [--fused-adam] [--lr-min LR --warmup STEPS] [--bake RES[:B[:STORAGE]] [--bake-finetune STEPS [--bake-reg TV_SIGMA:TV_COEF:SPARSITY] [--bake-optimizer adam|lazy]
-                                             [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]] [--bake-prune-seen T_VIS] [--bake-locate DEG:DIST]]
+                                             [--bake-levels RES:STEPS[,RES:STEPS...]] [--bake-prune TAU]] [--bake-prune-seen T_VIS] [--bake-locate DEG:DIST] [--bake-signed [CLIP]]]
 
 ``--scene solid``: the dataset is scenes.SolidScene.default() -- opaque solids in empty space on a white background, ground truth rendered by
 mi_scene_render -- instead of views of a random network.  ``--mesh PATH``: after training, the fine network's density on a (mesh-res + 1)^3 lattice of the box
@@ -31,6 +31,9 @@ records, Cauchy sparsity of the density; e.g. 0.01:0.01:0.01) and is refused wit
 level's resolution -- eight times fewer evaluations per halving -- and each level's steps are followed by a resample to the next
 (RadianceGrid.resample); the final level is ``--bake`` RES with ``--bake-finetune`` STEPS.  ``--bake-prune TAU`` ends every level with
 RadianceGrid.prune(TAU): density and records are cleared away from density above TAU.  Both are refused without ``--bake RES --bake-finetune STEPS``.
+``--bake-signed [CLIP]`` (any storage) bakes A SIGNED GRID (docs/design/29_signed_density.md): the plane is the network's density before its
+ReLU, clamped to [-CLIP, CLIP] when CLIP is given, the ReLU is applied after the interpolation, and ``--bake-finetune`` trains it without the
+clamp at 0.  It is refused together with ``--bake-prune-seen`` and ``--bake-locate``, whose rules read the density without the ReLU.
 ``--bake-prune-seen T_VIS`` (dense storage) prunes the grid by the training views (RadianceGrid.seen, RadianceGrid.prune(seen=...)): after the
 bake, and with ``--bake-levels`` after every level instead; active points, record MiB and the held-out PSNR are printed before and after.
 ``--bake-locate DEG:DIST`` (any storage) turns the first held-out pose by DEG degrees and moves it by DIST, then recovers it against the
@@ -82,6 +85,8 @@ def main(argv=None):
     ap.add_argument("--bake-levels", default=None, metavar="RES:STEPS[,RES:STEPS...]",
                     help="with --bake RES --bake-finetune STEPS: bake at the first level's resolution and train coarse to fine through these levels; the final level is RES with STEPS steps")
     ap.add_argument("--bake-prune", type=float, default=None, metavar="TAU", help="with --bake-finetune: after each level, clear density and records away from density above TAU")
+    ap.add_argument("--bake-signed", type=float, nargs="?", const=0.0, default=None, metavar="CLIP",
+                    help="with --bake: a signed grid -- the density before its ReLU, clamped to [-CLIP, CLIP] when CLIP is given, the ReLU after the interpolation")
     ap.add_argument("--bake-prune-seen", type=float, default=None, metavar="T_VIS",
                     help="with --bake (dense): prune the grid by the training views -- density stays only around points that some training view sees with "
                          "transmittance at least T_VIS; after the bake, and after every level with --bake-levels")
@@ -109,6 +114,11 @@ def main(argv=None):
             ap.error("--bake-prune-seen needs --bake with dense storage (prune dense, then compact)")
         if not 0.0 <= a.bake_prune_seen <= 1.0:
             ap.error("--bake-prune-seen takes a transmittance, 0 .. 1")
+    if a.bake_signed is not None:
+        if a.bake is None or not (np.isfinite(a.bake_signed) and a.bake_signed >= 0):
+            ap.error("--bake-signed takes an optional CLIP, a finite number > 0, and needs --bake RES")
+        if a.bake_prune_seen is not None or a.bake_locate is not None:
+            ap.error("--bake-signed: --bake-prune-seen and --bake-locate read the density without the ReLU and refuse a signed grid")
     bake_reg = {}
     if a.bake_reg is not None:
         if not a.bake_finetune:
@@ -244,10 +254,12 @@ def main(argv=None):
         from nerf_pytorch_paeng_amd import baked
         t_bake = time.perf_counter()
         if bake_storage == "dense":
-            grid = baked.RadianceGrid(-a.mesh_box, a.mesh_box, bake_levels[0][0] if bake_levels else bake_res, B=bake_B)      # coarse to fine: the first level's lattice
+            grid = baked.RadianceGrid(-a.mesh_box, a.mesh_box, bake_levels[0][0] if bake_levels else bake_res, B=bake_B,
+                                      signed=a.bake_signed is not None)                                                      # coarse to fine: the first level's lattice
         else:
-            grid = baked.SparseRadianceGrid(-a.mesh_box, a.mesh_box, bake_res, B=bake_B, storage="f16" if bake_storage == "sparse16" else "fp32")
-        grid = grid.bake(fresh, network="fine", precision=a.precision)
+            grid = baked.SparseRadianceGrid(-a.mesh_box, a.mesh_box, bake_res, B=bake_B, storage="f16" if bake_storage == "sparse16" else "fp32",
+                                            signed=a.bake_signed is not None)
+        grid = grid.bake(fresh, network="fine", precision=a.precision, clip=a.bake_signed or None)
         torch.cuda.synchronize()
         t_bake = time.perf_counter() - t_bake
         opts.baked = grid                                                                        # the same poses, from the grid alone
@@ -256,7 +268,7 @@ def main(argv=None):
         t_grid = time.perf_counter() - t_grid
         opts.baked = None
         mse = np.mean((rgbs_g.astype(np.float64) - rgbs.astype(np.float64)) ** 2, axis=(1, 2, 3)) / 255.0 ** 2
-        print(f"bake: {grid.res[0]}^3 cells, B={bake_B}, {bake_storage}, {grid.nbytes / 2 ** 20:.1f} MiB in {t_bake:.2f} s; {rgbs_g.shape[0]} frames from the grid in {t_grid * 1e3:.1f} ms "
+        print(f"bake: {grid.res[0]}^3 cells, B={bake_B}, {bake_storage}{', signed' if grid.signed else ''}, {grid.nbytes / 2 ** 20:.1f} MiB in {t_bake:.2f} s; {rgbs_g.shape[0]} frames from the grid in {t_grid * 1e3:.1f} ms "
               f"(the network: {t_net * 1e3:.1f} ms, PNG writing included in both); PSNR of the grid's frames against the network's "
               f"{['%.2f' % (-10.0 * np.log10(max(m, 1e-12))) for m in mse]} dB; {a.out}/render_baked")
         from nerf_pytorch_paeng_amd.rays import make_o_d

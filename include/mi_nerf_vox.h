@@ -166,6 +166,32 @@
  * blocks exactly as step 5 lets the renderer: d_rays with use_skip 0 and 1 are EQUAL.  The check outputs rgb_check, acc_check and
  * depth_check receive the forward values, the renderer's own bit for bit.  expf is the one operation a restatement in another fp32
  * arithmetic cannot be held to bit for bit, as in the render rule.
+ *
+ * A SIGNED GRID (mi_vox_build_skip_signed, mi_vox_render_signed, mi_vox_render_sparse_signed) stores the density BEFORE its ReLU and
+ * applies the ReLU after the interpolation.  The zero crossing of a trilinear function can lie anywhere inside a cell, so a surface is
+ * no longer bound to lattice planes and a cell with one dense corner is no longer fogged; a negative value is "empty, with headroom".
+ *   sigma   float [P_z, P_y, P_x], finite, of any sign.  coef, the compact grid's slot and table, and active are what they are above.
+ *   render  Step 3 of THE RENDER RULE becomes sigma_s = fmaxf(the interpolation of sigma, 0).  Everything else of steps 1 to 5 stays
+ *           word for word; the compact render rule changes in the same one place.
+ *   skip    the signed skip plane's byte is 0 iff sigma <= 0 at every lattice point of the block's cells extended by one cell: the points
+ *           of THE GRID's skip, the test sigma > 0 in the place of sigma != 0.
+ *   Skipping stays exact.  Weights are >= 0, so a sample whose eight corners are <= 0 interpolates to a value <= 0 and has sigma_s = 0:
+ *           it adds exactly nothing.  The jump never passes a sample whose cell lies outside the block extended by one cell.  So rgb,
+ *           disp, acc and depth are BIT-IDENTICAL with use_skip 0 and 1, and visited is the only output that differs.
+ *   On a plane that is >= 0 everywhere fmaxf(x, 0) = x: every output of the three entries, visited and the skip plane included, is
+ *           bit-identical to that of mi_vox_build_skip, mi_vox_render and mi_vox_render_sparse.
+ *   There is no gain factor: the plane is in the units of sigma.
+ * The rest of the tool chain reads a signed plane as it is:
+ *   Activity and compact storage.  A sample with sigma_s > 0 has a corner with sigma > 0 (weights are >= 0), so all eight corners are
+ *           active (mi_vox_index tests sigma > 0): the compact signed renderer equals the dense signed renderer bit for bit.
+ *   mi_vox_prune at tau = 0.  A point that is not kept has sigma <= 0 itself and at its 26 neighbours, so every corner of every cell it
+ *           touches is <= 0 before and after: every sample there has sigma_s = 0 either way, and no output bit changes.
+ *   Invisible negatives.  A point that is <= 0 with all 26 neighbours <= 0 may hold any negative number without changing a bit of any
+ *           render, for the same reason.
+ *   mi_vox_resample is linear in sigma: an integer refinement on the same box represents the identical field (up to rounding), and the
+ *           ReLU is applied to it afterwards as before.
+ * THE SHADOW RULE, THE VISIBILITY RULE, THE SEEN PRUNING RULE and THE RAY GRADIENT RULE read sigma without the ReLU: they are not defined
+ * on a signed plane.
  */
 #ifndef MI_NERF_VOX_H
 #define MI_NERF_VOX_H
@@ -305,6 +331,19 @@ int mi_vox_render_sparse_backward_rays(const mi_vox_grid* grid, int B, int fmt, 
                                        int64_t M, const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg,
                                        const float* g_rgb_dev, const float* g_acc_dev, const float* g_depth_dev, float* d_rays_dev, float* rgb_check_dev,
                                        float* acc_check_dev, float* depth_check_dev, void* stream);
+
+/* A SIGNED GRID (added within ABI 2: nothing earlier changed).  Each entry takes the arguments of its unsigned counterpart -- of
+ * mi_vox_build_skip, mi_vox_render and mi_vox_render_sparse in this order -- with the same NULL, alignment and n == 0 conventions and the
+ * same refusals; sigma_dev is a signed plane and skip_dev a signed skip plane. */
+int mi_vox_build_skip_signed(const mi_vox_grid* grid, const float* sigma_dev, uint8_t* skip_dev, void* stream);
+
+int mi_vox_render_signed(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev, const float* rays_dev,
+                         int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev,
+                         uint32_t* visited_dev, void* stream);
+
+int mi_vox_render_sparse_signed(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev, int64_t M,
+                                const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev,
+                                float* disp_dev, float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,12 @@
  *                touches is not written; a contribution that is exactly 0 is not added.  Consecutive samples of a ray that share a cell
  *                are summed in registers first, the coefficient sums as sum over k of w_e * dL/d q_k[c], multiplied by Y_b(u) once per
  *                cell: a reordering inside the bound above.
+ *   Signed.      The rule's domain is A SIGNED GRID of include/mi_nerf_vox.h as well: sigma of any sign, with
+ *                sigma_s = fmaxf(the interpolation of sigma, 0) in both marches, and skip that header's signed skip plane.
+ *                d_sigma[corner e] += w_e * dL/d sigma_s,k only where the interpolation is >= 0; where it is negative nothing flows
+ *                through the ReLU and nothing is added.  A value of exactly 0 keeps the one-sided derivative written above, so an
+ *                all-zero grid can still learn.  On a plane that is >= 0 everywhere fmaxf(x, 0) = x and this is the rule as written
+ *                above: the check outputs are the unsigned renderer's bits there, and the signed renderer's bits on a signed plane.
  */
 #ifndef MI_NERF_VOXGRAD_H
 #define MI_NERF_VOXGRAD_H

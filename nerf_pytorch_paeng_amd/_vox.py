@@ -58,6 +58,10 @@ SIGNATURES = {
     "mi_vox_prune_seen": (_I, [_GRIDP, _I, _F, _F, _P, _P, _P, _P, _P]),
     "mi_vox_render_backward_rays": (_I, [_GRIDP, _I, _P, _P, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mi_vox_render_sparse_backward_rays": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # A SIGNED GRID: the argument lists of mi_vox_build_skip, mi_vox_render and mi_vox_render_sparse
+    "mi_vox_build_skip_signed": (_I, [_GRIDP, _P, _P, _P]),
+    "mi_vox_render_signed": (_I, [_GRIDP, _I, _P, _P, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P]),
+    "mi_vox_render_sparse_signed": (_I, [_GRIDP, _I, _I, _P, _P, _P, _I64, _P, _P, _I64, _CFGP, _P, _P, _P, _P, _P, _P]),
 }
 
 lib, check, last_error = loader(globals(), "mi_vox")

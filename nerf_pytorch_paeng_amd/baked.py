@@ -9,6 +9,8 @@
     grid.prune(0.5)                                                      # sigma and records cleared away from density > 0.5 (THE PRUNING RULE)
     od = grid.seen(baked.Views(H, W, K, poses))                          # the least optical depth under which a camera sees each point
     grid.prune(0.0, seen=od, T_vis=1e-3)                                 # ... and what no camera sees with transmittance 1e-3 goes too
+    signed = grid.to_signed()                                            # A SIGNED GRID: the density before its ReLU, the ReLU after the interpolation
+    signed = baked.RadianceGrid(-1.2, 1.2, 256, B=9, signed=True).bake(model)           # ... baked from the network's own signed density
 
 The lattice is the one of mesh.density_lattice (include/mi_nerf_mesh.h): the grid's sigma plane is that lattice after a ReLU.  Colour is
 the network's post-sigmoid colour at the lattice point, seen from D fixed directions, projected by least squares onto B real spherical
@@ -107,12 +109,16 @@ class Views:
 
 class RadianceGrid:
     """``sigma`` float [P_z, P_y, P_x], ``coef`` float [P_z, P_y, P_x, R], ``skip`` uint8 [B_z, B_y, B_x] on ``device`` (THE GRID of the
-    header); None until ``allocate`` / ``bake`` / ``load``."""
+    header); None until ``allocate`` / ``bake`` / ``load``.  ``signed=True``: A SIGNED GRID of the header -- ``sigma`` holds the density
+    before its ReLU, of any sign, and ``render``, ``build_skip`` and ``compact`` go through the signed entries; ``resample`` and
+    ``prune(tau)`` keep the flag.  What reads sigma without the ReLU (``seen``, ``prune(seen=)``, ``render_backward_rays``, baked_pose)
+    refuses a signed grid."""
 
-    def __init__(self, lo, hi, res, B: int = 9):
+    def __init__(self, lo, hi, res, B: int = 9, signed: bool = False):
         # the box is fp32, as the library reads it: what save() writes is what load() reads
         self.lo, self.hi, self.res = _triple(lo, lambda v: float(np.float32(v))), _triple(hi, lambda v: float(np.float32(v))), _triple(res, int)
         self.B = _check_basis(B)
+        self.signed = bool(signed)
         self.sigma: Optional[torch.Tensor] = None
         self.coef: Optional[torch.Tensor] = None
         self.skip: Optional[torch.Tensor] = None
@@ -168,6 +174,10 @@ class RadianceGrid:
         if self.sigma is None or self.coef is None or self.skip is None:
             raise MiNerfError("the grid holds nothing yet: bake(), bake_field(), allocate() or load() first")
 
+    def _need_unsigned(self, what: str) -> None:
+        if self.signed:
+            raise MiNerfError(f"{what} is not defined on a signed grid: its rule reads sigma without the ReLU (include/mi_nerf_vox.h, A SIGNED GRID)")
+
     # ---- the library's entries -----------------------------------------------------------------------
     def project(self, raw: torch.Tensor, proj: torch.Tensor, index: torch.Tensor, write_sigma: bool = True) -> "RadianceGrid":
         """mi_vox_project: raw [M, D, 4], proj [B, D], index [M] (int64 flat lattice indices, distinct) -> records (and sigma)."""
@@ -184,13 +194,14 @@ class RadianceGrid:
         return self
 
     def build_skip(self) -> "RadianceGrid":
-        """mi_vox_build_skip: the empty-space plane from sigma."""
+        """mi_vox_build_skip (a signed grid: mi_vox_build_skip_signed): the empty-space plane from sigma."""
         self._need()
         dev = self.sigma.device
         g = self.c_grid()
+        name = "mi_vox_build_skip_signed" if self.signed else "mi_vox_build_skip"
         with ops._guard(dev):
-            _vox.check(_vox.lib().mi_vox_build_skip(C.byref(g), dev_ptr(self.sigma, "sigma"), dev_ptr(self.skip, "skip", torch.uint8, 1), stream_ptr(dev)),
-                       "mi_vox_build_skip")
+            _vox.check(getattr(_vox.lib(), name)(C.byref(g), dev_ptr(self.sigma.detach(), "sigma"), dev_ptr(self.skip, "skip", torch.uint8, 1), stream_ptr(dev)),
+                       name)
         return self
 
     def render(self, rays: torch.Tensor, step: Optional[float] = None, near: float = 0.0, far: float = math.inf, T_min: float = 0.0,
@@ -218,10 +229,11 @@ class RadianceGrid:
 
     def _launch_render(self, rays, n, cfg, rgb, disp, acc, depth, seen, dev) -> None:
         g = self.c_grid()
-        _vox.check(_vox.lib().mi_vox_render(C.byref(g), self.B, dev_ptr(self.sigma, "sigma"), dev_ptr(self.coef, "coef", torch.float32, 16),
-                                            dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
-                                            dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
-                                            dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render")
+        name = "mi_vox_render_signed" if self.signed else "mi_vox_render"
+        _vox.check(getattr(_vox.lib(), name)(C.byref(g), self.B, dev_ptr(self.sigma, "sigma"), dev_ptr(self.coef, "coef", torch.float32, 16),
+                                             dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
+                                             dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
+                                             dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), name)
 
     def render_backward_rays(self, rays: torch.Tensor, g_rgb: torch.Tensor, g_acc: Optional[torch.Tensor] = None,
                              g_depth: Optional[torch.Tensor] = None, step: Optional[float] = None, near: float = 0.0, far: float = math.inf,
@@ -231,6 +243,7 @@ class RadianceGrid:
         and equal with and without the skip plane.  ``check=True`` returns (d_rays, rgb [n,3], acc [n], depth [n]): the forward the entry
         recomputed, ``render``'s own bits.  The other arguments are ``render``'s."""
         self._need()
+        self._need_unsigned("render_backward_rays (THE RAY GRADIENT RULE)")
         dev = self.sigma.device
         if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
             raise MiNerfError(f"rays [n,6] expected, got {tuple(rays.shape) if isinstance(rays, torch.Tensor) else type(rays).__name__}")
@@ -258,12 +271,30 @@ class RadianceGrid:
     def compact(self, storage: str = "fp32") -> "SparseRadianceGrid":
         """The same grid as a SparseRadianceGrid: mi_vox_index, one read-back of the count, mi_vox_pack.  sigma and skip are copies."""
         self._need()
-        out = SparseRadianceGrid(self.lo, self.hi, self.res, self.B, storage)
+        out = SparseRadianceGrid(self.lo, self.hi, self.res, self.B, storage, signed=self.signed)
         out.sigma, out.skip = self.sigma.clone(), self.skip.clone()
         out.index()
         out.table = out.empty_table(out.count)
         out.pack(self.coef, out.table, out.count, slot=out.slot)
         return out
+
+    def to_signed(self) -> "RadianceGrid":
+        """A signed grid (``signed=True``) for a plane that only knows inside and outside: sigma stays where it is > 0 and becomes minus the
+        largest sigma of the 26 neighbours (clipped to the lattice) elsewhere, so that the zero crossing of the interpolation lies half way
+        between a dense point and an empty neighbour and not at the empty one.  Away from density the plane stays 0.  The records are
+        copies, and the skip plane has the same blocks: a point that turns negative has a neighbour with density in every block that holds
+        it.  Torch ops on the dense plane (as ``fill_shell``): not the hot path."""
+        self._need()
+        if self.signed:
+            raise MiNerfError("the grid is signed already")
+        out = RadianceGrid(self.lo, self.hi, self.res, self.B, signed=True)
+        with torch.no_grad():
+            s = self.sigma.detach()
+            best = torch.nn.functional.max_pool3d(s.clamp_min(0.0)[None, None], 3, stride=1, padding=1)[0, 0]      # -inf padding: clipped
+            out.sigma = torch.where(s > 0, s, -best).contiguous()
+            out.coef = self.coef.detach().clone()
+            out.skip = torch.empty_like(self.skip)
+        return out.build_skip()
 
     # ---- coarse to fine ------------------------------------------------------------------------------
     def resample(self, res, lo=None, hi=None) -> "RadianceGrid":
@@ -272,7 +303,7 @@ class RadianceGrid:
         identical field; a smaller box crops, a larger one extends the faces.  This grid is left as it is."""
         self._need()
         dev = self.sigma.device
-        out = RadianceGrid(self.lo if lo is None else lo, self.hi if hi is None else hi, res, self.B)
+        out = RadianceGrid(self.lo if lo is None else lo, self.hi if hi is None else hi, res, self.B, signed=self.signed)
         out.sigma = torch.empty(out.points, dtype=torch.float32, device=dev)
         out.coef = torch.empty(*out.points, out.record_floats, dtype=torch.float32, device=dev)
         out.skip = torch.empty(out.skip_shape, dtype=torch.uint8, device=dev)
@@ -291,6 +322,7 @@ class RadianceGrid:
         self._need()
         dev = self.sigma.device
         if seen is not None:
+            self._need_unsigned("prune(seen=) (THE SEEN PRUNING RULE)")
             if not isinstance(seen, torch.Tensor) or tuple(seen.shape) != self.points or seen.device != dev:
                 raise MiNerfError(f"seen must be the grid's od plane {self.points} on {dev}: what seen(views) returns")
             if not (isinstance(T_vis, (int, float)) and 0.0 <= T_vis <= 1.0):
@@ -334,6 +366,7 @@ class RadianceGrid:
         step), ``bias`` the shadow-map bias in slices, ``skip`` uses the grid's skip plane (the result is the same bit for bit),
         ``out`` a plane to reuse."""
         self._need()
+        self._need_unsigned("seen (THE SHADOW RULE)")
         dev = self.sigma.device
         if not isinstance(views, Views):
             raise MiNerfError(f"views: a baked.Views expected, got {type(views).__name__}")
@@ -365,28 +398,32 @@ class RadianceGrid:
 
     # ---- baking --------------------------------------------------------------------------------------
     def bake(self, model_or_packed, network: str = "fine", D: int = 32, sigma_min: float = 0.0, precision=None,
-             slab_points: int = SLAB_POINTS, shell: str = "field") -> "RadianceGrid":
+             slab_points: int = SLAB_POINTS, shell: str = "field", signed: Optional[bool] = None, clip: Optional[float] = None) -> "RadianceGrid":
         """Bake one network: sigma from mesh.density_lattice (values <= sigma_min become 0), colour from one-sample rays through
-        ops.mlp_rays (fp32) at every point within one lattice step of density.  See ``bake_field``."""
+        ops.mlp_rays (fp32) at every point within one lattice step of density.  ``signed=True`` (default: the grid's own flag) makes this a
+        signed grid whose plane is the density lattice without the ReLU, clamped to [-clip, clip] when ``clip`` is given.  See
+        ``bake_field``."""
+        self.signed = self.signed if signed is None else bool(signed)
         from . import mesh
         from .weights import packed_for
         packed = packed_for(model_or_packed)                                # packed once for the lattice and the colour rays
         dev, net, blob = mesh._blob(packed, network, mesh.check_precision(None))
         density = mesh.density_lattice(packed, self.lo, self.hi, self.res, network=network, precision=precision)
         return bake_field(lambda rays, z: ops.mlp_rays(net, blob, rays, z), self.lo, self.hi, self.res, B=self.B, D=D, sigma_min=sigma_min,
-                          slab_points=slab_points, device=dev, density=density, grid=self, shell=shell)
+                          slab_points=slab_points, device=dev, density=density, grid=self, shell=shell, signed=self.signed, clip=clip)
 
     # ---- persistence ---------------------------------------------------------------------------------
     def save(self, path: str) -> None:
-        """npz: lo, hi, res, B and the three arrays."""
+        """npz: lo, hi, res, B and the three arrays; a signed grid adds the field ``signed`` (a file without it holds an unsigned grid)."""
         self._need()
+        flag = dict(signed=np.asarray(1, np.int32)) if self.signed else {}
         np.savez_compressed(path, lo=np.asarray(self.lo, np.float32), hi=np.asarray(self.hi, np.float32), res=np.asarray(self.res, np.int32),
-                            B=np.asarray(self.B, np.int32), sigma=self.sigma.cpu().numpy(), coef=self.coef.cpu().numpy(), skip=self.skip.cpu().numpy())
+                            B=np.asarray(self.B, np.int32), **flag, sigma=self.sigma.detach().cpu().numpy(), coef=self.coef.cpu().numpy(), skip=self.skip.cpu().numpy())
 
     @classmethod
     def load(cls, path: str, device=None) -> "RadianceGrid":
         with np.load(path, allow_pickle=False) as f:
-            grid = cls(f["lo"].tolist(), f["hi"].tolist(), f["res"].tolist(), int(f["B"]))
+            grid = cls(f["lo"].tolist(), f["hi"].tolist(), f["res"].tolist(), int(f["B"]), signed=bool(int(f["signed"])) if "signed" in f.files else False)
             sigma, coef, skip = (torch.from_numpy(np.ascontiguousarray(f[k])) for k in ("sigma", "coef", "skip"))
         if tuple(sigma.shape) != grid.points or tuple(coef.shape) != grid.points + (grid.record_floats,) or tuple(skip.shape) != grid.skip_shape:
             raise MiNerfError(f"{path}: the arrays do not fit the grid ({tuple(sigma.shape)}, {tuple(coef.shape)}, {tuple(skip.shape)})")
@@ -402,10 +439,10 @@ class SparseRadianceGrid(RadianceGrid):
     active point, -1 elsewhere), ``table`` [count, R] float32 (``storage="fp32"``) or float16 (``"f16"``), ``count`` the number of active
     points.  ``coef`` stays None: there is no dense record array.  Renders bit for bit what the dense grid with the same records renders."""
 
-    def __init__(self, lo, hi, res, B: int = 9, storage: str = "fp32"):
+    def __init__(self, lo, hi, res, B: int = 9, storage: str = "fp32", signed: bool = False):
         if storage not in STORAGES:
             raise MiNerfError(f"storage={storage!r}: 'fp32' or 'f16'")
-        super().__init__(lo, hi, res, B)
+        super().__init__(lo, hi, res, B, signed=signed)
         self.storage = storage
         self.slot: Optional[torch.Tensor] = None
         self.table: Optional[torch.Tensor] = None
@@ -455,6 +492,9 @@ class SparseRadianceGrid(RadianceGrid):
     def prune(self, *args, **kwargs):
         raise MiNerfError("a SparseRadianceGrid has no dense record array to prune: refine the dense grid, then compact()")
 
+    def to_signed(self):
+        raise MiNerfError("a SparseRadianceGrid is made signed on the dense grid: to_signed(), then compact()")
+
     # ---- the library's entries -----------------------------------------------------------------------
     def index(self) -> "SparseRadianceGrid":
         """mi_vox_index: ``slot`` and ``count`` from ``sigma`` (the count is read back once)."""
@@ -484,11 +524,12 @@ class SparseRadianceGrid(RadianceGrid):
 
     def _launch_render(self, rays, n, cfg, rgb, disp, acc, depth, seen, dev) -> None:
         g = self.c_grid()
-        _vox.check(_vox.lib().mi_vox_render_sparse(C.byref(g), self.B, self.fmt, dev_ptr(self.sigma, "sigma"), dev_ptr(self.slot, "slot", torch.int32),
-                                                   dev_ptr(self.table, "table", STORAGES[self.storage][1], 16) if self.count else None, self.count,
-                                                   dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
-                                                   dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
-                                                   dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), "mi_vox_render_sparse")
+        name = "mi_vox_render_sparse_signed" if self.signed else "mi_vox_render_sparse"
+        _vox.check(getattr(_vox.lib(), name)(C.byref(g), self.B, self.fmt, dev_ptr(self.sigma, "sigma"), dev_ptr(self.slot, "slot", torch.int32),
+                                             dev_ptr(self.table, "table", STORAGES[self.storage][1], 16) if self.count else None, self.count,
+                                             dev_ptr(self.skip, "skip", torch.uint8, 1), dev_ptr(rays, "rays"), n, C.byref(cfg), dev_ptr(rgb, "rgb"),
+                                             dev_ptr(disp, "disp"), dev_ptr(acc, "acc"), dev_ptr(depth, "depth"),
+                                             dev_ptr(seen, "visited", torch.int32), stream_ptr(dev)), name)
 
     def _launch_ray_grad(self, rays, n, cfg, tail) -> None:
         g = self.c_grid()
@@ -504,7 +545,7 @@ class SparseRadianceGrid(RadianceGrid):
     def to_dense(self) -> RadianceGrid:
         """A RadianceGrid with the same records (binary16 widened exactly); inactive points hold zero records.  Torch ops: works on any device."""
         self._need()
-        out = RadianceGrid(self.lo, self.hi, self.res, self.B)
+        out = RadianceGrid(self.lo, self.hi, self.res, self.B, signed=self.signed)
         out.sigma, out.skip = self.sigma.clone(), self.skip.clone()
         out.coef = torch.zeros(*self.points, self.record_floats, dtype=torch.float32, device=self.sigma.device)
         where = (self.slot >= 0) & (self.slot < self.count)
@@ -513,8 +554,9 @@ class SparseRadianceGrid(RadianceGrid):
 
     # ---- baking --------------------------------------------------------------------------------------
     def bake(self, model_or_packed, network: str = "fine", D: int = 32, sigma_min: float = 0.0, precision=None,
-             slab_points: int = SLAB_POINTS, shell: str = "field") -> "SparseRadianceGrid":
+             slab_points: int = SLAB_POINTS, shell: str = "field", signed: Optional[bool] = None, clip: Optional[float] = None) -> "SparseRadianceGrid":
         """RadianceGrid.bake without a dense record array: see ``bake_field(..., storage=...)``."""
+        self.signed = self.signed if signed is None else bool(signed)
         from . import mesh
         from .weights import packed_for
         packed = packed_for(model_or_packed)
@@ -522,20 +564,22 @@ class SparseRadianceGrid(RadianceGrid):
         density = mesh.density_lattice(packed, self.lo, self.hi, self.res, network=network, precision=precision)
         return bake_field(lambda rays, z: ops.mlp_rays(net, blob, rays, z), self.lo, self.hi, self.res, B=self.B, D=D, sigma_min=sigma_min,
                           slab_points=slab_points, device=dev, density=density, grid=self, shell=shell,
-                          storage="sparse16" if self.storage == "f16" else "sparse")
+                          storage="sparse16" if self.storage == "f16" else "sparse", signed=self.signed, clip=clip)
 
     # ---- persistence ---------------------------------------------------------------------------------
     def save(self, path: str) -> None:
-        """npz: lo, hi, res, B, storage and the four arrays."""
+        """npz: lo, hi, res, B, storage and the four arrays; a signed grid adds the field ``signed``."""
         self._need()
+        flag = dict(signed=np.asarray(1, np.int32)) if self.signed else {}
         np.savez_compressed(path, lo=np.asarray(self.lo, np.float32), hi=np.asarray(self.hi, np.float32), res=np.asarray(self.res, np.int32),
-                            B=np.asarray(self.B, np.int32), storage=np.asarray(self.storage), sigma=self.sigma.cpu().numpy(), slot=self.slot.cpu().numpy(),
+                            B=np.asarray(self.B, np.int32), storage=np.asarray(self.storage), **flag, sigma=self.sigma.cpu().numpy(), slot=self.slot.cpu().numpy(),
                             table=self.table.cpu().numpy(), skip=self.skip.cpu().numpy())
 
     @classmethod
     def load(cls, path: str, device=None) -> "SparseRadianceGrid":
         with np.load(path, allow_pickle=False) as f:
-            grid = cls(f["lo"].tolist(), f["hi"].tolist(), f["res"].tolist(), int(f["B"]), str(f["storage"]))
+            grid = cls(f["lo"].tolist(), f["hi"].tolist(), f["res"].tolist(), int(f["B"]), str(f["storage"]),
+                       signed=bool(int(f["signed"])) if "signed" in f.files else False)
             sigma, slot, table, skip = (torch.from_numpy(np.ascontiguousarray(f[k])) for k in ("sigma", "slot", "table", "skip"))
         if (tuple(sigma.shape) != grid.points or tuple(slot.shape) != grid.points or table.dim() != 2 or table.shape[1] != grid.record_floats
                 or tuple(skip.shape) != grid.skip_shape or table.dtype != STORAGES[grid.storage][1]):
@@ -550,7 +594,7 @@ def fill_shell(grid: RadianceGrid) -> RadianceGrid:
     grid._need()
     dense = (grid.sigma > 0).to(torch.float32)[None, None]
     count = torch.nn.functional.avg_pool3d(dense, 3, stride=1, padding=1)[0, 0]              # (dense neighbours) / 27, zero padding
-    shell = (grid.sigma == 0) & (count > 0)
+    shell = ~(grid.sigma > 0) & (count > 0)                                                 # sigma == 0; on a signed grid sigma <= 0
     for c in range(3 * grid.B):                                                             # plane by plane: no second copy of the table
         plane = grid.coef[..., c]
         mean = torch.nn.functional.avg_pool3d((plane * dense[0, 0])[None, None], 3, stride=1, padding=1)[0, 0] / count.clamp_min(1e-9)
@@ -574,7 +618,8 @@ def lattice_positions(lo, hi, res, index: torch.Tensor) -> torch.Tensor:
 
 def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi, res, B: int = 9, D: int = 32, sigma_min: float = 0.0,
                slab_points: int = SLAB_POINTS, device="cuda:0", density: Optional[torch.Tensor] = None,
-               grid: Optional[RadianceGrid] = None, shell: str = "field", storage: str = "dense") -> RadianceGrid:
+               grid: Optional[RadianceGrid] = None, shell: str = "field", storage: str = "dense", signed: Optional[bool] = None,
+               clip: Optional[float] = None) -> RadianceGrid:
     """Bake any field ``fn(rays [n,6], z [n,S]) -> raw [n,S,4]`` (a network's fused entry, ``SolidScene.field``) into a RadianceGrid.
       1. sigma: ``density`` [P_z, P_y, P_x] (raw, before the ReLU) when given, else fn over the lattice rows of mesh.lattice_rows; values
          <= sigma_min (and NaN) become 0.
@@ -591,7 +636,12 @@ def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi,
     allocate a dense record array: after sigma, mi_vox_index numbers the active points, the table of that many records is allocated, and
     step 3 projects slab by slab into the table with record numbers as mi_vox_project's index list (for binary16 into a slab-sized fp32
     buffer that mi_vox_pack converts into the table).  The result equals the dense bake's ``compact()`` bit for bit.  shell="neighbours"
-    works on the dense table only."""
+    works on the dense table only.
+    ``signed=True`` (default: the flag of ``grid``, False without one) gives A SIGNED GRID of the header: the plane is the density lattice
+    WITHOUT the ReLU -- a NaN becomes 0, a value <= sigma_min that is > 0 becomes 0 as before, a negative value stays -- clamped to
+    [-clip, clip] when ``clip`` (> 0) is given: a network's density before its ReLU can be far more negative than it is ever positive, and
+    the size of the negative side sets how far the optimiser must walk to open a point.  Records are stored where the unsigned bake's
+    active stencil puts them (it tests sigma > 0)."""
     from . import mesh
     if storage not in ("dense", "sparse", "sparse16"):
         raise MiNerfError(f"storage={storage!r}: 'dense', 'sparse' or 'sparse16'")
@@ -599,7 +649,12 @@ def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi,
     if sparse and shell == "neighbours":
         raise MiNerfError("shell='neighbours' fills the shell on the dense table: bake dense, then compact()")
     if grid is None:
-        grid = SparseRadianceGrid(lo, hi, res, B, "f16" if storage == "sparse16" else "fp32") if sparse else RadianceGrid(lo, hi, res, B)
+        grid = (SparseRadianceGrid(lo, hi, res, B, "f16" if storage == "sparse16" else "fp32", signed=bool(signed)) if sparse else
+                RadianceGrid(lo, hi, res, B, signed=bool(signed)))
+    elif signed is not None:
+        grid.signed = bool(signed)
+    if clip is not None and not (grid.signed and isinstance(clip, (int, float)) and math.isfinite(clip) and clip > 0):
+        raise MiNerfError(f"clip={clip!r}: a finite number > 0, for a signed bake only")
     if isinstance(grid, SparseRadianceGrid) != sparse or (sparse and grid.storage != ("f16" if storage == "sparse16" else "fp32")):
         raise MiNerfError(f"storage={storage!r} does not fit the grid handed in ({type(grid).__name__})")
     dev = torch.device(device)
@@ -618,7 +673,11 @@ def bake_field(fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], lo, hi,
         density = as_f32_dev(density, dev)
         if tuple(density.shape) != grid.points:
             raise MiNerfError(f"density must be {grid.points}, got {tuple(density.shape)}")
-        sigma = torch.where(density > float(sigma_min), density, torch.zeros_like(density)).clamp_(min=0.0, max=torch.finfo(torch.float32).max)
+        big = torch.finfo(torch.float32).max
+        sigma = torch.where(density > float(sigma_min), density, torch.zeros_like(density)).clamp_(min=0.0, max=big)
+        if grid.signed:                                                          # the negative side as the field gives it; a NaN fails both tests
+            bound = big if clip is None else float(clip)
+            sigma = torch.where(density < 0, density, sigma).clamp_(min=-bound, max=bound)
         if sparse:
             return _bake_sparse(fn, grid, sigma.contiguous(), proj, omega, D, slab_points)
         grid.allocate(dev)

@@ -26,6 +26,7 @@ def _check(grid, rays) -> torch.device:
     if not isinstance(grid, RadianceGrid):
         raise MiNerfError(f"a baked.RadianceGrid or baked.SparseRadianceGrid expected, got {type(grid).__name__}")
     grid._need()
+    grid._need_unsigned("baked_pose (THE RAY GRADIENT RULE)")
     dev = grid.sigma.device
     if dev.type != "cuda":
         raise MiNerfError(f"the grid must live on a HIP device (got {dev}); this path has no CPU fallback")
@@ -94,6 +95,7 @@ def locate(grid: RadianceGrid, H: int, W: int, K, pose0, target: torch.Tensor, s
     if not isinstance(grid, RadianceGrid):
         raise MiNerfError(f"a baked.RadianceGrid or baked.SparseRadianceGrid expected, got {type(grid).__name__}")
     grid._need()
+    grid._need_unsigned("baked_pose (THE RAY GRADIENT RULE)")
     dev = grid.sigma.device
     if dev.type != "cuda":
         raise MiNerfError(f"the grid must live on a HIP device (got {dev}); this path has no CPU fallback")

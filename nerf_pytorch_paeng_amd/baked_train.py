@@ -192,7 +192,7 @@ def _regularise(grid: RadianceGrid, masked: bool, n_points: int, tv_sigma: float
 def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps: int, batch: int = 4096, lr_sigma: float = 0.05, lr_coef: float = 0.005,
              optimizer=torch.optim.Adam, rebuild_skip_every: int = 1, seed: int = 0, step: Optional[float] = None, near: float = 0.0,
              far: float = math.inf, T_min: float = 0.0, bg=(1.0, 1.0, 1.0), skip: bool = True, tv_sigma: float = 0.0, tv_coef: float = 0.0,
-             sparsity: float = 0.0, tv_eps: float = 1e-8) -> torch.Tensor:
+             sparsity: float = 0.0, tv_eps: float = 1e-8, sigma_floor: Optional[float] = None) -> torch.Tensor:
     """``steps`` optimiser steps on ``grid.sigma`` (lr_sigma) and ``grid.coef`` (lr_coef) against target [N,3], the rgb of rays [N,6]: a
     seeded batch of ``batch`` rays drawn on the device per step, the mean squared error on rgb, and ``sigma.clamp_(min=0)`` after every
     step.  Returns the per-step losses [steps] as a device tensor: nothing synchronises with the host.
@@ -217,10 +217,21 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
     once; a step renders under ``no_grad``, forms ``g_rgb = 2 (rgb - target) / (3 n)`` itself, has ``backward`` and the regularisers add
     straight into those buffers, and ends in ``LazyAdam.step`` with ``clamp_min=0`` on sigma and ``consume=True``, which updates the touched
     elements and leaves the buffers zero.  No ``zero_grad``, no ``clamp_``, no autograd node, no ``zeros_like``: nothing sweeps the grid
-    but the optimiser's read of the gradients.  An element no ray reaches stays what it is, moments included."""
+    but the optimiser's read of the gradients.  An element no ray reaches stays what it is, moments included.
+
+    A SIGNED GRID (``grid.signed``; include/mi_nerf_vox.h) is trained by the same steps with the ReLU after the interpolation in the
+    forward and in the backward (the Signed paragraph of THE BACKWARD RULE), and WITHOUT the clamp at 0: sigma keeps its sign, the
+    autograd path runs no ``clamp_`` and LazyAdam's ``clamp_min`` is None -- or ``sigma_floor`` (<= 0, signed grids only), an optional
+    lower bound on sigma that keeps a point the optimiser pushes away from being pushed out of reach.  The skip plane is rebuilt by the
+    signed builder.  There is no gain factor between the stored plane and the density: Adam's step is in parameter units, so a plane of
+    amplitude c trained with ``lr_sigma = c r`` follows the same trajectory as one of amplitude 1 with ``lr_sigma = r`` -- choose
+    ``lr_sigma`` in units of the plane's amplitude."""
     if not all(isinstance(w, (int, float)) and math.isfinite(w) and w >= 0 for w in (tv_sigma, tv_coef, sparsity)):
         raise MiNerfError(f"tv_sigma={tv_sigma}, tv_coef={tv_coef} and sparsity={sparsity} must be finite numbers >= 0")
     dev = _check(grid, rays)
+    if sigma_floor is not None and not (grid.signed and isinstance(sigma_floor, (int, float)) and math.isfinite(sigma_floor) and sigma_floor <= 0):
+        raise MiNerfError(f"sigma_floor={sigma_floor!r}: a finite number <= 0, for a signed grid only")
+    floor = (None if sigma_floor is None else float(sigma_floor)) if grid.signed else 0.0      # the lower bound on sigma after a step
     N = rays.shape[0]
     if not isinstance(target, torch.Tensor) or tuple(target.shape) != (N, 3) or target.device != dev:
         raise MiNerfError(f"target [{N},3] on {dev} expected")
@@ -237,7 +248,7 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
     losses = []
     try:
         if lazy:                                                             # the direct path: no dense sweep of the grid per step
-            opt.param_groups[0]["clamp_min"] = 0.0                           # sigma >= 0, applied where the step lands
+            opt.param_groups[0]["clamp_min"] = floor                         # sigma >= 0 (a signed grid: no bound, or sigma_floor), applied where the step lands
             opt.consume = True                                               # the step leaves the gradients zero: no zero_grad
             grid.sigma.grad, grid.coef.grad = torch.zeros_like(grid.sigma), torch.zeros_like(grid.coef)
             kw = dict(step=step, near=near, far=far, T_min=T_min, bg=tuple(float(v) for v in bg))
@@ -264,8 +275,9 @@ def finetune(grid: RadianceGrid, rays: torch.Tensor, target: torch.Tensor, steps
             loss.backward()
             _regularise(grid, skip and fresh, n_points, tv_sigma, tv_coef, sparsity, tv_eps)
             opt.step()
-            with torch.no_grad():
-                grid.sigma.clamp_(min=0.0)
+            if floor is not None:
+                with torch.no_grad():
+                    grid.sigma.clamp_(min=floor)
             losses.append(loss.detach())
     finally:
         grid.sigma.requires_grad_(was[0])

@@ -51,6 +51,9 @@
 //                          dt, t1, L and lane e's share of dL/dY_b stay in registers.  At the ray's end the shares are group-summed, the
 //                          basis, dt, L and the slab's entry and exit are differentiated, and lane 0 stores six floats.  A struct of its own
 //                          (RayGradArgs), so that RenderArgs and the renderer's code stay what they were.
+//   skip_signed_kernel,    A SIGNED GRID: skip_kernel with the test sigma > 0, and render_kernel's march with sigma_s = fmaxf(the group's sum, 0) --
+//   render_signed_kernel<B, ST>  one v_max_f32 per sample more, the same nine instantiations.  Kernels of their own, spelled out again,
+//                          so that skip_kernel and render_kernel keep their names and their code (docs/design/29_signed_density.md).
 //
 // No atomic, no host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
 #include <hip/hip_runtime.h>
@@ -127,6 +130,28 @@ __global__ __launch_bounds__(64) void skip_kernel(const Lattice g, const float* 
     for (int t = threadIdx.x; t < total; t += 64) {
         const int x = p0[0] + t % np[0], y = p0[1] + (t / np[0]) % np[1], z = p0[2] + t / (np[0] * np[1]);
         any |= sigma[((long long)z * g.P[1] + y) * g.P[0] + x] != 0.0f;
+    }
+    const bool found = __ballot(any) != 0ull;
+    if (threadIdx.x == 0) skip[blk] = found ? 1 : 0;
+}
+
+// skip_kernel with the signed plane's test: the byte is 0 iff sigma <= 0 at every point of the block extended by one cell
+__global__ __launch_bounds__(64) void skip_signed_kernel(const Lattice g, const float* __restrict__ sigma, uint8_t* __restrict__ skip) {
+    const int blk = blockIdx.x;
+    const int bx = blk % g.nb[0], by = (blk / g.nb[0]) % g.nb[1], bz = blk / (g.nb[0] * g.nb[1]);
+    const int b[3] = {bx, by, bz};
+    int p0[3], np[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int c1 = min(BLK * b[i] + BLK, g.res[i]);
+        p0[i] = max(BLK * b[i] - 1, 0);
+        np[i] = min(c1 + 1, g.res[i]) - p0[i] + 1;
+    }
+    const int total = np[0] * np[1] * np[2];
+    bool any = false;
+    for (int t = threadIdx.x; t < total; t += 64) {
+        const int x = p0[0] + t % np[0], y = p0[1] + (t / np[0]) % np[1], z = p0[2] + t / (np[0] * np[1]);
+        any |= sigma[((long long)z * g.P[1] + y) * g.P[0] + x] > 0.0f;
     }
     const bool found = __ballot(any) != 0ull;
     if (threadIdx.x == 0) skip[blk] = found ? 1 : 0;
@@ -636,6 +661,139 @@ __global__ __launch_bounds__(THREADS) void render_kernel(const RenderArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// mi_vox_render_signed, mi_vox_render_sparse_signed: A SIGNED GRID of the header (its skip builder stands beside skip_kernel)
+// ------------------------------------------------------------------------------------------------
+// render_kernel's march spelled again with step 3's sigma_s = fmaxf(interpolation, 0).  A kernel of its own and not a template flag on
+// render_kernel: that kernel's names and code stay what they were (vox_rule.h on why the march is not shared through a function).
+// On a plane that is >= 0 the fmaxf returns its argument, so every output equals render_kernel's bit for bit.  A sample in a block whose
+// signed byte is 0 has eight corners <= 0 and weights >= 0: the interpolation is <= 0, sigma_s = 0, and it adds exactly nothing.
+template <int B, int ST>
+__global__ __launch_bounds__(THREADS) void render_signed_kernel(const RenderArgs a) {
+    const int e = threadIdx.x & (GROUP - 1);               // this lane's corner
+    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 3);
+    if (ray >= a.n) return;                                // a whole group leaves together
+    const Lattice& g = a.g;
+    const float* rp = a.rays + ray * 6;
+    const float o[3] = {rp[0], rp[1], rp[2]}, d[3] = {rp[3], rp[4], rp[5]};
+    const float L = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    bool miss = !(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(L)) || L == 0.0f;
+    float entry = -INFINITY, exit_ = INFINITY;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (d[i] != 0.0f) {
+            const float ta = (g.lo[i] - o[i]) / d[i], tb = (g.hi[i] - o[i]) / d[i];
+            entry = fmaxf(entry, fminf(ta, tb));
+            exit_ = fminf(exit_, fmaxf(ta, tb));
+        } else if (!(g.lo[i] <= o[i] && o[i] <= g.hi[i])) {
+            miss = true;
+        }
+    }
+    const float t0 = fmaxf(a.t_near, entry), t1 = fminf(a.t_far, exit_);
+    if (!(t1 > t0)) miss = true;
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, sd = 0.0f;
+    unsigned seen = 0;
+    if (!miss) {
+        const float dt = a.step / L;
+        const float ux = d[0] / L, uy = d[1] / L, uz = d[2] / L;
+        float Y[B];
+        sh_basis<B>(ux, uy, uz, Y);
+        // jumping over an empty block: allowed only where the fp32 position error stays below an eighth of a cell
+        const float tmax = fmaxf(fabsf(t0), fabsf(t1));
+        float gu[3], gv[3];
+        bool can_jump = a.use_skip != 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            gu[i] = (o[i] - g.lo[i]) * g.inv[i];
+            gv[i] = d[i] * g.inv[i];
+            const float err = 16.0f * EPS32 * (fabsf(o[i]) + tmax * fabsf(d[i]) + fabsf(g.lo[i]) + fabsf(g.hi[i])) * g.inv[i];
+            can_jump = can_jump && err <= 0.125f;
+        }
+        const int ex = e & 1, ey = (e >> 1) & 1, ez = e >> 2;
+        float T = 1.0f;
+        int k = 0;
+        while (k < a.max_steps) {
+            const float ak = t0 + (float)k * dt;
+            if (!(ak < t1)) break;
+            const float bk = fminf(t0 + (float)(k + 1) * dt, t1);
+            const float mk = 0.5f * (ak + bk);
+            int c[3];
+            float f[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float p = o[i] + mk * d[i];
+                cell_of((p - g.lo[i]) * g.inv[i], g.res[i], c[i], f[i]);
+            }
+            if (a.use_skip) {
+                const int bx = c[0] >> 3, by = c[1] >> 3, bz = c[2] >> 3;
+                if (a.skip[(bz * g.nb[1] + by) * g.nb[0] + bx] == 0) {
+                    int next = k + 1;
+                    if (can_jump) {
+                        // where the ray leaves the block extended by half a cell, in lattice units; the first sample that is evaluated
+                        // again starts a whole interval before that
+                        const int bb[3] = {bx, by, bz};
+                        float t_exit = INFINITY;
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            const float far_ = (float)min(BLK * bb[i] + BLK, g.res[i]) + 0.5f, near_ = (float)(BLK * bb[i]) - 0.5f;
+                            if (gv[i] > 0.0f) t_exit = fminf(t_exit, (far_ - gu[i]) / gv[i]);
+                            else if (gv[i] < 0.0f) t_exit = fminf(t_exit, (near_ - gu[i]) / gv[i]);
+                        }
+                        const float kf = floorf((t_exit - t0) / dt) - 1.0f;
+                        if (kf > (float)next) next = (int)fminf(kf, (float)a.max_steps);
+                    }
+                    k = next;
+                    continue;
+                }
+            }
+            // lane e: corner e
+            const long long at = ((long long)(c[2] + ez) * g.P[1] + (c[1] + ey)) * g.P[0] + (c[0] + ex);
+            const float wx = ex ? f[0] : 1.0f - f[0], wy = ey ? f[1] : 1.0f - f[1], wz = ez ? f[2] : 1.0f - f[2];
+            const float w = (wx * wy) * wz;
+            const float sigma_s = fmaxf(group_sum(w * a.sigma[at]), 0.0f);   // the ReLU AFTER the interpolation: the one change
+            ++seen;
+            const float delta = (bk - ak) * L;
+            const float alpha = 1.0f - expf(-(sigma_s * delta));
+            const float wt = T * alpha;
+            if (sigma_s > 0.0f) {
+                float kc[record_regs<B, ST>()];
+                fetch_record<B, ST>(a.coef, a.slot, a.M, at, kc);
+                float col[3];
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    float q = kc[ch] * Y[0];
+#pragma unroll
+                    for (int b = 1; b < B; ++b) q += kc[3 * b + ch] * Y[b];
+                    col[ch] = fminf(fmaxf(group_sum(w * q), 0.0f), 1.0f);
+                }
+                sr += wt * col[0]; sg += wt * col[1]; sb += wt * col[2];
+            }
+            sw += wt;
+            sd += wt * mk;
+            T = T * (1.0f - alpha);
+            ++k;
+            if (T < a.T_min) break;
+        }
+    }
+    if (e == 0) {
+        const float rest = 1.0f - sw;
+        a.rgb[ray * 3 + 0] = sr + rest * a.bg[0];
+        a.rgb[ray * 3 + 1] = sg + rest * a.bg[1];
+        a.rgb[ray * 3 + 2] = sb + rest * a.bg[2];
+        if (a.disp) {
+            const float q = sd / sw;
+            const float m = (q != q) ? q : fmaxf(1e-10f, q);
+            float disp = 1.0f / m;
+            if (disp != disp) disp = 0.0f;
+            if (disp > 5.0f) disp = 5.0f;
+            a.disp[ray] = disp;
+        }
+        if (a.acc) a.acc[ray] = sw;
+        if (a.depth) a.depth[ray] = sd;
+        if (a.visited) a.visited[ray] = seen;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // mi_vox_render_backward_rays, mi_vox_render_sparse_backward_rays
 // ------------------------------------------------------------------------------------------------
 struct RayGradArgs {
@@ -990,8 +1148,16 @@ static void launch_render(int B, dim3 blocks, hipStream_t st, const RenderArgs& 
     else hipLaunchKernelGGL((render_kernel<9, ST>), blocks, dim3(THREADS), 0, st, a);
 }
 
-// mi_vox_render (slot_dev NULL, fmt and M unused) and mi_vox_render_sparse: one set of checks, one kernel body
-static int render(const char* who, bool sparse, const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const void* coef_dev,
+template <int ST>
+static void launch_render_signed(int B, dim3 blocks, hipStream_t st, const RenderArgs& a) {
+    if (B == 1) hipLaunchKernelGGL((render_signed_kernel<1, ST>), blocks, dim3(THREADS), 0, st, a);
+    else if (B == 4) hipLaunchKernelGGL((render_signed_kernel<4, ST>), blocks, dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL((render_signed_kernel<9, ST>), blocks, dim3(THREADS), 0, st, a);
+}
+
+// mi_vox_render (slot_dev NULL, fmt and M unused) and mi_vox_render_sparse: one set of checks, one kernel body; is_signed: the two entries
+// of A SIGNED GRID, the same checks and the signed kernel
+static int render(const char* who, bool sparse, bool is_signed, const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const void* coef_dev,
                   const int32_t* slot_dev, int64_t M, const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg,
                   float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream) {
     RenderArgs a{};
@@ -1022,6 +1188,13 @@ static int render(const char* who, bool sparse, const mi_vox_grid* grid, int B, 
     a.rgb = rgb_dev; a.disp = disp_dev; a.acc = acc_dev; a.depth = depth_dev; a.visited = visited_dev;
     const dim3 blocks((unsigned)((n + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK));
     hipStream_t st = (hipStream_t)stream;
+    if (is_signed) {
+        if (!sparse) launch_render_signed<DENSE>(B, blocks, st, a);
+        else if (fmt == MI_VOX_FMT_F32) launch_render_signed<SPARSE32>(B, blocks, st, a);
+        else launch_render_signed<SPARSE16>(B, blocks, st, a);
+        VOX_LAUNCH_CHECK("render_signed_kernel");
+        return MI_VOX_OK;
+    }
     if (!sparse) launch_render<DENSE>(B, blocks, st, a);
     else if (fmt == MI_VOX_FMT_F32) launch_render<SPARSE32>(B, blocks, st, a);
     else launch_render<SPARSE16>(B, blocks, st, a);
@@ -1143,14 +1316,14 @@ int mi_vox_build_skip(const mi_vox_grid* grid, const float* sigma_dev, uint8_t* 
 int mi_vox_render(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev, const float* rays_dev,
                   int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev,
                   uint32_t* visited_dev, void* stream) {
-    return render("mi_vox_render", false, grid, B, MI_VOX_FMT_F32, sigma_dev, coef_dev, nullptr, 0, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev, acc_dev,
+    return render("mi_vox_render", false, false, grid, B, MI_VOX_FMT_F32, sigma_dev, coef_dev, nullptr, 0, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev, acc_dev,
                   depth_dev, visited_dev, stream);
 }
 
 int mi_vox_render_sparse(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev, int64_t M,
                          const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev,
                          float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream) {
-    return render("mi_vox_render_sparse", true, grid, B, fmt, sigma_dev, table_dev, slot_dev, M, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev, acc_dev,
+    return render("mi_vox_render_sparse", true, false, grid, B, fmt, sigma_dev, table_dev, slot_dev, M, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev, acc_dev,
                   depth_dev, visited_dev, stream);
 }
 
@@ -1339,6 +1512,31 @@ int mi_vox_render_sparse_backward_rays(const mi_vox_grid* grid, int B, int fmt, 
                                        float* acc_check_dev, float* depth_check_dev, void* stream) {
     return ray_grad("mi_vox_render_sparse_backward_rays", true, grid, B, fmt, sigma_dev, table_dev, slot_dev, M, skip_dev, rays_dev, n, cfg, g_rgb_dev,
                     g_acc_dev, g_depth_dev, d_rays_dev, rgb_check_dev, acc_check_dev, depth_check_dev, stream);
+}
+
+int mi_vox_build_skip_signed(const mi_vox_grid* grid, const float* sigma_dev, uint8_t* skip_dev, void* stream) {
+    const char* who = "mi_vox_build_skip_signed";
+    Lattice g;
+    if (int rc = check_grid(who, grid, &g)) return rc;
+    VOX_CHECK_ARG(sigma_dev && skip_dev, "%s: NULL pointer", who);
+    VOX_CHECK_ARG(aligned(sigma_dev, 4), "%s: sigma must be 4-byte aligned", who);
+    hipLaunchKernelGGL(skip_signed_kernel, dim3((unsigned)(g.nb[0] * g.nb[1] * g.nb[2])), dim3(64), 0, (hipStream_t)stream, g, sigma_dev, skip_dev);
+    VOX_LAUNCH_CHECK("skip_signed_kernel");
+    return MI_VOX_OK;
+}
+
+int mi_vox_render_signed(const mi_vox_grid* grid, int B, const float* sigma_dev, const float* coef_dev, const uint8_t* skip_dev, const float* rays_dev,
+                         int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev, float* disp_dev, float* acc_dev, float* depth_dev,
+                         uint32_t* visited_dev, void* stream) {
+    return render("mi_vox_render_signed", false, true, grid, B, MI_VOX_FMT_F32, sigma_dev, coef_dev, nullptr, 0, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev,
+                  acc_dev, depth_dev, visited_dev, stream);
+}
+
+int mi_vox_render_sparse_signed(const mi_vox_grid* grid, int B, int fmt, const float* sigma_dev, const int32_t* slot_dev, const void* table_dev, int64_t M,
+                                const uint8_t* skip_dev, const float* rays_dev, int64_t n, const mi_vox_render_cfg* cfg, float* rgb_dev,
+                                float* disp_dev, float* acc_dev, float* depth_dev, uint32_t* visited_dev, void* stream) {
+    return render("mi_vox_render_sparse_signed", true, true, grid, B, fmt, sigma_dev, table_dev, slot_dev, M, skip_dev, rays_dev, n, cfg, rgb_dev, disp_dev,
+                  acc_dev, depth_dev, visited_dev, stream);
 }
 
 }  // extern "C"

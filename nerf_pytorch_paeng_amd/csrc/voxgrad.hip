@@ -17,6 +17,9 @@
 //                          0 issues no add: a sample with w_k == 0 costs no coefficient traffic.
 //                          The adds are fp32 hardware atomics without return (global_atomic_add_f32): the one entry of the project whose
 //                          result depends on arrival order in its last bits.
+//                          The rule's domain is a signed plane as well (the header's Signed paragraph): both marches take
+//                          sigma_s = fmaxf(the group's sum, 0), and march 2 adds w_e dL/d sigma_s only where that sum is >= 0.  On a plane
+//                          that is >= 0 neither changes a bit.
 //
 // No host synchronisation, no copy, no allocation.  Compiled with -ffp-contract=off: the rule is evaluated as it is written.
 #include <hip/hip_runtime.h>
@@ -179,7 +182,7 @@ __global__ __launch_bounds__(THREADS) void backward_kernel(const BackArgs a) {
                 const long long at = ((long long)(s.c[2] + ez) * g.P[1] + (s.c[1] + ey)) * g.P[0] + (s.c[0] + ex);
                 const float wx = ex ? s.f[0] : 1.0f - s.f[0], wy = ey ? s.f[1] : 1.0f - s.f[1], wz = ez ? s.f[2] : 1.0f - s.f[2];
                 const float w = (wx * wy) * wz;
-                const float sigma_s = group_sum(w * a.sigma[at]);
+                const float sigma_s = fmaxf(group_sum(w * a.sigma[at]), 0.0f);             // A SIGNED GRID: the ReLU after the interpolation
                 const float delta = (s.bk - s.ak) * L;
                 const float alpha = 1.0f - expf(-(sigma_s * delta));
                 const float wt = T * alpha;
@@ -216,7 +219,8 @@ __global__ __launch_bounds__(THREADS) void backward_kernel(const BackArgs a) {
                 }
                 const float wx = ex ? s.f[0] : 1.0f - s.f[0], wy = ey ? s.f[1] : 1.0f - s.f[1], wz = ez ? s.f[2] : 1.0f - s.f[2];
                 const float w = (wx * wy) * wz;
-                const float sigma_s = group_sum(w * a.sigma[at]);
+                const float raw_s = group_sum(w * a.sigma[at]);
+                const float sigma_s = fmaxf(raw_s, 0.0f);
                 const float delta = (s.bk - s.ak) * L;
                 const float alpha = 1.0f - expf(-(sigma_s * delta));
                 const float wt = T * alpha;
@@ -229,7 +233,7 @@ __global__ __launch_bounds__(THREADS) void backward_kernel(const BackArgs a) {
                 }
                 const float sk = (((G[0] * col[0] + G[1] * col[1]) + G[2] * col[2]) + gap) + gd * s.mk;
                 const float dsig = delta * (T * sk - (S - P));
-                ps += w * dsig;
+                if (raw_s >= 0.0f) ps += w * dsig;             // nothing flows through the ReLU where the interpolation is negative; 0 keeps the one-sided value
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) {
                     const float gq = (q[ch] >= 0.0f && q[ch] <= 1.0f) ? wt * G[ch] : 0.0f;
